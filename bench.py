@@ -8,7 +8,12 @@ rescoring merge -> (N > 1) RCCL all-gather of the per-shard top-15 over xGMI + G
 The corpus is fixed at 10M rows and sharded over the N ranks (strong scaling), contiguous
 row ranges, identical data for every N (1M-row chunks, each from its own seed).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+       A plain run sets up, warms up, times the K steps and prints the line. --full adds what
+       takes work of its own after the timed region: the certified exactness / recall check of
+       every timed batch, the CPU baseline, the standalone scan timing and the config-2 /
+       config-3 legs. --dump-outputs DIR writes the last timed step's result (scores.npy,
+       ids.npy) for an output-for-output comparison of two builds.
        N > 1 either under a launcher that sets WORLD_SIZE / RANK / LOCAL_RANK
        (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...), or
        plain `python bench.py --gpus N`: the process then starts N rank processes itself
@@ -40,6 +45,18 @@ HBM_PEAK = 8.0e12   # B/s, MI355X_MICROARCH.md chip table (spec)
 # scan-kernel HIP events on every PROF_EVERY-th step of the timed region (an event record
 # idles the queue for a few us; sampling keeps the timed steps unperturbed)
 PROF_EVERY = 4
+# --full certifies every timed batch up to this many; of a longer run, this many batches evenly
+# spaced over the timed steps, the first and the last among them (a batch takes ~0.4 s of
+# host time to certify, so the check of a run of thousands of steps stays at ~20 s)
+CHECK_MAX = 50
+
+
+def checked_steps(steps: int) -> np.ndarray:
+    """Timed steps that --full certifies: all of them up to CHECK_MAX, else CHECK_MAX evenly
+    spaced ones from the first to the last."""
+    if steps <= CHECK_MAX:
+        return np.arange(steps)
+    return np.unique(np.linspace(0, steps - 1, CHECK_MAX).round().astype(np.int64))
 
 
 def gen_chunk(c: int, dev, rows: int = CHUNK) -> torch.Tensor:
@@ -69,21 +86,21 @@ def make_queries(n_batches, n_total, dev):
     pure random (the non-planted case)."""
     rng = np.random.default_rng(1)
     picks = rng.integers(0, n_total, (n_batches, B))
-    need = sorted(set((picks // CHUNK).ravel().tolist()))
-    rows = {}
-    for c in need:
+    flat = picks.ravel()
+    base = torch.empty((n_batches * B, D), device=dev, dtype=torch.float32)
+    for c in sorted(set((flat // CHUNK).tolist())):
+        # one gather per chunk (a run of thousands of steps picks ~1e5 rows)
         x = gen_chunk(c, dev, chunk_rows(c, n_total))
-        sel = picks[(picks // CHUNK) == c]
-        for r in np.unique(sel):
-            rows[int(r)] = x[int(r) - c * CHUNK].clone()
+        at = np.nonzero(flat // CHUNK == c)[0]
+        base[torch.from_numpy(at).to(dev)] = x[torch.from_numpy(flat[at] - c * CHUNK).to(dev)]
         del x
+    base = base.view(n_batches, B, D)
     g = torch.Generator(device=dev)
     g.manual_seed(2)
     qs = []
     for i in range(n_batches):
-        base = torch.stack([rows[int(r)] for r in picks[i]])
         noise = torch.randn((B, D), generator=g, device=dev)
-        q = base + 0.05 * noise if i % 4 != 3 else noise
+        q = base[i] + 0.05 * noise if i % 4 != 3 else noise
         qs.append(q.contiguous())
     return qs, picks
 
@@ -225,6 +242,17 @@ def verify_exact(idx, q, gpu_s, gpu_ids, lo, rank, world, dev):
     return r5, ok
 
 
+def dump_outputs(out_dir: str, scores, ids) -> None:
+    """--dump-outputs: what the caller of the timed path received from its last timed step,
+    the [B, k] scores and global row ids of one batch, as scores.npy (float32) and ids.npy
+    (float64: row ids are far below 2^53, so the conversion is exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"),
+            np.ascontiguousarray(scores.detach().cpu().numpy(), dtype=np.float32))
+    np.save(os.path.join(out_dir, "ids.npy"),
+            np.ascontiguousarray(ids.detach().cpu().numpy(), dtype=np.float64))
+
+
 def _free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -305,8 +333,22 @@ def main():
                          "hipGraphs are captured per padded shape and per stream, so the "
                          "pipelines need a few batches per stream to reach steady state)")
     ap.add_argument("--rows", type=int, default=10_000_000)
-    ap.add_argument("--no-recall", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="the headline line with everything beside its figure: the certified "
+                         "exactness / recall check of every timed batch (of more than 50, an "
+                         "evenly spaced 50), the CPU baseline, the "
+                         "standalone scan timing and the config-2 / config-3 legs, all after "
+                         "the timed region (a plain run leaves their keys null / skipped). "
+                         "The --config lines are runs of their own and do not need it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's result as "
+                         "DIR/scores.npy (float32 [batch, k]) and DIR/ids.npy (float64 "
+                         "[batch, k] global rows); the inputs are seeded, so two builds run "
+                         "with the same arguments can be compared output for output")
+    ap.add_argument("--no-recall", action="store_true",
+                    help="with --full: without the exactness / recall check")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--streams", type=int, default=0,
                     help="batches in flight (0 = by shard size: 4 below 4M rows per GPU, "
@@ -363,6 +405,8 @@ def main():
         # process touches the GPU; rank 0 prints the line
         sys.exit(launch_ranks(world, sys.argv[1:]))
     if args.config != "4":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is for the headline line (--config 4)")
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         import bench_modes
         if args.rows == 10_000_000:
@@ -508,6 +552,8 @@ def main():
     alone_ms = scan_avg_ms
     if partition is not None:
         alone_ms = None        # a partition's scan alone runs on 1/n of the CUs: not comparable
+    elif len(streams) > 1 and not serial and not args.full:
+        alone_ms = None        # a run of its own: --full
     elif len(streams) > 1 and not serial:
         torch.cuda.synchronize()
         idx.profile(True)
@@ -522,29 +568,35 @@ def main():
                          dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, scan_avg_ms, alone_ms, busy_ms = (float(v) for v in t.tolist())
-        alone_ms = alone_ms if partition is None else None
+        alone_ms = alone_ms or None
+    if rank == 0 and args.dump_outputs and outs:
+        dump_outputs(args.dump_outputs, *outs[-1])
 
     check = None
-    if not args.no_recall:
-        # every timed batch (planted and pure-random), after the timed region
-        q_all = torch.cat(qs[args.warmup:args.warmup + args.steps])
-        g_s = torch.cat([o[0] for o in outs]).cpu().numpy()
-        g_i = torch.cat([o[1] for o in outs]).cpu().numpy()
+    if args.full and not args.no_recall:
+        # every timed batch (planted and pure-random; of more than CHECK_MAX, an evenly
+        # spaced CHECK_MAX of them), after the timed region
+        chk = checked_steps(args.steps)
+        n_chk = len(chk)
+        q_all = torch.cat([qs[args.warmup + int(k)] for k in chk])
+        g_s = torch.cat([outs[int(k)][0] for k in chk]).cpu().numpy()
+        g_i = torch.cat([outs[int(k)][1] for k in chk]).cpu().numpy()
         res = verify_exact(idx, q_all.cpu().numpy(), g_s, g_i, lo, rank, world, dev)
         r32 = recall_fp32(q_all, g_i, lo, hi, n_total, rank, world, dev)
         if rank == 0:
             r5, ok = res
-            per_b = r5.reshape(args.steps, B).mean(1)
-            ok_b = ok.reshape(args.steps, B).all(1)
-            f32_b = r32.reshape(args.steps, B).mean(1)
+            per_b = r5.reshape(n_chk, B).mean(1)
+            ok_b = ok.reshape(n_chk, B).all(1)
+            f32_b = r32.reshape(n_chk, B).mean(1)
             check = {"recall_at_5": round(float(r5.mean()), 6),
                      "recall_at_5_min": round(float(per_b.min()), 6),
-                     "exact_batches": f"{int(ok_b.sum())}/{args.steps}",
+                     "exact_batches": f"{int(ok_b.sum())}/{n_chk}",
+                     "all_exact": bool(ok_b.all()),
                      "recall_at_5_vs_fp32_corpus": round(float(r32.mean()), 6),
                      "recall_at_5_vs_fp32_corpus_min": round(float(f32_b.min()), 6)}
 
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # at every N (north_star: the CPU path "in the same run"), rank 0, after the timed
         # region: the whole-corpus CPU rate, from a sample of rank 0's shard
         sample = idx.export_rows(0, min(CHUNK, hi - lo))
@@ -600,7 +652,7 @@ def main():
             "recall_at_5": check and check["recall_at_5"],
             "recall_at_5_min": check and check["recall_at_5_min"],
             "exact_batches": check and check["exact_batches"],
-            "top15_exact_vs_oracle": check and check["exact_batches"] == f"{args.steps}/{args.steps}",
+            "top15_exact_vs_oracle": check and check["all_exact"],
             "recall_at_5_vs_fp32_corpus": check and check["recall_at_5_vs_fp32_corpus"],
             "recall_at_5_vs_fp32_corpus_min": check and check["recall_at_5_vs_fp32_corpus_min"],
             "exactness_fallbacks": {"queries": B * args.steps, "tier1_list_rescoring": tier1,
@@ -643,11 +695,13 @@ def main():
         # 1M x 384) after the headline's timed region, each with its own parity legs,
         # rooflines and CPU baseline, as extra keys; value / ms_per_step stay the headline's.
         # N = 1 only (at N > 1 every rank would run its own replica of them).
-        legs_on = world == 1 and not rehearsal and not args.no_configs
+        legs_on = args.full and world == 1 and not rehearsal and not args.no_configs
         leg_fn = _config_leg_inproc if args.legs == "inproc" else _config_leg
         for cfg in ("2", "3"):
             line[f"config{cfg}"] = (leg_fn(args, cfg) if legs_on else
-                                    {"skipped": "--no-configs" if args.no_configs else
+                                    {"skipped": "plain run (--full measures it)"
+                                     if not args.full else
+                                     "--no-configs" if args.no_configs else
                                      "N > 1 (measured by the N = 1 run)"})
         print(json.dumps(line), flush=True)
 

@@ -241,3 +241,67 @@ def test_bench_py_help_renders():
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     assert "--legs" in r.stdout and "--certify" in r.stdout
+
+
+def test_bench_py_help_names_full_and_dump_outputs():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: scores.npy float32 and ids.npy float64 ([B, k], ids exact), into a
+    directory that need not exist yet; a second dump of the same result is identical."""
+    g = torch.Generator()
+    g.manual_seed(7)
+    s = torch.randn((bench.B, bench.K_TOP), generator=g)
+    i = torch.randint(0, 10_000_000, (bench.B, bench.K_TOP), generator=g, dtype=torch.int64)
+    i[0, 0] = 9_999_999
+    for d in (tmp_path / "a" / "b", tmp_path / "c"):
+        bench.dump_outputs(str(d), s, i)
+        assert sorted(p.name for p in d.iterdir()) == ["ids.npy", "scores.npy"]
+    got_s, got_i = np.load(tmp_path / "c" / "scores.npy"), np.load(tmp_path / "c" / "ids.npy")
+    assert got_s.dtype == np.float32 and got_i.dtype == np.float64
+    assert got_s.shape == got_i.shape == (bench.B, bench.K_TOP)
+    assert np.array_equal(got_s, s.numpy())
+    assert np.array_equal(got_i.astype(np.int64), i.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "b" / "ids.npy"), got_i)
+
+
+def test_dump_outputs_is_headline_only():
+    """`bench.py --config 2 --dump-outputs DIR` is refused before any GPU or data work."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2",
+                        "--dump-outputs", "unused"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0
+    assert "--dump-outputs" in r.stderr
+
+
+def test_checked_steps_all_then_evenly_spaced():
+    """--full certifies every timed batch up to CHECK_MAX, then CHECK_MAX evenly spaced ones
+    that include the first and the last timed step."""
+    m = bench.CHECK_MAX
+    assert list(bench.checked_steps(1)) == [0]
+    assert list(bench.checked_steps(m)) == list(range(m))
+    for steps in (m + 1, 777, 20000):
+        c = bench.checked_steps(steps)
+        assert len(c) == m and c[0] == 0 and c[-1] == steps - 1
+        assert (np.diff(c) >= 1).all() and np.diff(c).max() - np.diff(c).min() <= 1
+
+
+def test_make_queries_rows_and_noise(small_chunks):
+    """Planted batches are the picked corpus rows + 0.05 x the seeded noise, every 4th batch
+    the noise alone; the picks span several chunks and repeat rows."""
+    n, nb = 2500, 9
+    dev = torch.device("cpu")
+    qs, picks = bench.make_queries(nb, n, dev)
+    assert picks.shape == (nb, bench.B) and len(set((picks // bench.CHUNK).ravel())) == 3
+    x = _corpus(small_chunks, n)
+    g = torch.Generator()
+    g.manual_seed(2)
+    for i in range(nb):
+        noise = torch.randn((bench.B, bench.D), generator=g)
+        want = x[torch.from_numpy(picks[i])] + 0.05 * noise if i % 4 != 3 else noise
+        assert torch.equal(qs[i], want)
