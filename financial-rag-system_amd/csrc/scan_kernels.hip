@@ -2724,36 +2724,72 @@ __global__ __launch_bounds__(64) void mark_unanswered_kernel(int* __restrict__ t
 }
 
 // ----------------------------------------------------------------------------------------
-// merge of exact per-shard lists (after the RCCL all-gather): [n_lists][B][k] -> [B][k]
+// merge of exact per-shard lists: n_lists x [B][k] -> [B][k]
 // ----------------------------------------------------------------------------------------
-// PACKED: input is the [n_lists][B][k][2] int32 (score bits, row) exchange format of
-// rag_index_search_packed (one all-gather instead of two); in_s then points at it.
+// Where the lists lie is a fetch policy: fetch(l, b, pos, s, id) loads entry `pos` of list l
+// for query b and leaves (s, id) alone where that entry is padding (id < 0).
+//
+// StackedLists: one contiguous [n_lists][B][k] array, as an RCCL all-gather leaves it. PACKED:
+// the [n_lists][B][k][2] int32 (score bits, row) exchange format of rag_index_search_packed
+// (one all-gather instead of two); in_s then points at it.
 template <bool PACKED>
-__global__ __launch_bounds__(64) void merge_exact_kernel(const float* __restrict__ in_s,
-                                                         const int64_t* __restrict__ in_i,
-                                                         int n_lists, int B, int k,
-                                                         float* __restrict__ out_s,
-                                                         int64_t* __restrict__ out_i) {
+struct StackedLists {
+  const float* __restrict__ in_s;
+  const int64_t* __restrict__ in_i;
+  int B, k;
+  __device__ __forceinline__ void operator()(int l, int b, int pos, float& s, int64_t& id) const {
+    const int64_t off = ((int64_t)l * B + b) * k + pos;
+    if constexpr (PACKED) {
+      const int2 pv = reinterpret_cast<const int2*>(in_s)[off];
+      if (pv.y >= 0) {
+        s = __int_as_float(pv.x);
+        id = pv.y;
+      }
+    } else {
+      const int64_t v = in_i[off];
+      if (v >= 0) {
+        s = in_s[off];
+        id = v;
+      }
+    }
+  }
+};
+
+// GatheredLists: n separate packed [B][k][2] lists of shard-local rows (the shard set,
+// rag_shardset_search: every shard's list stays where its search or its peer copy wrote it).
+// The table travels in the kernel arguments (~1 KB), so no search uploads one; a valid local
+// row becomes the global id local * mul + add[l].
+constexpr int kMaxShards = 64;   // RAG_MAX_SHARDS
+struct GatheredLists {
+  const int2* list[kMaxShards];
+  int64_t add[kMaxShards];
+  int64_t mul;
+  int k;
+  __device__ __forceinline__ void operator()(int l, int b, int pos, float& s, int64_t& id) const {
+    const int2 pv = list[l][(int64_t)b * k + pos];
+    if (pv.y >= 0) {
+      s = __int_as_float(pv.x);
+      id = (int64_t)pv.y * mul + add[l];
+    }
+  }
+  // out_empty[l * B + b] = 1 when list l holds nothing for query b (lists are best-first, so
+  // its first id says so): one lane per list, the first kMaxShards threads of the workgroup
+  __device__ __forceinline__ void flag_empty(int n_lists, int B, int b, uint8_t* out_empty) const {
+    const int l = threadIdx.x;
+    if (out_empty && l < n_lists) out_empty[l * B + b] = list[l][(int64_t)b * k].y < 0 ? 1 : 0;
+  }
+};
+
+// k <= 32: one wave per query; lanes 0-31 hold the running best, lanes 32-63 the next list
+template <class Fetch>
+__device__ __forceinline__ void merge_exact_body(const Fetch& fetch_list, int n_lists, int k,
+                                                 float* __restrict__ out_s,
+                                                 int64_t* __restrict__ out_i) {
   const int b = blockIdx.x, lane = threadIdx.x;
   auto fetch = [&](int l, int pos, float& s, int64_t& id) {
     s = kNegInf;
     id = INT64_MAX;
-    if (l < n_lists && pos < k) {
-      const int64_t off = ((int64_t)l * B + b) * k + pos;
-      if constexpr (PACKED) {
-        const int2 pv = reinterpret_cast<const int2*>(in_s)[off];
-        if (pv.y >= 0) {
-          s = __int_as_float(pv.x);
-          id = pv.y;
-        }
-      } else {
-        const int64_t v = in_i[off];
-        if (v >= 0) {
-          s = in_s[off];
-          id = v;
-        }
-      }
-    }
+    if (l < n_lists && pos < k) fetch_list(l, b, pos, s, id);
   };
   float s;
   int64_t id;
@@ -2774,43 +2810,40 @@ __global__ __launch_bounds__(64) void merge_exact_kernel(const float* __restrict
   }
 }
 
-// the same merge for 32 < k <= kLkMerge (the large-k path's exchange, round 5): one 256-thread
-// workgroup per query keeps the running best k in LDS; each further list's k entries go beside
-// them and a bitonic sort of the 2k by (score desc, row asc) keeps the first k
-constexpr int kLkMerge = 4096;
 template <bool PACKED>
-__global__ __launch_bounds__(256) void merge_large_kernel(const float* __restrict__ in_s,
-                                                          const int64_t* __restrict__ in_i,
-                                                          int n_lists, int B, int k,
-                                                          float* __restrict__ out_s,
-                                                          int64_t* __restrict__ out_i) {
-  __shared__ float ms[2 * kLkMerge];
-  __shared__ int64_t mi[2 * kLkMerge];
+__global__ __launch_bounds__(64) void merge_exact_kernel(const float* __restrict__ in_s,
+                                                         const int64_t* __restrict__ in_i,
+                                                         int n_lists, int B, int k,
+                                                         float* __restrict__ out_s,
+                                                         int64_t* __restrict__ out_i) {
+  merge_exact_body(StackedLists<PACKED>{in_s, in_i, B, k}, n_lists, k, out_s, out_i);
+}
+
+__global__ __launch_bounds__(64) void merge_gather_kernel(const GatheredLists lists, int n_lists,
+                                                          int B, float* __restrict__ out_s,
+                                                          int64_t* __restrict__ out_i,
+                                                          uint8_t* __restrict__ out_empty) {
+  merge_exact_body(lists, n_lists, lists.k, out_s, out_i);
+  lists.flag_empty(n_lists, B, blockIdx.x, out_empty);
+}
+
+// the same merge for 32 < k <= kLkMerge (the large-k path's exchange, round 5): one 256-thread
+// workgroup per query keeps the running best k in LDS (ms / mi, 2 * kLkMerge entries each);
+// each further list's k entries go beside them and a bitonic sort of the 2k by (score desc,
+// row asc) keeps the first k
+constexpr int kLkMerge = 4096;
+template <class Fetch>
+__device__ __forceinline__ void merge_large_body(const Fetch& fetch_list, int n_lists, int k,
+                                                 float* ms, int64_t* mi,
+                                                 float* __restrict__ out_s,
+                                                 int64_t* __restrict__ out_i) {
   const int b = blockIdx.x;
   int P = 1;
   while (P < 2 * k) P <<= 1;
-  auto fetch = [&](int l, int pos, float& s, int64_t& id) {
-    s = kNegInf;
-    id = INT64_MAX;
-    const int64_t off = ((int64_t)l * B + b) * k + pos;
-    if constexpr (PACKED) {
-      const int2 pv = reinterpret_cast<const int2*>(in_s)[off];
-      if (pv.y >= 0) {
-        s = __int_as_float(pv.x);
-        id = pv.y;
-      }
-    } else {
-      const int64_t v = in_i[off];
-      if (v >= 0) {
-        s = in_s[off];
-        id = v;
-      }
-    }
-  };
   for (int i = threadIdx.x; i < P; i += 256) {
     float s = kNegInf;
     int64_t id = INT64_MAX;
-    if (i < k) fetch(0, i, s, id);
+    if (i < k) fetch_list(0, b, i, s, id);
     ms[i] = s;
     mi[i] = id;
   }
@@ -2820,7 +2853,7 @@ __global__ __launch_bounds__(256) void merge_large_kernel(const float* __restric
     for (int i = threadIdx.x; i < P - k; i += 256) {
       float s = kNegInf;
       int64_t id = INT64_MAX;
-      if (i < k) fetch(l, i, s, id);
+      if (i < k) fetch_list(l, b, i, s, id);
       ms[k + i] = s;
       mi[k + i] = id;
     }
@@ -2851,6 +2884,43 @@ __global__ __launch_bounds__(256) void merge_large_kernel(const float* __restric
     const bool ok = s != kNegInf;
     out_s[(int64_t)b * k + j] = s;
     out_i[(int64_t)b * k + j] = ok ? mi[j] : (int64_t)-1;
+  }
+}
+
+template <bool PACKED>
+__global__ __launch_bounds__(256) void merge_large_kernel(const float* __restrict__ in_s,
+                                                          const int64_t* __restrict__ in_i,
+                                                          int n_lists, int B, int k,
+                                                          float* __restrict__ out_s,
+                                                          int64_t* __restrict__ out_i) {
+  __shared__ float ms[2 * kLkMerge];
+  __shared__ int64_t mi[2 * kLkMerge];
+  merge_large_body(StackedLists<PACKED>{in_s, in_i, B, k}, n_lists, k, ms, mi, out_s, out_i);
+}
+
+__global__ __launch_bounds__(256) void merge_gather_large_kernel(
+    const GatheredLists lists, int n_lists, int B, float* __restrict__ out_s,
+    int64_t* __restrict__ out_i, uint8_t* __restrict__ out_empty) {
+  __shared__ float ms[2 * kLkMerge];
+  __shared__ int64_t mi[2 * kLkMerge];
+  merge_large_body(lists, n_lists, lists.k, ms, mi, out_s, out_i);
+  lists.flag_empty(n_lists, B, blockIdx.x, out_empty);
+}
+
+// Unpacked shard-set path (k > kLkMerge, or the full exact pass): the stacked local ids
+// [n_lists][B][k] become global in place, list l's id -> id * mul + l (-1 stays -1), and
+// out_empty[l * B + b] (may be NULL) says whether list l holds nothing for query b.
+// Grid: (blocks over B * k, n_lists).
+__global__ __launch_bounds__(256) void remap_ids_kernel(int64_t* __restrict__ ids, int B, int k,
+                                                        int64_t mul,
+                                                        uint8_t* __restrict__ out_empty) {
+  const int l = blockIdx.y;
+  const int64_t n = (int64_t)B * k;
+  int64_t* list = ids + (int64_t)l * n;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+    const int64_t id = list[j];
+    if (id >= 0) list[j] = id * mul + l;
+    if (out_empty && j % k == 0) out_empty[(int64_t)l * B + j / k] = id < 0 ? 1 : 0;
   }
 }
 

@@ -115,6 +115,14 @@ INDEX_API = {
                                       c_vp, c_vp, c_vp]),
     "rag_merge_topk_packed": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              c_vp, c_vp, c_vp]),
+    "rag_merge_topk_gather": (ctypes.c_int, [ctypes.POINTER(c_vp), ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int64, c_i64p, c_vp, c_vp,
+                                             c_vp, c_vp]),
+    "rag_shardset_create": (ctypes.c_int, [ctypes.POINTER(c_vp), ctypes.c_int,
+                                           ctypes.POINTER(c_vp)]),
+    "rag_shardset_destroy": (ctypes.c_int, [c_vp]),
+    "rag_shardset_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp,
+                                           ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "rag_bench_scan": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(ctypes.c_double)]),
     "rag_index_set_scan_order": (ctypes.c_int, [c_vp, ctypes.c_int]),

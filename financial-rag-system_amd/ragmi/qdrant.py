@@ -32,6 +32,7 @@ import torch
 
 from . import qdrant_models as models
 from .index import MAX_K, FlatIndex
+from .shardset import ShardSet, parse_devices
 
 DEFAULT_TAG_FIELDS = ("ticker", "document_type")
 
@@ -226,14 +227,19 @@ def _storage_of(vectors_config) -> str:
 
 
 class Collection:
-    """One COSINE collection: FlatIndex in HBM + host-side id/payload maps."""
+    """One COSINE collection: FlatIndex in HBM + host-side id/payload maps. With `devices`
+    (one device index per shard, ragmi.shardset.parse_devices) the rows are striped over a
+    ShardSet instead; rows, ids, payloads and tags stay global and host-side either way."""
 
     def __init__(self, name: str, dim: int, device, tag_fields=DEFAULT_TAG_FIELDS,
-                 capacity: int = 1024, storage: str = "fp32"):
+                 capacity: int = 1024, storage: str = "fp32", devices=None):
         self.name = name
         self.dim = dim
         self.tags = PayloadTags(tag_fields)
-        self.index = FlatIndex(dim=dim, capacity=capacity, device=device, storage=storage)
+        devices = parse_devices(devices)
+        self.index = (ShardSet(dim=dim, devices=devices, capacity=capacity, storage=storage)
+                      if devices is not None else
+                      FlatIndex(dim=dim, capacity=capacity, device=device, storage=storage))
         self.id_to_row: dict[Any, int] = {}
         self.row_ids: list[Any] = []
         self.payloads: list[dict | None] = []
@@ -304,10 +310,19 @@ class Collection:
             q = q[live] if len(live) != B else q
             fl = np.asarray([filters[i] for i in live], dtype=np.uint32).reshape(-1, 2)
             use = fl if fl.any() else None
-            s, ids = self.index.search(q, k, filters=use)
+            sharded = isinstance(self.index, ShardSet)
+            if sharded:
+                # a shard that left a query unanswered hands the merge an all -1 list, which
+                # the merged top-k does not show: the set reads its per-shard flags and
+                # re-answers those queries itself (ShardSet.search, rescue)
+                before = self.index.rescued
+                s, ids = self.index.search(q, k, filters=use, rescue=True)
+                self.rescued += self.index.rescued - before
+            else:
+                s, ids = self.index.search(q, k, filters=use)
             s = s.cpu().numpy()
             ids = ids.cpu().numpy()
-            if (ids < 0).any():
+            if not sharded and (ids < 0).any():
                 # a -1 is padding (fewer matching points than k) unless the pass left the
                 # query unanswered (tier 3: more than 16384 rows tied within the error band
                 # of its k-th best on the large-k pass). Only then, re-run those queries on
@@ -340,9 +355,13 @@ class QdrantClient:
     """In-process, GPU-resident replacement for qdrant_client.QdrantClient."""
 
     def __init__(self, url: str | None = None, *args, device=None, path: str | None = None,
-                 coalesce: bool = True, coalesce_window_s: float = 0.0, **kwargs):
+                 coalesce: bool = True, coalesce_window_s: float = 0.0, devices=None, **kwargs):
         self.url = url
         self.device = device
+        # devices: None = every collection is one FlatIndex on `device`; a list of device
+        # indices (or "all") = every collection is a ShardSet with one shard per entry, the
+        # first being the merge device (a repeated index: logical shards on one GPU)
+        self.devices = parse_devices(devices)
         self.path = path
         # concurrent query_points calls share GPU scans (Coalescer); coalesce=False searches
         # every call on its own
@@ -355,7 +374,7 @@ class QdrantClient:
             for name in sorted(os.listdir(path)):
                 d = os.path.join(path, name)
                 if os.path.isfile(os.path.join(d, "collection.json")):
-                    col = load_collection(d, device)
+                    col = load_collection(d, device, devices=self.devices)
                     col.coalescer.window = self.coalesce_window_s
                     self._collections[col.name] = col
 
@@ -396,7 +415,8 @@ class QdrantClient:
             if collection_name in self._collections:
                 raise ValueError(f"collection {collection_name!r} already exists")
             col = Collection(collection_name, int(vectors_config.size), self.device,
-                             tuple(payload_tag_fields), capacity, storage)
+                             tuple(payload_tag_fields), capacity, storage,
+                             devices=self.devices)
             col.coalescer.window = self.coalesce_window_s
             self._collections[collection_name] = col
         return True

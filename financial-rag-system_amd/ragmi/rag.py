@@ -18,7 +18,9 @@ plus the batched forms a rewritten main2.batch_processor uses (SURVEY §8f rows 
 Models come from local directories (env RAGMI_BGE_DIR, RAGMI_CE_DIR: config.json +
 model.safetensors + vocab.txt) — the reference's hub names cannot be fetched here. Env
 RAGMI_STORAGE (optional) points the in-HBM collection at an on-disk shard directory
-(ragmi.store), the role of the reference's Qdrant storage volume.
+(ragmi.store), the role of the reference's Qdrant storage volume. Env RAGMI_DEVICES (optional,
+"0,1,2,3" or "all") stripes the collection over several GPUs of the node from this one
+process (ragmi.shardset); the functions below do not change.
 """
 from __future__ import annotations
 
@@ -82,8 +84,10 @@ def get_qdrant():
         return None
     from .qdrant import QdrantClient
     # RAGMI_STORAGE: directory of saved collections (the Qdrant volume's role); loaded here,
-    # written back by QdrantClient.save()/close()
-    return QdrantClient(url=QDRANT_URL, path=os.environ.get("RAGMI_STORAGE") or None)
+    # written back by QdrantClient.save()/close(). RAGMI_DEVICES ("0,1,2,3" or "all"): the
+    # collections are striped over these GPUs (ragmi.shardset); unset: one GPU
+    return QdrantClient(url=QDRANT_URL, path=os.environ.get("RAGMI_STORAGE") or None,
+                        devices=os.environ.get("RAGMI_DEVICES") or None)
 
 
 # ------------------------------------------------------------------ stage 1: embed

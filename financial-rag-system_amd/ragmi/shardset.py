@@ -1,0 +1,346 @@
+"""ShardSet — N FlatIndex shards on one or several GPUs, searched as one index from ONE process.
+
+The reference service is one process whose every request reaches the index through
+`get_qdrant().query_points(...)` (main.py:92-95, 232-237). `ragmi.dist.ShardedIndex` shards
+over one process per GPU under torch.distributed; a ShardSet shards inside the process, so
+`QdrantClient(devices=[0, 1, ...])` serves one collection from several GPUs behind the same
+calls (rag_shardset_search, include/ragmi.h).
+
+Row placement is striped: global row g lives on shard g % N at local row g // N. A Qdrant
+collection grows by `upsert` with no total known in advance (ingest.py:171-175); contiguous
+ranges would fill GPU 0 first, stripes fill every shard evenly at every size. Within a shard
+local order is global order, so each shard's exact top-k by (score desc, local row asc) is
+its exact top-k by (score desc, global row asc) and the merged list equals the unsharded one
+bit for bit. Everything here works in global rows: a ShardSet offers what `qdrant.Collection`
+and `ragmi.store` use of a FlatIndex.
+"""
+from __future__ import annotations
+
+import ctypes
+import functools
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+
+MAX_SHARDS = 64      # RAG_MAX_SHARDS in include/ragmi.h
+SHARDSET_FULL = 1    # RAG_SHARDSET_FULL
+
+
+# ------------------------------------------------------------------ placement (pure, host)
+def shard_of(row, n: int):
+    """Shard holding global row `row` (int or integer array)."""
+    return row % n
+
+
+def local_of(row, n: int):
+    """Row slot of global row `row` on its shard."""
+    return row // n
+
+
+def global_of(local, shard, n: int):
+    """Global row of local row `local` on shard `shard`."""
+    return local * n + shard
+
+
+def shard_count(count: int, shard: int, n: int) -> int:
+    """Rows of shard `shard` when the set holds global rows [0, count)."""
+    return max(0, -((shard - count) // n))
+
+
+def parse_devices(spec, device_count: int | None = None) -> list[int] | None:
+    """The `devices` argument of QdrantClient / the RAGMI_DEVICES variable -> device indices.
+    None or "" -> None (one FlatIndex on one device, no shard set); "all" -> every visible
+    device; "0,1,2,3", or a sequence of ints -> that list. An index may repeat: logical shards
+    sharing one GPU (one-GPU rehearsal, tests). `device_count` (default: what torch sees)
+    resolves "all" and bounds the indices when given."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        text = spec.strip()
+        if not text:
+            return None
+        if text.lower() == "all":
+            n = torch.cuda.device_count() if device_count is None else int(device_count)
+            if n < 1:
+                raise ValueError("devices='all': no HIP device visible")
+            return list(range(n))
+        try:
+            devs = [int(p) for p in text.split(",")]
+        except ValueError:
+            raise ValueError(f"devices {spec!r}: expected 'all' or indices like '0,1,2,3'") from None
+    else:
+        devs = []
+        for d in spec:
+            if isinstance(d, bool) or not isinstance(d, (int, np.integer)):
+                raise ValueError(f"devices {spec!r}: device indices must be ints")
+            devs.append(int(d))
+    if not 1 <= len(devs) <= MAX_SHARDS:
+        raise ValueError(f"devices {spec!r}: 1 to {MAX_SHARDS} shards")
+    for d in devs:
+        if d < 0 or (device_count is not None and d >= device_count):
+            raise ValueError(f"devices {spec!r}: no device {d}")
+    return devs
+
+
+def gather_merge_np(lists, k: int, id_mul: int, id_add):
+    """numpy restatement of rag_merge_topk_gather: `lists` = packed int32 [B, k, 2] arrays
+    (score bits, local row; -1 = none). Returns (scores [B, k], ids [B, k], empty [n, B])."""
+    n, B = len(lists), lists[0].shape[0]
+    out_s = np.full((B, k), -np.inf, np.float32)
+    out_i = np.full((B, k), -1, np.int64)
+    empty = np.zeros((n, B), np.uint8)
+    for b in range(B):
+        sc, ids = [], []
+        for l, lst in enumerate(lists):
+            row = np.ascontiguousarray(lst[b])
+            ok = row[:, 1] >= 0
+            empty[l, b] = 0 if row[0, 1] >= 0 else 1
+            sc.append(np.ascontiguousarray(row[:, 0]).view(np.float32)[ok])
+            ids.append(row[ok, 1].astype(np.int64) * id_mul + int(id_add[l]))
+        sc, ids = np.concatenate(sc), np.concatenate(ids)
+        order = np.lexsort((ids, -sc.astype(np.float64)))[:k]     # score desc, then id asc
+        out_s[b, :len(order)] = sc[order]
+        out_i[b, :len(order)] = ids[order]
+    return out_s, out_i, empty
+
+
+def merge_topk_gather(lists, k: int, id_mul: int, id_add):
+    """rag_merge_topk_gather over separate packed lists (cuda int32 [B, k, 2] tensors on one
+    device). Returns (scores [B, k], ids [B, k], empty uint8 [n_lists, B]) on the current
+    stream."""
+    L = _lib.load()
+    n = len(lists)
+    B = lists[0].shape[0]
+    dev = lists[0].device
+    for t in lists:
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, k, 2) or not t.is_contiguous():
+            raise ValueError("lists must be contiguous int32 [B, k, 2]")
+    ptrs = (_lib.c_vp * n)(*[t.data_ptr() for t in lists])
+    add = (ctypes.c_int64 * n)(*[int(a) for a in id_add])
+    out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((B, k), dtype=torch.int64, device=dev)
+    empty = torch.empty((n, B), dtype=torch.uint8, device=dev)
+    check(L.rag_merge_topk_gather(ptrs, n, B, int(k), int(id_mul), add, out_s.data_ptr(),
+                                  out_i.data_ptr(), empty.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream))
+    return out_s, out_i, empty
+
+
+# ------------------------------------------------------------------ the set
+def _keeps_device(fn):
+    """The rag_index_* calls behind a FlatIndex leave the thread's current HIP device on that
+    index's device; a method that walks shards on several devices puts the caller's back."""
+    @functools.wraps(fn)
+    def wrapped(*args, **kwargs):
+        prev = torch.cuda.current_device() if torch.cuda.is_available() else None
+        try:
+            return fn(*args, **kwargs)
+        finally:
+            if prev is not None:
+                torch.cuda.set_device(prev)
+    return wrapped
+
+
+class ShardSet:
+    """N FlatIndex shards + the C shard-set handle, addressed in global rows. `devices`: one
+    device index per shard (see parse_devices); `device`, the merge device, is the first."""
+
+    @_keeps_device
+    def __init__(self, dim: int = 384, devices=(0,), capacity: int = 0, storage: str = "fp16"):
+        from .index import FlatIndex
+        devs = parse_devices(devices)
+        if devs is None:
+            raise ValueError("ShardSet needs a list of devices")
+        _lib.require_gpu()
+        self._L = _lib.load()
+        self.n = len(devs)
+        self.dim = int(dim)
+        self.storage = storage
+        self.shards: list = []
+        self._h = None
+        per = -(-int(capacity) // self.n)
+        try:
+            for d in devs:
+                self.shards.append(FlatIndex(dim, per, torch.device("cuda", d), storage))
+            arr = (_lib.c_vp * self.n)(*[s._h.value for s in self.shards])
+            h = ctypes.c_void_p()
+            check(self._L.rag_shardset_create(arr, self.n, ctypes.byref(h)))
+            self._h = h
+        except BaseException:
+            self.close()
+            raise
+        self.device = self.shards[0].device
+        self._count = 0
+        self._unanswered = [0] * self.n   # each shard's unanswered() as last read (rescue)
+        self.rescued = 0                  # queries re-answered on the full exact pass
+
+    # ---------------------------------------------------------------- lifetime
+    @_keeps_device
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.rag_shardset_destroy(self._h)
+        self._h = None
+        for s in getattr(self, "shards", []):
+            s.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---------------------------------------------------------------- properties
+    @property
+    def count(self) -> int:
+        return self._count
+
+    @property
+    def capacity(self) -> int:
+        return min(s.capacity for s in self.shards) * self.n
+
+    @_keeps_device
+    def reserve(self, capacity: int) -> None:
+        per = -(-int(capacity) // self.n)
+        for s in self.shards:
+            if s.capacity < per:
+                s.reserve(per)
+
+    def _stripe(self, shard: int, row0: int, n: int):
+        """Global rows [row0, row0 + n) that live on `shard`: (offset of the first one in the
+        range, its local row, how many)."""
+        first = (shard - row0) % self.n
+        if first >= n:
+            return first, 0, 0
+        return first, (row0 + first) // self.n, -(-(n - first) // self.n)
+
+    def _settle(self, shard) -> None:
+        # a shard off the merge device is searched on a stream of its own, which nothing
+        # orders behind the write just enqueued on that device's current stream
+        if shard.device != self.device:
+            torch.cuda.current_stream(shard.device).synchronize()
+
+    # ---------------------------------------------------------------- writes
+    @_keeps_device
+    def upsert(self, vectors, rows, tags=None, new_count: int | None = None) -> None:
+        """FlatIndex.upsert in global rows: each row goes to its shard."""
+        r = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        r = r.astype(np.int64).reshape(-1)
+        v = vectors if isinstance(vectors, torch.Tensor) else np.asarray(vectors, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.dim or v.shape[0] != r.shape[0]:
+            raise ValueError(f"vectors must be [n, {self.dim}] with one row slot each")
+        if r.size and (int(r.min()) < 0 or int(r.max()) >= self.capacity):
+            raise IndexError("row slot outside capacity; reserve() first")
+        t = None
+        if tags is not None:
+            t = (tags.detach().cpu().numpy().view(np.uint32) if isinstance(tags, torch.Tensor)
+                 else np.asarray(tags, dtype=np.uint32))
+        if new_count is None:
+            new_count = max(self._count, int(r.max()) + 1 if r.size else 0)
+        for s, shard in enumerate(self.shards):
+            sel = np.nonzero(shard_of(r, self.n) == s)[0]
+            cnt = shard_count(new_count, s, self.n)
+            if sel.size:
+                vs = v[torch.as_tensor(sel, device=v.device)] if isinstance(v, torch.Tensor) \
+                    else v[sel]
+                shard.upsert(vs, local_of(r[sel], self.n), t[sel] if t is not None else None,
+                             new_count=cnt)
+            elif shard.count != cnt:
+                shard.set_count(cnt)
+            self._settle(shard)
+        self._count = int(new_count)
+
+    # ---------------------------------------------------------------- search
+    @_keeps_device
+    def search(self, queries, k: int, filters=None, full: bool = False, rescue: bool = False):
+        """Top-k of each query over all shards: (scores fp32 [B, k], ids int64 [B, k], global
+        rows, -1 where fewer than k rows match) on the merge device's current stream —
+        FlatIndex.search's result on the same rows, bit for bit. full=True: every shard
+        answers by its full exact pass. rescue=True (Collection.search): read back which
+        shards returned nothing per query; where such a shard's unanswered() rose, its
+        large-k pass left the query unanswered and the merged top-k lacks that shard's rows,
+        so those queries are re-run with full=True (counted once each in `rescued`).
+        Synchronises when rescue is set."""
+        q, B, f = self.shards[0]._search_args(queries, k, filters)
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        empty = torch.empty((self.n, B), dtype=torch.uint8, device=self.device)
+        check(self._L.rag_shardset_search(
+            self._h, q.data_ptr(), B, int(k), f.data_ptr() if f is not None else None,
+            SHARDSET_FULL if full else 0, out_s.data_ptr(), out_i.data_ptr(), empty.data_ptr(),
+            torch.cuda.current_stream(self.device).cuda_stream))
+        if rescue and not full and B:
+            e = empty.cpu().numpy().astype(bool)
+            redo = np.zeros(B, bool)
+            for s in np.nonzero(e.any(axis=1))[0]:
+                n_un = self.shards[s].unanswered()
+                if n_un > self._unanswered[s]:
+                    redo |= e[s]
+                self._unanswered[s] = n_un
+            if redo.any():
+                sel = torch.as_tensor(np.nonzero(redo)[0], device=self.device)
+                s2, i2 = self.search(q[sel], k, f[sel] if f is not None else None, full=True)
+                out_s[sel] = s2
+                out_i[sel] = i2
+                self.rescued += int(redo.sum())
+        return out_s, out_i
+
+    @_keeps_device
+    def unanswered(self) -> int:
+        """Sum of the shards' FlatIndex.unanswered()."""
+        return sum(s.unanswered() for s in self.shards)
+
+    # ---------------------------------------------------------------- export / import
+    @_keeps_device
+    def _export(self, name: str, row0: int, n, shape_tail: tuple, dtype) -> np.ndarray:
+        if n is None:
+            n = self._count - row0
+        out = np.empty((n,) + shape_tail, dtype=dtype)
+        for s, shard in enumerate(self.shards):
+            first, l0, m = self._stripe(s, row0, n)
+            if m:
+                out[first::self.n] = getattr(shard, name)(l0, m)
+        return out
+
+    def export_rows(self, row0: int = 0, n: int | None = None) -> np.ndarray:
+        """Stored fp16 rows (uint16 bits) [n, dim] of global rows [row0, row0 + n)."""
+        return self._export("export_rows", row0, n, (self.dim,), np.uint16)
+
+    def export_rows32(self, row0: int = 0, n: int | None = None) -> np.ndarray:
+        return self._export("export_rows32", row0, n, (self.dim,), np.float32)
+
+    def export_tags(self, row0: int = 0, n: int | None = None) -> np.ndarray:
+        return self._export("export_tags", row0, n, (), np.uint32)
+
+    @_keeps_device
+    def _import(self, name: str, a: np.ndarray, row0: int, tags, new_count) -> None:
+        n = a.shape[0]
+        t = None
+        if tags is not None:
+            t = np.ascontiguousarray(tags, dtype=np.uint32)
+            if t.shape != (n,):
+                raise ValueError("tags must be [n]")
+        if new_count is None:
+            new_count = max(self._count, row0 + n)
+        for s, shard in enumerate(self.shards):
+            first, l0, m = self._stripe(s, row0, n)
+            cnt = shard_count(new_count, s, self.n)
+            if m:
+                getattr(shard, name)(np.ascontiguousarray(a[first::self.n]), l0,
+                                     np.ascontiguousarray(t[first::self.n]) if t is not None
+                                     else None, new_count=cnt)
+            elif shard.count != cnt:
+                shard.set_count(cnt)
+                self._settle(shard)
+        self._count = int(new_count)
+
+    def import_rows(self, rows_f16, row0: int = 0, tags=None,
+                    new_count: int | None = None) -> None:
+        """FlatIndex.import_rows in global rows: the range is de-interleaved over the shards."""
+        self._import("import_rows", np.asarray(rows_f16), row0, tags, new_count)
+
+    def import_rows32(self, rows_f32, row0: int = 0, tags=None,
+                      new_count: int | None = None) -> None:
+        self._import("import_rows32", np.asarray(rows_f32), row0, tags, new_count)

@@ -230,15 +230,17 @@ def save_collection(col, path: str) -> None:
             "codebooks": [[[v, c] for v, c in t.items()] for t in col.tags.codes]})
 
 
-def load_collection(path: str, device=None):
-    """collection directory -> qdrant.Collection (rows, tags, ids, payloads, versions)."""
+def load_collection(path: str, device=None, devices=None):
+    """collection directory -> qdrant.Collection (rows, tags, ids, payloads, versions).
+    `devices`: load into a ShardSet over these devices. The directory holds the rows in global
+    order whatever the shard count was at save time, so any count loads any directory."""
     from .qdrant import Collection
     with open(os.path.join(path, "collection.json")) as f:
         cj = json.load(f)
     meta = read_meta(os.path.join(path, "shard"))
     col = Collection(cj["name"], int(cj["dim"]), device, tuple(cj["tag_fields"]),
                      capacity=max(meta["count"], 1024),
-                     storage=cj.get("storage", meta.get("storage", "fp16")))
+                     storage=cj.get("storage", meta.get("storage", "fp16")), devices=devices)
     for f_i, book in enumerate(cj["codebooks"]):
         col.tags.codes[f_i] = {v: int(c) for v, c in book}
     with open(os.path.join(path, "points.jsonl")) as f:

@@ -195,6 +195,50 @@ int rag_merge_topk(const float* in_scores_dev, const int64_t* in_ids_dev, int n_
 int rag_merge_topk_packed(const int32_t* in_packed_dev, int n_lists, int B, int k,
                           float* out_scores_dev, int64_t* out_ids_dev, void* stream);
 
+/* The same merge over n_lists SEPARATE packed lists (each int32 [B][k][2] of shard-local rows,
+ * see rag_index_search_packed): `lists` is a host array of n_lists device pointers, and a valid
+ * local row r of list l becomes the global id r * id_mul + id_add_host[l] (int64) before the
+ * merge by (score desc, id asc) — gather, id remap and merge in one launch; the pointer table
+ * and the offsets travel in the kernel arguments, nothing is uploaded. out_empty_dev (uint8
+ * [n_lists][B], may be NULL) receives 1 where list l holds no entry for query b (its first id
+ * is -1), else 0. 1 <= n_lists <= RAG_MAX_SHARDS, 1 <= k <= RAG_MAX_K_LARGE. The merge of
+ * rag_shardset_search; no reference counterpart (the reference's Qdrant is one node). */
+#define RAG_MAX_SHARDS 64
+int rag_merge_topk_gather(const int32_t* const* lists, int n_lists, int B, int k, int64_t id_mul,
+                          const int64_t* id_add_host, float* out_scores_dev, int64_t* out_ids_dev,
+                          uint8_t* out_empty_dev, void* stream);
+
+/* Shard set: n_shards flat indexes (same dim and storage; on any devices, several may share
+ * one) searched as ONE index from one process — a Qdrant collection spanning the GPUs of a
+ * node behind the same query_points (main.py:232-237). Placement is striped: global row g
+ * lives on shard g % n_shards at local row g / n_shards, so a collection that grows by upsert
+ * (ingest.py:171-175, no total known in advance) fills every shard evenly, and local order is
+ * global order: each shard's exact top-k by (score desc, local row asc) is its exact top-k in
+ * global rows, and the merged list equals the unsharded index's bit for bit. The set borrows
+ * the shard handles: the caller upserts into them (rag_index_upsert at the local rows), keeps
+ * them alive while the set lives and destroys them afterwards. */
+typedef struct rag_shardset rag_shardset_t;
+int rag_shardset_create(rag_index_t* const* shards, int n_shards, rag_shardset_t** out);
+int rag_shardset_destroy(rag_shardset_t* set);
+/* rag_index_search over the set: out_scores_dev fp32 [B][k], out_ids_dev int64 [B][k] in
+ * global rows (-1 / -inf past the matching rows). Asynchronous on `stream`, a stream of the
+ * merge device (shard 0's), where queries, filters and outputs live. Every shard searches on a
+ * stream of its own behind `stream` (one event out, one event back per shard); a shard on
+ * another device gets the queries and filters by hipMemcpyPeerAsync and its packed list is
+ * copied back the same way (no kernel reads another GPU's memory); then one
+ * rag_merge_topk_gather launch on `stream`. k > RAG_MAX_K_LARGE, or flags & RAG_SHARDSET_FULL
+ * (every shard answers by rag_index_search_full): unpacked per-shard lists, an id-remap kernel
+ * and rag_merge_topk. out_empty_dev (uint8 [n_shards][B], may be NULL): 1 where shard s
+ * returned nothing for query b — no matching row there, or a large-k pass that left the query
+ * unanswered (rag_index_unanswered on the shard tells which; re-run such queries with
+ * RAG_SHARDSET_FULL). Re-entrant like an index: searches from several threads on several
+ * streams are safe (per-search buffers in event-guarded slots). The calling thread's current
+ * HIP device is restored on return. */
+#define RAG_SHARDSET_FULL 1
+int rag_shardset_search(rag_shardset_t* set, const float* queries_dev, int B, int k,
+                        const uint32_t* filters_dev, int flags, float* out_scores_dev,
+                        int64_t* out_ids_dev, uint8_t* out_empty_dev, void* stream);
+
 /* Exactness bookkeeping (tests, bench): tier1 / tier2 = number of queries, since the index
  * was created, whose top-k was certified by the list re-scoring fallback / needed the second
  * pass over the shard (all other queries passed the error-bound check directly).
