@@ -9,10 +9,12 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ragmi.h"
@@ -80,6 +82,135 @@ struct ProfPair {
   hipEvent_t a, b;
 };
 
+// One search pass's share of a search call: at most one pass's queries, their filters and the
+// output rows they fill (out_packed, or out_s and out_i)
+struct PassArgs {
+  const float* q;
+  int Bq, k;
+  const uint32_t* filt;
+  int64_t id_offset;
+  float* out_s;
+  int64_t* out_i;
+  int32_t* out_packed;
+};
+
+// Runtime value -> compile-time constant, handed to a generic lambda that reads it as
+// decltype(tag)::value (the idiom of bert_capi.hip): `filt != nullptr` as a bool_constant ...
+template <typename F>
+auto with_filter(const uint32_t* filt, F&& f) {
+  if (filt) return f(std::bool_constant<true>{});
+  return f(std::bool_constant<false>{});
+}
+
+// ... and the handle's dim as an integral_constant; the lambda returns the status
+template <typename F>
+int with_dim(int dim, F&& f) {
+  if (dim == 384) return f(std::integral_constant<int, 384>{});
+  if (dim == 1024) return f(std::integral_constant<int, 1024>{});
+  return ragmi::fail(RAG_EINVAL, "unsupported dim (built: 384, 1024)");
+}
+
+// The slot (Workspace, SetSlot) a call on stream `st` takes: the one bound to `st`, else the
+// first unused one. Neither: nullptr, every slot being bound to another stream whose last call
+// may still be running; `lru` is the least recently used one, for the caller to wait for and
+// rebind.
+template <typename Slot, size_t N>
+Slot* pick_slot(Slot (&slots)[N], hipStream_t st, Slot*& lru) {
+  lru = &slots[0];
+  for (auto& s : slots)
+    if (s.tick < lru->tick) lru = &s;
+  for (auto& s : slots)
+    if (s.used && s.owner == st) return &s;
+  for (auto& s : slots)
+    if (!s.used) return &s;
+  return nullptr;
+}
+
+// Transient resources of one call, released on every return path.
+// Stream-ordered scratch: freed on the stream it was allocated on
+struct StreamScratch {
+  hipStream_t st;
+  char* p = nullptr;
+  explicit StreamScratch(hipStream_t s) : st(s) {}
+  StreamScratch(const StreamScratch&) = delete;
+  ~StreamScratch() {
+    if (p) (void)hipFreeAsync(p, st);
+  }
+  hipError_t alloc(size_t bytes) { return hipMallocAsync(reinterpret_cast<void**>(&p), bytes, st); }
+};
+
+// a hipMalloc buffer; release() hands it to a longer-lived owner
+template <typename T>
+struct DeviceBuf {
+  T* p = nullptr;
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf&) = delete;
+  ~DeviceBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t bytes) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+  T* release() {
+    T* r = p;
+    p = nullptr;
+    return r;
+  }
+};
+
+// a pair of timing events
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  hipError_t create() {
+    const hipError_t e = hipEventCreate(&a);
+    return e != hipSuccess ? e : hipEventCreate(&b);
+  }
+};
+
+// *ms = device time of `reps` back-to-back calls of `one` (launches on the null stream), after
+// one warm-up call
+template <typename F>
+int time_launches(int reps, F&& one, float* ms) {
+  EventPair ev;
+  RAG_HIP(ev.create());
+  one();  // warm
+  RAG_HIP(hipEventRecord(ev.a, nullptr));
+  for (int r = 0; r < reps; ++r) one();
+  RAG_HIP(hipEventRecord(ev.b, nullptr));
+  RAG_HIP(hipEventSynchronize(ev.b));
+  RAG_HIP(hipEventElapsedTime(ms, ev.a, ev.b));
+  return RAG_OK;
+}
+
+// One device buffer of a Workspace: where its pointer lives, its size, zeroed at creation or not
+struct WsBuf {
+  void** p;
+  size_t bytes;
+  bool zero;
+};
+template <typename T>
+WsBuf ws_buf(T*& p, size_t bytes, bool zero = false) {
+  return {reinterpret_cast<void**>(&p), bytes, zero};
+}
+
+// The large-k buffers, allocated together on first use (ensure_lk)
+std::array<WsBuf, 7> lk_buffers(Workspace& w) {
+  using namespace ragmi;
+  const size_t Q = kQ;
+  return {ws_buf(w.lk_smax, Q * kLkSampleMax * 4), ws_buf(w.lk_thr, Q * 4),
+          ws_buf(w.lk_cnt, Q * 4),                 ws_buf(w.lk_again, Q * 4),
+          ws_buf(w.lk_need, 64),                   ws_buf(w.lk_cand, Q * kLkCap * 4),
+          ws_buf(w.lk_es, Q * kLkCap * 4)};
+}
+
 }  // namespace
 
 struct rag_index {
@@ -128,12 +259,41 @@ namespace {
 
 int64_t round16(int64_t n) { return (n + 15) & ~int64_t(15); }
 
+// The buffers every Workspace of `h` holds from creation to destruction (h->dim, groups and
+// max_wgs set), in allocation order: rag_index_create_ex gives each its own hipMalloc in this
+// order, rag_index_destroy frees them.
+std::array<WsBuf, 19> ws_buffers(const rag_index* h, Workspace& w) {
+  using namespace ragmi;
+  const size_t G = (size_t)h->groups, Q = kQ, dim = (size_t)h->dim;
+  const size_t max_lists = (size_t)std::min(h->max_wgs * kWavesPerWG, kMaxLists);
+  return {ws_buf(w.qn, G * Q * dim * 4),
+          ws_buf(w.qfrag, G * 2 * (dim / 32) * 64 * 16),
+          ws_buf(w.filt, G * Q * 2 * 4),
+          ws_buf(w.smax, G * (dim > 384 ? kMaxSampleWide : kMaxSample) * Q * 4),
+          ws_buf(w.heads_s, G * kMaxLists * Q * 4),
+          ws_buf(w.heads_i, G * kMaxLists * Q * 4),
+          ws_buf(w.heads_n, G * kMaxLists * Q * 4),
+          ws_buf(w.seed, G * Q * 4),
+          ws_buf(w.part_s, G * max_lists * Q * kKS * 4),
+          ws_buf(w.part_i, G * max_lists * Q * kKS * 4),
+          ws_buf(w.progress, G * kMaxLists * 4),
+          ws_buf(w.eps, G * Q * 4),
+          ws_buf(w.fb_tier, G * Q * 4, true),
+          ws_buf(w.fb_cnt, 32, true),
+          ws_buf(w.tileq, 8 * kTileQStride * 4, true),
+          ws_buf(w.t2, G * Q * 2 * 4),
+          ws_buf(w.t2_s, G * Q * kRescanMaxWG * 32 * 4),
+          ws_buf(w.t2_i, G * Q * kRescanMaxWG * 32 * 4),
+          ws_buf(w.t2_tk, 64, true)};
+}
+
 int alloc_corpus(rag_index* h, int64_t cap_rows, half8** corpus, uint32_t** tags) {
   const size_t cbytes = (size_t)cap_rows * h->dim * 2;
   RAG_HIP(hipMalloc(reinterpret_cast<void**>(corpus), std::max<size_t>(cbytes, 16)));
   if (hipMalloc(reinterpret_cast<void**>(tags), std::max<size_t>(cap_rows * 4, 16)) !=
       hipSuccess) {
     (void)hipFree(*corpus);
+    *corpus = nullptr;
     return ragmi::fail(RAG_ENOMEM, "hipMalloc(tags) failed");
   }
   RAG_HIP(hipMemset(*corpus, 0, std::max<size_t>(cbytes, 16)));
@@ -149,13 +309,6 @@ int ensure_stage(rag_index* h, size_t bytes) {
   RAG_HIP(hipMalloc(&h->stage, bytes));
   h->stage_bytes = bytes;
   return RAG_OK;
-}
-
-template <int D>
-void launch_upsert(rag_index* h, const float* v, const int64_t* rows, const uint32_t* tags,
-                   int64_t n, hipStream_t st) {
-  ragmi::upsert_kernel<D><<<dim3((unsigned)n), dim3(64), 0, st>>>(
-      v, rows, tags, h->corpus, h->tags, n, h->cap_rows, h->rows32);
 }
 
 // qprep's extra error-bound term for fp32 storage (scan_kernels.hip qprep_kernel): the exact
@@ -258,10 +411,10 @@ void launch_seed(rag_index* h, Workspace& w, int groups, hipStream_t st,
 }
 
 template <int D>
-int launch_search_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k,
-                       const uint32_t* filt, int64_t id_offset, float* out_s, int64_t* out_i,
-                       int32_t* out_packed, hipStream_t st) {
+int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_t st) {
   using namespace ragmi;
+  const uint32_t* const filt = a.filt;
+  const int Bq = a.Bq;
   // Bq <= 32 * h->groups queries: `groups` query groups of 32 (one for D <= 384)
   const int groups = (Bq + kQ - 1) / kQ;
   // fused qprep + sample only in free scan order (small shards, several scans overlapping):
@@ -270,17 +423,13 @@ int launch_search_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k
   // CU with scan workgroups, landed between a scan's workgroups and stretched the scan launch
   // (10M rows: scan 0.76 vs 0.83 of the roofline, same qps, profiles/r03i_headline_prep_ab.jsonl)
   if (D <= 384 && groups == 1 && fused_prep() && h->serial_scans == 0) {
-    if (filt)
-      launch_seed<D, true>(h, w, groups, st, q, Bq, filt);
-    else
-      launch_seed<D, false>(h, w, groups, st, q, Bq, nullptr);
+    with_filter(filt, [&](auto f) {
+      launch_seed<D, decltype(f)::value>(h, w, groups, st, a.q, Bq, filt);
+    });
   } else {
-    qprep_kernel<D><<<dim3(groups * kQ), dim3(64), 0, st>>>(q, Bq, filt, w.qn, w.qfrag, w.filt,
+    qprep_kernel<D><<<dim3(groups * kQ), dim3(64), 0, st>>>(a.q, Bq, filt, w.qn, w.qfrag, w.filt,
                                                             w.eps, store_eps(h));
-    if (filt)
-      launch_seed<D, true>(h, w, groups, st);
-    else
-      launch_seed<D, false>(h, w, groups, st);
+    with_filter(filt, [&](auto f) { launch_seed<D, decltype(f)::value>(h, w, groups, st); });
   }
   const int64_t n_tiles = (h->count + 15) / 16;
   // D <= 384: queries in VGPRs, 2 workgroups per CU; wider rows: queries in LDS, 1 per CU,
@@ -346,9 +495,11 @@ int launch_search_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k
     // the 384-d scan times its own dispatch (launch_fixed_timed below)
     if constexpr (kLdsQ) RAG_HIP(hipEventRecord(pp.a, st));
   }
-#define RAG_SCAN_ARGS                                                                    \
-  h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, (int)n_tiles, w.seed, w.part_s, w.part_i, \
-      w.heads_s, w.heads_i, w.heads_n
+  // go(the arguments scan_kernel and scan_lds_kernel share, then `tail`)
+  const auto with_scan_args = [&](auto&& go, auto... tail) {
+    return go(h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, (int)n_tiles, w.seed, w.part_s,
+              w.part_i, w.heads_s, w.heads_i, w.heads_n, tail...);
+  };
   const bool wide = kLdsQ && groups > 1 && !filt;
   if (wide) {
     // RAGMI_WIDE_WGS (diagnostic A/B): workgroup cap of the wide scan (default one per CU)
@@ -367,37 +518,44 @@ int launch_search_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k
       launch_fixed<kWideBlock>(scan_wide_kernel<D, 0, true>, dim3(grid), 0, st, h->corpus,
                                w.qfrag, (int)h->count, (int)n_tiles, w.seed, w.part_s,
                                w.part_i, w.heads_s, w.heads_i, w.heads_n, groups);
-    } else if (groups == 1) {
-      if (filt)
-        launch_fixed<kLdsBlock>(scan_lds_kernel<D, true, true>, g3, 0, st, RAG_SCAN_ARGS, groups,
-                                w.progress);
-      else
-        launch_fixed<kLdsBlock>(scan_lds_kernel<D, false, true>, g3, 0, st, RAG_SCAN_ARGS, groups,
-                                w.progress);
     } else {
-      RAG_HIP(hipMemsetAsync(w.progress, 0, (size_t)grid * kLdsWaves * groups * 4, st));
-      if (filt)
-        launch_fixed<kLdsBlock>(scan_lds_kernel<D, true, false>, g3, 0, st, RAG_SCAN_ARGS, groups,
-                                w.progress);
+      // one group: non-temporal ring loads; several: the groups share tiles through the
+      // throttle words, zeroed first
+      if (groups > 1)
+        RAG_HIP(hipMemsetAsync(w.progress, 0, (size_t)grid * kLdsWaves * groups * 4, st));
+      const auto launch = [&](auto nt) {
+        with_filter(filt, [&](auto f) {
+          with_scan_args(
+              [&](auto... args) {
+                launch_fixed<kLdsBlock>(
+                    scan_lds_kernel<D, decltype(f)::value, decltype(nt)::value>, g3, 0, st,
+                    args...);
+              },
+              groups, w.progress);
+        });
+      };
+      if (groups == 1)
+        launch(std::true_type{});
       else
-        launch_fixed<kLdsBlock>(scan_lds_kernel<D, false, false>, g3, 0, st, RAG_SCAN_ARGS, groups,
-                                w.progress);
+        launch(std::false_type{});
     }
-  } else if (timed) {
-    // the timed launch carries its own start / end timestamps (launch_fixed_timed)
-    if (filt)
-      RAG_HIP(launch_fixed_timed<kScanBlock>(scan_kernel<D, true>, dim3(grid), 0, st, pp.a, pp.b,
-                                             RAG_SCAN_ARGS, nullptr));
-    else
-      RAG_HIP(launch_fixed_timed<kScanBlock>(scan_kernel<D, false>, dim3(grid), 0, st, pp.a, pp.b,
-                                             RAG_SCAN_ARGS, nullptr));
   } else {
-    if (filt)
-      launch_fixed<kScanBlock>(scan_kernel<D, true>, dim3(grid), 0, st, RAG_SCAN_ARGS, nullptr);
-    else
-      launch_fixed<kScanBlock>(scan_kernel<D, false>, dim3(grid), 0, st, RAG_SCAN_ARGS, nullptr);
+    const int rc = with_filter(filt, [&](auto f) {
+      constexpr bool F = decltype(f)::value;
+      return with_scan_args(
+          [&](auto... args) -> int {
+            // the timed launch carries its own start / end timestamps (launch_fixed_timed)
+            if (timed)
+              RAG_HIP(launch_fixed_timed<kScanBlock>(scan_kernel<D, F>, dim3(grid), 0, st, pp.a,
+                                                     pp.b, args...));
+            else
+              launch_fixed<kScanBlock>(scan_kernel<D, F>, dim3(grid), 0, st, args...);
+            return RAG_OK;
+          },
+          nullptr);
+    });
+    if (rc) return rc;
   }
-#undef RAG_SCAN_ARGS
   if (timed) {
     if constexpr (kLdsQ) RAG_HIP(hipEventRecord(pp.b, st));
     h->prof_pairs.push_back(pp);
@@ -415,31 +573,24 @@ int launch_search_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k
   const ExactStats fb{w.fb_tier, w.fb_cnt, w.t2};
   // select certifies every query's top-k; its fallbacks (list re-scoring, a workgroup-local
   // second pass over the shard) run inside the same launch
-#define RAG_SELECT(F)                                                                          \
-  select_kernel<D, F><<<dim3(Bq), dim3(256), 0, st>>>(                                         \
-      w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, h->tags,      \
-      w.filt, w.qfrag, (int)h->count, w.qn, k, w.eps, w.seed, fb, id_offset, out_s, out_i,   \
-      out_packed, h->rows32)
-  if (filt)
-    RAG_SELECT(true);
-  else
-    RAG_SELECT(false);
-#undef RAG_SELECT
+  with_filter(filt, [&](auto f) {
+    select_kernel<D, decltype(f)::value><<<dim3(Bq), dim3(256), 0, st>>>(
+        w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, h->tags, w.filt,
+        w.qfrag, (int)h->count, w.qn, a.k, w.eps, w.seed, fb, a.id_offset, a.out_s, a.out_i,
+        a.out_packed, h->rows32);
+  });
   // tier 2 of the certificate (rescan_kernel): returns at once unless select marked a query
   // of the pass; otherwise its R workgroups stream the shard once per 16 marked queries.
   // RAGMI_RESCAN_WG (diagnostic A/B) caps R; 0 skips the launch, and mark_unanswered_kernel
   // then records the marked queries as unanswered (tier 3, rag_index_unanswered): timing only
   const int R = std::min(rescan_grid(h), part ? w.cus : h->n_cu);
   if (R > 0) {
-#define RAG_RESCAN(F)                                                                   \
-  launch_fixed<kScanBlock>(rescan_kernel<D, F>, dim3(R), 0, st, w.fb_tier, w.t2, Bq, h->corpus,  \
-                           h->tags, w.filt, w.qfrag, (int)h->count, w.qn, k, w.eps, w.t2_s,  \
-                           w.t2_i, w.t2_tk, id_offset, out_s, out_i, out_packed, h->rows32)
-    if (filt)
-      RAG_RESCAN(true);
-    else
-      RAG_RESCAN(false);
-#undef RAG_RESCAN
+    with_filter(filt, [&](auto f) {
+      launch_fixed<kScanBlock>(rescan_kernel<D, decltype(f)::value>, dim3(R), 0, st, w.fb_tier,
+                               w.t2, Bq, h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, w.qn,
+                               a.k, w.eps, w.t2_s, w.t2_i, w.t2_tk, a.id_offset, a.out_s, a.out_i,
+                               a.out_packed, h->rows32);
+    });
   } else {
     mark_unanswered_kernel<<<dim3(1), dim3(64), 0, st>>>(w.fb_tier, Bq, w.fb_cnt);
   }
@@ -452,29 +603,20 @@ int launch_search_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k
 // kLkRounds (collect, final) launch pairs; rounds after the first return at once unless a
 // query's candidate list overflowed in the previous one.
 int ensure_lk(Workspace& w) {
-  using namespace ragmi;
   if (w.lk_cand) return RAG_OK;
-  const size_t Q = kQ;
   // all seven or none: each buffer is allocated into a local and the workspace takes them only
   // when every allocation succeeded (a partial set would be re-allocated, and leaked, by the
   // next large-k call)
-  void* p[7] = {};
-  const size_t bytes[7] = {Q * kLkSampleMax * 4, Q * 4, Q * 4, Q * 4, 64, Q * kLkCap * 4,
-                           Q * kLkCap * 4};
-  for (int i = 0; i < 7; ++i) {
-    if (hipMalloc(&p[i], bytes[i]) != hipSuccess) {
+  const auto bufs = lk_buffers(w);
+  void* p[bufs.size()] = {};
+  for (size_t i = 0; i < bufs.size(); ++i) {
+    if (hipMalloc(&p[i], bufs[i].bytes) != hipSuccess) {
       (void)hipGetLastError();
-      for (int j = 0; j < i; ++j) (void)hipFree(p[j]);
+      for (size_t j = 0; j < i; ++j) (void)hipFree(p[j]);
       return ragmi::fail(RAG_ENOMEM, "large-k workspace allocation failed");
     }
   }
-  w.lk_smax = static_cast<float*>(p[0]);
-  w.lk_thr = static_cast<float*>(p[1]);
-  w.lk_cnt = static_cast<int*>(p[2]);
-  w.lk_again = static_cast<int*>(p[3]);
-  w.lk_need = static_cast<int*>(p[4]);
-  w.lk_cand = static_cast<int*>(p[5]);
-  w.lk_es = static_cast<float*>(p[6]);
+  for (size_t i = 0; i < bufs.size(); ++i) *bufs[i].p = p[i];
   return RAG_OK;
 }
 
@@ -483,26 +625,28 @@ int ensure_lk(Workspace& w) {
 // row, a stable descending radix sort of (key, row), the first k emitted. The sort buffers
 // (16 B per row + hipcub's scratch) are stream-ordered allocations released at the pass's end.
 template <int D>
-int launch_full_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k,
-                     const uint32_t* filt, int64_t id_offset, float* out_s, int64_t* out_i,
-                     int32_t* out_packed, hipStream_t st) {
+int launch_full_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_t st) {
   using namespace ragmi;
-  qprep_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(q, Bq, filt, w.qn, w.qfrag, w.filt, w.eps,
+  const int Bq = a.Bq, k = a.k;
+  qprep_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(a.q, Bq, a.filt, w.qn, w.qfrag, w.filt, w.eps,
                                                   store_eps(h));
   RAG_HIP(hipGetLastError());
   const int n = (int)h->count;
-  auto emit_grid = [&]() { return dim3((unsigned)std::min<int64_t>(1024, (k + 255) / 256)); };
+  // query j's top k out of the sorted (keys, rows), of which n_match[0] matched its filter
+  auto emit = [&](int j, const uint32_t* keys, const int* rows, const int* n_match) {
+    full_emit_kernel<<<dim3((unsigned)std::min<int64_t>(1024, (k + 255) / 256)), dim3(256), 0,
+                       st>>>(keys, rows, n_match, k, a.id_offset,
+                             a.out_s ? a.out_s + (int64_t)j * k : nullptr,
+                             a.out_i ? a.out_i + (int64_t)j * k : nullptr,
+                             a.out_packed ? a.out_packed + (int64_t)j * k * 2 : nullptr);
+  };
+  StreamScratch scratch(st);
   if (n == 0) {
-    int* zero = nullptr;
-    RAG_HIP(hipMallocAsync(reinterpret_cast<void**>(&zero), 4, st));
+    RAG_HIP(scratch.alloc(4));
+    int* zero = reinterpret_cast<int*>(scratch.p);
     RAG_HIP(hipMemsetAsync(zero, 0, 4, st));
-    for (int j = 0; j < Bq; ++j)
-      full_emit_kernel<<<emit_grid(), dim3(256), 0, st>>>(
-          nullptr, nullptr, zero, k, id_offset, out_s ? out_s + (int64_t)j * k : nullptr,
-          out_i ? out_i + (int64_t)j * k : nullptr,
-          out_packed ? out_packed + (int64_t)j * k * 2 : nullptr);
+    for (int j = 0; j < Bq; ++j) emit(j, nullptr, nullptr, zero);
     RAG_HIP(hipGetLastError());
-    RAG_HIP(hipFreeAsync(zero, st));
     return RAG_OK;
   }
   size_t tmp_bytes = 0;
@@ -510,9 +654,9 @@ int launch_full_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k,
       nullptr, tmp_bytes, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
       static_cast<const int*>(nullptr), static_cast<int*>(nullptr), n, 0, 32, st));
   const size_t nb = (size_t)n * 4;
-  char* buf = nullptr;
   const size_t m_off = 4 * nb, t_off = m_off + 256;
-  RAG_HIP(hipMallocAsync(reinterpret_cast<void**>(&buf), t_off + tmp_bytes, st));
+  RAG_HIP(scratch.alloc(t_off + tmp_bytes));
+  char* const buf = scratch.p;
   uint32_t* k_in = reinterpret_cast<uint32_t*>(buf);
   uint32_t* k_out = reinterpret_cast<uint32_t*>(buf + nb);
   int* v_in = reinterpret_cast<int*>(buf + 2 * nb);
@@ -524,14 +668,12 @@ int launch_full_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k,
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(8 * h->n_cu, (n + 31) / 32));
   int rc = RAG_OK;
   for (int j = 0; j < Bq && rc == RAG_OK; ++j) {
-    if (filt)
-      full_score_kernel<D, true><<<dim3(grid), dim3(256), 0, st>>>(
-          h->corpus, h->tags, w.filt + 2 * j, w.qn + (int64_t)j * D, n, h->rows32, k_in, v_in,
-          n_match + j);
-    else
-      full_score_kernel<D, false><<<dim3(grid), dim3(256), 0, st>>>(
-          h->corpus, h->tags, nullptr, w.qn + (int64_t)j * D, n, h->rows32, k_in, v_in,
-          n_match + j);
+    with_filter(a.filt, [&](auto f) {
+      constexpr bool F = decltype(f)::value;
+      full_score_kernel<D, F><<<dim3(grid), dim3(256), 0, st>>>(
+          h->corpus, h->tags, F ? w.filt + 2 * j : nullptr, w.qn + (int64_t)j * D, n, h->rows32,
+          k_in, v_in, n_match + j);
+    });
     if (hipGetLastError() != hipSuccess ||
         hipcub::DeviceRadixSort::SortPairsDescending(tmp, tmp_bytes,
                                                      static_cast<const uint32_t*>(k_in), k_out,
@@ -540,15 +682,11 @@ int launch_full_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k,
       rc = ragmi::fail(RAG_EHIP, "full exact pass: score / sort launch failed");
       break;
     }
-    full_emit_kernel<<<emit_grid(), dim3(256), 0, st>>>(
-        k_out, v_out, n_match + j, k, id_offset, out_s ? out_s + (int64_t)j * k : nullptr,
-        out_i ? out_i + (int64_t)j * k : nullptr,
-        out_packed ? out_packed + (int64_t)j * k * 2 : nullptr);
+    emit(j, k_out, v_out, n_match + j);
     if (hipGetLastError() != hipSuccess) rc = ragmi::fail(RAG_EHIP, "full exact pass: emit");
   }
   // the pass certifies every query (tier 0) by construction
   (void)hipMemsetAsync(w.fb_tier, 0, 4 * kQ, st);
-  (void)hipFreeAsync(buf, st);
   return rc;
 }
 
@@ -567,14 +705,14 @@ int merge_any_k(const float* in_s, const int64_t* in_i, int n_lists, int B, int 
       static_cast<const int*>(nullptr), static_cast<int*>(nullptr), n, 0, 32, st));
   // keys in/out + positions in/out: 16 B per entry, + scratch (256-B aligned)
   const size_t nb = (size_t)n;
-  char* buf = nullptr;
+  StreamScratch buf(st);
   const size_t t_off = (nb * 16 + 255) & ~(size_t)255;
-  RAG_HIP(hipMallocAsync(reinterpret_cast<void**>(&buf), t_off + tmp, st));
-  uint32_t* ka = reinterpret_cast<uint32_t*>(buf);
+  RAG_HIP(buf.alloc(t_off + tmp));
+  uint32_t* ka = reinterpret_cast<uint32_t*>(buf.p);
   uint32_t* kb = ka + nb;
   int* pa = reinterpret_cast<int*>(kb + nb);
   int* pb = pa + nb;
-  void* scratch = buf + t_off;
+  void* scratch = buf.p + t_off;
   const dim3 g((unsigned)std::min<int64_t>(1024, (n64 + 255) / 256));
   const dim3 ge((unsigned)std::min<int64_t>(1024, ((int64_t)k + 255) / 256));
   auto sort = [&]() {   // (ka, pa) -> (kb, pb), stable, keys descending
@@ -604,86 +742,123 @@ int merge_any_k(const float* in_s, const int64_t* in_i, int n_lists, int B, int 
     }
     if (!ok) rc = ragmi::fail(RAG_EHIP, "merge: sort / launch failed");
   }
-  (void)hipFreeAsync(buf, st);
   return rc;
 }
 
+// rag_merge_topk (in_s, in_i) / rag_merge_topk_packed (PACKED: in_s holds the int32 pairs, in_i
+// is unused) behind their argument checks: the merge kernel by the size of k
+template <bool PACKED>
+int merge_topk(const float* in_s, const int64_t* in_i, int n_lists, int B, int k, float* out_s,
+               int64_t* out_i, hipStream_t st) {
+  if (B == 0) return RAG_OK;
+  if (k > RAG_MAX_K_LARGE) return merge_any_k<PACKED>(in_s, in_i, n_lists, B, k, out_s, out_i, st);
+  if (k > RAG_MAX_K)
+    ragmi::merge_large_kernel<PACKED><<<dim3(B), dim3(256), 0, st>>>(in_s, in_i, n_lists, B, k,
+                                                                    out_s, out_i);
+  else
+    ragmi::merge_exact_kernel<PACKED><<<dim3(B), dim3(64), 0, st>>>(in_s, in_i, n_lists, B, k,
+                                                                   out_s, out_i);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
 template <int D>
-int launch_large_k_pass(rag_index* h, Workspace& w, const float* q, int Bq, int k,
-                        const uint32_t* filt, int64_t id_offset, float* out_s, int64_t* out_i,
-                        int32_t* out_packed, hipStream_t st) {
+int launch_large_k_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_t st) {
   using namespace ragmi;
+  const uint32_t* const filt = a.filt;
+  const int Bq = a.Bq, k = a.k;
   int rc = ensure_lk(w);
   if (rc) return rc;
-  qprep_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(q, Bq, filt, w.qn, w.qfrag, w.filt, w.eps,
+  qprep_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(a.q, Bq, filt, w.qn, w.qfrag, w.filt, w.eps,
                                                   store_eps(h));
   const int n_tiles = (int)((h->count + 15) / 16);
   // bound sample: >= 4k tiles (so k distinct-row maxima exist with margin), >= 1/32 of the
   // shard, at most kLkSampleMax
   const int n_sample = n_tiles == 0 ? 0 : std::min({n_tiles, std::max(4 * k, n_tiles / 32),
                                                     kLkSampleMax});
-  if (n_sample > 0) {
-    if (filt)
-      sample_kernel<D, true><<<dim3((n_sample + 7) / 8, 1), dim3(256), 0, st>>>(
+  if (n_sample > 0)
+    with_filter(filt, [&](auto f) {
+      sample_kernel<D, decltype(f)::value><<<dim3((n_sample + 7) / 8, 1), dim3(256), 0, st>>>(
           h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, n_tiles, n_sample, w.lk_smax);
-    else
-      sample_kernel<D, false><<<dim3((n_sample + 7) / 8, 1), dim3(256), 0, st>>>(
-          h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, n_tiles, n_sample, w.lk_smax);
-  }
+    });
   lk_bound_kernel<<<dim3(Bq), dim3(256), 0, st>>>(w.lk_smax, n_sample, k, w.eps, w.lk_thr,
                                                   w.lk_cnt, w.lk_again, w.lk_need);
   // collection grid: two workgroups per CU (10M rows, k = 33: 1.54-1.55 ms per pass vs
   // 1.57-1.64 at four, 2.37 at one; k = 100 1.64 either way; profiles/r05q_large_k_grid.jsonl)
   const int cgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2 * h->n_cu, (n_tiles + 3) / 4));
   for (int r = 0; r < kLkRounds; ++r) {
-    if (filt)
-      lk_collect_kernel<D, true><<<dim3(cgrid), dim3(256), 0, st>>>(
+    with_filter(filt, [&](auto f) {
+      lk_collect_kernel<D, decltype(f)::value><<<dim3(cgrid), dim3(256), 0, st>>>(
           h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, n_tiles, Bq, w.lk_thr, w.lk_cnt,
           w.lk_cand, w.lk_again, w.lk_need, r);
-    else
-      lk_collect_kernel<D, false><<<dim3(cgrid), dim3(256), 0, st>>>(
-          h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, n_tiles, Bq, w.lk_thr, w.lk_cnt,
-          w.lk_cand, w.lk_again, w.lk_need, r);
+    });
     lk_rescore_kernel<D><<<dim3(kLkCap / 256, Bq), dim3(256), 0, st>>>(
         h->corpus, w.qn, w.lk_cnt, w.lk_cand, w.lk_again, w.lk_need, r, w.lk_es, h->rows32);
     lk_final_kernel<D><<<dim3(Bq), dim3(256), 0, st>>>(
         h->corpus, w.qn, k, w.lk_cnt, w.lk_cand, w.lk_es, w.eps, w.lk_thr, w.lk_again, w.lk_need, r,
-        w.fb_tier, w.fb_cnt, id_offset, out_s, out_i, out_packed, h->rows32);
+        w.fb_tier, w.fb_cnt, a.id_offset, a.out_s, a.out_i, a.out_packed, h->rows32);
   }
   RAG_HIP(hipGetLastError());
   return RAG_OK;
 }
 
-template <int D>
-void launch_import(rag_index* h, const half8* in, int64_t row0, int64_t n, hipStream_t st) {
-  const int64_t total = n * (D / 8);
-  ragmi::import_kernel<D><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(
-      in, row0, n, h->corpus);
+// rag_index_import_rows (T = uint16_t: fp16 rows into an fp16-storage index) and
+// rag_index_import_rows32 (T = float: fp32 rows into an fp32-storage index, the scan's fp16
+// copy derived on the device): staged through device memory, synchronous
+template <typename T>
+int import_rows(rag_index* h, int64_t row0, int64_t n, const T* rows, const uint32_t* tags,
+                int64_t new_count) {
+  constexpr bool k32 = std::is_same_v<T, float>;
+  ragmi::clear_error();
+  if (!h || (n > 0 && !rows) || row0 < 0 || n < 0 || row0 + n > h->cap_rows)
+    return ragmi::fail(RAG_EINVAL, "bad import range (reserve capacity first)");
+  if (k32 && !h->rows32) return ragmi::fail(RAG_EINVAL, "index has fp16 storage (no fp32 rows)");
+  if (!k32 && h->rows32)
+    return ragmi::fail(RAG_EINVAL, "fp32-storage index: load its fp32 rows (rag_index_import_rows32)");
+  if (new_count < 0 || new_count > h->cap_rows)
+    return ragmi::fail(RAG_ERANGE, "new_count exceeds capacity");
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  if (n > 0) {
+    const size_t bytes = (size_t)n * h->dim * sizeof(T);
+    int rc = ensure_stage(h, bytes);
+    if (rc) return rc;
+    RAG_HIP(hipDeviceSynchronize());
+    RAG_HIP(hipMemcpy(h->stage, rows, bytes, hipMemcpyHostToDevice));
+    rc = with_dim(h->dim, [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      const dim3 grid((unsigned)((n * (D / 8) + 255) / 256));
+      if constexpr (k32)
+        ragmi::import32_kernel<D><<<grid, dim3(256), 0, nullptr>>>(
+            static_cast<const float*>(h->stage), row0, n, h->corpus, h->rows32);
+      else
+        ragmi::import_kernel<D><<<grid, dim3(256), 0, nullptr>>>(
+            static_cast<const half8*>(h->stage), row0, n, h->corpus);
+      return RAG_OK;
+    });
+    if (rc) return rc;
+    RAG_HIP(hipGetLastError());
+    if (tags)
+      RAG_HIP(hipMemcpy(h->tags + row0, tags, (size_t)n * 4, hipMemcpyHostToDevice));
+    RAG_HIP(hipDeviceSynchronize());
+  }
+  h->count = new_count;
+  return RAG_OK;
 }
 
-template <int D>
-void launch_import32(rag_index* h, const float* in, int64_t row0, int64_t n, hipStream_t st) {
-  const int64_t total = n * (D / 8);
-  ragmi::import32_kernel<D><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(
-      in, row0, n, h->corpus, h->rows32);
+// The three export entry points: their shared range check, then `body` under the handle's lock
+// on its device (need32: only an fp32-storage index has the rows)
+template <typename F>
+int export_range(rag_index* h, const void* out, int64_t row0, int64_t n, bool need32, F&& body) {
+  ragmi::clear_error();
+  if (!h || !out || row0 < 0 || n < 0 || row0 + n > h->cap_rows)
+    return ragmi::fail(RAG_EINVAL, "bad export range");
+  if (need32 && !h->rows32) return ragmi::fail(RAG_EINVAL, "index has fp16 storage (no fp32 rows)");
+  if (n == 0) return RAG_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  return body();
 }
-
-template <int D>
-void launch_export(rag_index* h, int64_t row0, int64_t n, half8* out, hipStream_t st) {
-  const int64_t total = n * (D / 8);
-  const int blocks = (int)((total + 255) / 256);
-  ragmi::export_kernel<D><<<dim3(blocks), dim3(256), 0, st>>>(h->corpus, row0, n, out);
-}
-
-#define RAG_DISPATCH_DIM(dim, FN, ...)                                   \
-  do {                                                                   \
-    if ((dim) == 384)                                                    \
-      FN<384>(__VA_ARGS__);                                              \
-    else if ((dim) == 1024)                                              \
-      FN<1024>(__VA_ARGS__);                                             \
-    else                                                                 \
-      return ragmi::fail(RAG_EINVAL, "unsupported dim (built: 384, 1024)"); \
-  } while (0)
 
 int upsert_locked(rag_index* h, const float* vecs, const int64_t* rows, const uint32_t* tags,
                   int64_t n, int64_t new_count, hipStream_t st) {
@@ -693,7 +868,12 @@ int upsert_locked(rag_index* h, const float* vecs, const int64_t* rows, const ui
   if (n > 0x7fffffff) return ragmi::fail(RAG_ERANGE, "n too large for one upsert");
   RAG_HIP(hipSetDevice(h->device));
   if (n > 0) {
-    RAG_DISPATCH_DIM(h->dim, launch_upsert, h, vecs, rows, tags, n, st);
+    const int rc = with_dim(h->dim, [&](auto d) {
+      ragmi::upsert_kernel<decltype(d)::value><<<dim3((unsigned)n), dim3(64), 0, st>>>(
+          vecs, rows, tags, h->corpus, h->tags, n, h->cap_rows, h->rows32);
+      return RAG_OK;
+    });
+    if (rc) return rc;
     RAG_HIP(hipGetLastError());
   }
   h->count = new_count;
@@ -716,18 +896,12 @@ int search_locked(rag_index* h, const float* q, int B, int k, const uint32_t* fi
   const int per_pass = large ? ragmi::kQ : ragmi::kQ * h->groups;
   for (int b0 = 0; b0 < B; b0 += per_pass) {
     const int Bq = std::min(per_pass, B - b0);
-    Workspace* wp = nullptr;
-    for (auto& s : h->ws)
-      if (s.used && s.owner == st) { wp = &s; break; }
-    if (!wp)
-      for (auto& s : h->ws)
-        if (!s.used) { wp = &s; break; }
+    Workspace* lru = nullptr;
+    Workspace* wp = pick_slot(h->ws, st, lru);
     if (!wp) {
       // every slot is bound to another stream whose last pass may still be running
       RAG_HIP(hipDeviceSynchronize());
-      wp = &h->ws[0];
-      for (auto& s : h->ws)
-        if (s.tick < wp->tick) wp = &s;
+      wp = lru;
     }
     Workspace& w = *wp;
     const uint64_t gen = g_stream_gen.load(std::memory_order_acquire);
@@ -738,48 +912,25 @@ int search_locked(rag_index* h, const float* q, int B, int k, const uint32_t* fi
     w.used = true;
     w.owner = st;
     w.tick = ++h->ws_tick;
-    int rc;
     h->last_ws = &w;
     h->last_bq = Bq;
-    if (large) {
-      float* os = out_packed ? nullptr : out_s + (int64_t)b0 * k;
-      int64_t* oi = out_packed ? nullptr : out_i + (int64_t)b0 * k;
-      int32_t* op = out_packed ? out_packed + (int64_t)b0 * k * 2 : nullptr;
-      const uint32_t* fq = filt ? filt + 2 * b0 : nullptr;
-      if (full) {
-        rc = h->dim == 384
-                 ? launch_full_pass<384>(h, w, q + (int64_t)b0 * h->dim, Bq, k, fq, id_offset, os,
-                                         oi, op, st)
-                 : launch_full_pass<1024>(h, w, q + (int64_t)b0 * h->dim, Bq, k, fq, id_offset,
-                                          os, oi, op, st);
-        if (rc) return rc;
-        continue;
-      }
-      rc = h->dim == 384
-               ? launch_large_k_pass<384>(h, w, q + (int64_t)b0 * h->dim, Bq, k, fq, id_offset, os,
-                                          oi, op, st)
-               : launch_large_k_pass<1024>(h, w, q + (int64_t)b0 * h->dim, Bq, k, fq, id_offset,
-                                           os, oi, op, st);
-      if (rc) return rc;
-      continue;
-    }
-    if (h->dim == 384)
-      rc = launch_search_pass<384>(
-          h, w, q + (int64_t)b0 * h->dim, Bq, k, filt ? filt + 2 * b0 : nullptr, id_offset,
-          out_packed ? nullptr : out_s + (int64_t)b0 * k,
-          out_packed ? nullptr : out_i + (int64_t)b0 * k,
-          out_packed ? out_packed + (int64_t)b0 * k * 2 : nullptr, st);
-    else
-      rc = launch_search_pass<1024>(
-          h, w, q + (int64_t)b0 * h->dim, Bq, k, filt ? filt + 2 * b0 : nullptr, id_offset,
-          out_packed ? nullptr : out_s + (int64_t)b0 * k,
-          out_packed ? nullptr : out_i + (int64_t)b0 * k,
-          out_packed ? out_packed + (int64_t)b0 * k * 2 : nullptr, st);
+    const PassArgs a{q + (int64_t)b0 * h->dim,
+                     Bq,
+                     k,
+                     filt ? filt + 2 * b0 : nullptr,
+                     id_offset,
+                     out_packed ? nullptr : out_s + (int64_t)b0 * k,
+                     out_packed ? nullptr : out_i + (int64_t)b0 * k,
+                     out_packed ? out_packed + (int64_t)b0 * k * 2 : nullptr};
+    const auto dim = [&](auto&& pass) { return with_dim(h->dim, pass); };
+    const int rc =
+        full    ? dim([&](auto d) { return launch_full_pass<decltype(d)::value>(h, w, a, st); })
+        : large ? dim([&](auto d) { return launch_large_k_pass<decltype(d)::value>(h, w, a, st); })
+                : dim([&](auto d) { return launch_search_pass<decltype(d)::value>(h, w, a, st); });
     if (rc) return rc;
   }
   return RAG_OK;
 }
-
 
 // Diagnostic A/B of scan variants (see scan_kernel's knobs). Returns avg device ms/launch.
 template <int D, int V>
@@ -821,26 +972,21 @@ int bench_scan(rag_index* h, const float* q, int B, int variant, int reps, doubl
   const int cap = k_wgs.get(0) > 0 ? std::max(8, k_wgs.get(0)) : h->scan_wgs;
   int grid = (int)std::min<int64_t>(std::min(h->max_wgs, cap), std::max<int64_t>(1, (n_tiles + 3) / 4));
   grid = std::min(grid, kMaxLists / kWavesPerWG);
-  // variant 8: the v_dot2 VALU ablation over a row-group-major copy of the corpus
-  half8* rows64 = nullptr;
-  half8* qc = nullptr;
-  const int n_groups = (int)((h->count + 63) / 64);
 #ifdef RAGMI_DIAG_BUILD
+  // variant 8: the v_dot2 VALU ablation over a row-group-major copy of the corpus
+  DeviceBuf<half8> rows64, qc;
+  const int n_groups = (int)((h->count + 63) / 64);
+  const int vgrid = std::min(h->max_wgs, std::max(1, (n_groups + 3) / 4));
   if (variant == 8) {
-    RAG_HIP(hipMalloc(reinterpret_cast<void**>(&rows64), (size_t)n_groups * 64 * D * 2));
-    RAG_HIP(hipMalloc(reinterpret_cast<void**>(&qc), (size_t)kQ * D * 2));
-    RAG_HIP(hipMemset(rows64, 0, (size_t)n_groups * 64 * D * 2));
+    RAG_HIP(rows64.alloc((size_t)n_groups * 64 * D * 2));
+    RAG_HIP(qc.alloc((size_t)kQ * D * 2));
+    RAG_HIP(hipMemset(rows64.p, 0, (size_t)n_groups * 64 * D * 2));
     const int64_t total = h->count * (D / 8);
     rows64_kernel<D><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr>>>(
-        h->corpus, h->count, rows64);
-    qchunk_kernel<D><<<dim3(kQ), dim3(64), 0, nullptr>>>(w.qn, qc);
+        h->corpus, h->count, rows64.p);
+    qchunk_kernel<D><<<dim3(kQ), dim3(64), 0, nullptr>>>(w.qn, qc.p);
   }
 #endif
-  const int vgrid = std::min(h->max_wgs, std::max(1, (n_groups + 3) / 4));
-  (void)vgrid;
-  hipEvent_t a, b;
-  RAG_HIP(hipEventCreate(&a));
-  RAG_HIP(hipEventCreate(&b));
   auto one = [&]() {
 #ifndef RAGMI_DIAG_BUILD
     // production library: the production scan only (variants 0 and 7); the MODE / DYN /
@@ -849,7 +995,7 @@ int bench_scan(rag_index* h, const float* q, int B, int variant, int reps, doubl
 #else
     if (variant == 8) {
       scan_valu_kernel<D><<<dim3(vgrid), dim3(256), 0, nullptr>>>(
-          rows64, qc, (int)h->count, n_groups, w.seed, w.part_s, w.part_i, w.heads_s,
+          rows64.p, qc.p, (int)h->count, n_groups, w.seed, w.part_s, w.part_i, w.heads_s,
           w.heads_i, w.heads_n);
       return;
     }
@@ -871,9 +1017,11 @@ int bench_scan(rag_index* h, const float* q, int B, int variant, int reps, doubl
 #ifdef RAGMI_DIAG_BUILD
   if (variant >= 9 && variant <= 14) {
     // one launch per event pair; the tile-queue heads are zeroed before each, outside it
+    EventPair ev;
+    RAG_HIP(ev.create());
     for (int r = -1; r < reps; ++r) {
       RAG_HIP(hipMemsetAsync(w.tileq, 0, 8 * kTileQStride * 4, nullptr));
-      RAG_HIP(hipEventRecord(a, nullptr));
+      RAG_HIP(hipEventRecord(ev.a, nullptr));
       switch (variant) {
         case 9: launch_variant<D, 9>(h, w, grid, nullptr); break;
         case 10: launch_variant<D, 10>(h, w, grid, nullptr); break;
@@ -882,26 +1030,18 @@ int bench_scan(rag_index* h, const float* q, int B, int variant, int reps, doubl
         case 13: launch_variant<D, 0>(h, w, grid, nullptr); break;
         default: launch_variant<D, 14>(h, w, grid, nullptr); break;
       }
-      RAG_HIP(hipEventRecord(b, nullptr));
-      RAG_HIP(hipEventSynchronize(b));
+      RAG_HIP(hipEventRecord(ev.b, nullptr));
+      RAG_HIP(hipEventSynchronize(ev.b));
       float m1 = 0.f;
-      RAG_HIP(hipEventElapsedTime(&m1, a, b));
+      RAG_HIP(hipEventElapsedTime(&m1, ev.a, ev.b));
       if (r >= 0) ms += m1;   // r = -1: warm-up
     }
   } else
 #endif
   {
-    one();  // warm
-    RAG_HIP(hipEventRecord(a, nullptr));
-    for (int r = 0; r < reps; ++r) one();
-    RAG_HIP(hipEventRecord(b, nullptr));
-    RAG_HIP(hipEventSynchronize(b));
-    RAG_HIP(hipEventElapsedTime(&ms, a, b));
+    const int rc = time_launches(reps, one, &ms);
+    if (rc) return rc;
   }
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  if (rows64) (void)hipFree(rows64);
-  if (qc) (void)hipFree(qc);
   RAG_HIP(hipGetLastError());
   *avg_ms = ms / reps;
   return RAG_OK;
@@ -939,18 +1079,9 @@ int bench_wide(rag_index* h, const float* q, int B, int mode, int reps, double* 
 #endif
 #undef RAG_WIDE
   };
-  hipEvent_t a, b;
-  RAG_HIP(hipEventCreate(&a));
-  RAG_HIP(hipEventCreate(&b));
-  one();  // warm
-  RAG_HIP(hipEventRecord(a, nullptr));
-  for (int r = 0; r < reps; ++r) one();
-  RAG_HIP(hipEventRecord(b, nullptr));
-  RAG_HIP(hipEventSynchronize(b));
   float ms = 0.f;
-  RAG_HIP(hipEventElapsedTime(&ms, a, b));
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
+  const int rc = time_launches(reps, one, &ms);
+  if (rc) return rc;
   RAG_HIP(hipGetLastError());
   *avg_ms = ms / reps;
   return RAG_OK;
@@ -1008,44 +1139,13 @@ int rag_index_create_ex(int dim, int64_t capacity_rows, int device, int storage,
   h->scan_wgs = std::max(8, (n_cu * 3 / 4) & ~7);
   // wide rows (LDS-query scan) take up to 4 query groups (128 queries) per pass
   h->groups = dim > 384 ? kMaxGroups : 1;
-  const size_t G = (size_t)h->groups, Q = ragmi::kQ;
-  const int max_lists = std::min(h->max_wgs * ragmi::kWavesPerWG, ragmi::kMaxLists);
   for (auto& w : h->ws) {
-    bool ok = hipMalloc(reinterpret_cast<void**>(&w.qn), G * Q * dim * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.qfrag), G * 2 * (dim / 32) * 64 * 16) ==
-                  hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.filt), G * Q * 2 * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.smax),
-                        G * (dim > 384 ? ragmi::kMaxSampleWide : ragmi::kMaxSample) * Q * 4) ==
-                  hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.heads_s),
-                        G * ragmi::kMaxLists * Q * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.heads_i),
-                        G * ragmi::kMaxLists * Q * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.heads_n),
-                        G * ragmi::kMaxLists * Q * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.seed), G * Q * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.part_s),
-                        G * max_lists * Q * ragmi::kKS * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.part_i),
-                        G * max_lists * Q * ragmi::kKS * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.progress),
-                        G * ragmi::kMaxLists * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.eps), G * Q * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.fb_tier), G * Q * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.fb_cnt), 32) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.tileq), 8 * ragmi::kTileQStride * 4) ==
-                  hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.t2), G * Q * 2 * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.t2_s),
-                        G * Q * ragmi::kRescanMaxWG * 32 * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.t2_i),
-                        G * Q * ragmi::kRescanMaxWG * 32 * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&w.t2_tk), 64) == hipSuccess &&
-              hipMemset(w.t2_tk, 0, 64) == hipSuccess &&
-              hipMemset(w.tileq, 0, 8 * ragmi::kTileQStride * 4) == hipSuccess &&
-              hipMemset(w.fb_cnt, 0, 32) == hipSuccess &&
-              hipMemset(w.fb_tier, 0, G * Q * 4) == hipSuccess;
+    // one hipMalloc per buffer, in the table's order (see ragmi/dist.py on allocation placement)
+    const auto bufs = ws_buffers(h, w);
+    bool ok = true;
+    for (const WsBuf& b : bufs) ok = ok && hipMalloc(b.p, b.bytes) == hipSuccess;
+    for (const WsBuf& b : bufs)
+      if (b.zero) ok = ok && hipMemset(*b.p, 0, b.bytes) == hipSuccess;
     if (!ok) {
       rag_index_destroy(h);
       return ragmi::fail(RAG_ENOMEM, "workspace allocation failed");
@@ -1080,26 +1180,10 @@ int rag_index_destroy(rag_index_t* h) {
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
   for (auto& w : h->ws) {
-    if (w.qn) (void)hipFree(w.qn);
-    if (w.qfrag) (void)hipFree(w.qfrag);
-    if (w.filt) (void)hipFree(w.filt);
-    if (w.smax) (void)hipFree(w.smax);
-    if (w.heads_s) (void)hipFree(w.heads_s);
-    if (w.heads_i) (void)hipFree(w.heads_i);
-    if (w.heads_n) (void)hipFree(w.heads_n);
-    if (w.seed) (void)hipFree(w.seed);
-    if (w.part_s) (void)hipFree(w.part_s);
-    if (w.part_i) (void)hipFree(w.part_i);
-    if (w.progress) (void)hipFree(w.progress);
-    if (w.eps) (void)hipFree(w.eps);
-    if (w.fb_tier) (void)hipFree(w.fb_tier);
-    if (w.fb_cnt) (void)hipFree(w.fb_cnt);
-    if (w.tileq) (void)hipFree(w.tileq);
-    for (void* p : {(void*)w.t2, (void*)w.t2_s, (void*)w.t2_i, (void*)w.t2_tk})
-      if (p) (void)hipFree(p);
-    for (void* p : {(void*)w.lk_smax, (void*)w.lk_thr, (void*)w.lk_cnt, (void*)w.lk_again,
-                    (void*)w.lk_need, (void*)w.lk_cand, (void*)w.lk_es})
-      if (p) (void)hipFree(p);
+    for (const WsBuf& b : ws_buffers(h, w))
+      if (*b.p) (void)hipFree(*b.p);
+    for (const WsBuf& b : lk_buffers(w))
+      if (*b.p) (void)hipFree(*b.p);
     if (w.ev_in) (void)hipEventDestroy(w.ev_in);
     if (w.ev_out) (void)hipEventDestroy(w.ev_out);
   }
@@ -1126,43 +1210,30 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
   const int64_t cap = round16(capacity_rows);
   if (cap <= h->cap_rows) return RAG_OK;
   RAG_HIP(hipSetDevice(h->device));
-  half8* nc = nullptr;
-  uint32_t* nt = nullptr;
-  float* n32 = nullptr;
   // the new buffers are freed on every error return below; released once the handle owns them
-  struct Guard {
-    half8** c; uint32_t** t; float** f;
-    ~Guard() {
-      if (*c) (void)hipFree(*c);
-      if (*t) (void)hipFree(*t);
-      if (*f) (void)hipFree(*f);
-    }
-  } guard{&nc, &nt, &n32};
-  int rc = alloc_corpus(h, cap, &nc, &nt);
+  DeviceBuf<half8> nc;
+  DeviceBuf<uint32_t> nt;
+  DeviceBuf<float> n32;
+  int rc = alloc_corpus(h, cap, &nc.p, &nt.p);
   if (rc) return rc;
   if (h->rows32) {
     const size_t b32 = (size_t)cap * h->dim * 4;
-    if (hipMalloc(reinterpret_cast<void**>(&n32), b32) != hipSuccess) {
-      n32 = nullptr;
-      return ragmi::fail(RAG_ENOMEM, "hipMalloc(rows32) failed");
-    }
-    RAG_HIP(hipMemset(n32, 0, b32));
+    if (n32.alloc(b32) != hipSuccess) return ragmi::fail(RAG_ENOMEM, "hipMalloc(rows32) failed");
+    RAG_HIP(hipMemset(n32.p, 0, b32));
   }
   RAG_HIP(hipDeviceSynchronize());
-  RAG_HIP(hipMemcpy(nc, h->corpus, (size_t)h->cap_rows * h->dim * 2, hipMemcpyDeviceToDevice));
-  RAG_HIP(hipMemcpy(nt, h->tags, (size_t)h->cap_rows * 4, hipMemcpyDeviceToDevice));
-  if (n32)
-    RAG_HIP(hipMemcpy(n32, h->rows32, (size_t)h->cap_rows * h->dim * 4, hipMemcpyDeviceToDevice));
+  RAG_HIP(hipMemcpy(nc.p, h->corpus, (size_t)h->cap_rows * h->dim * 2, hipMemcpyDeviceToDevice));
+  RAG_HIP(hipMemcpy(nt.p, h->tags, (size_t)h->cap_rows * 4, hipMemcpyDeviceToDevice));
+  if (n32.p)
+    RAG_HIP(hipMemcpy(n32.p, h->rows32, (size_t)h->cap_rows * h->dim * 4,
+                      hipMemcpyDeviceToDevice));
   (void)hipFree(h->corpus);
   (void)hipFree(h->tags);
   if (h->rows32) (void)hipFree(h->rows32);
-  h->corpus = nc;
-  h->tags = nt;
-  h->rows32 = n32;
+  h->corpus = nc.release();
+  h->tags = nt.release();
+  h->rows32 = n32.release();
   h->cap_rows = cap;
-  nc = nullptr;                                  // owned by the handle now
-  nt = nullptr;
-  n32 = nullptr;
   return RAG_OK;
 }
 
@@ -1268,104 +1339,53 @@ int rag_index_search_host(rag_index_t* h, const float* q, int B, int k,
 }
 
 int rag_index_export_rows(rag_index_t* h, int64_t row0, int64_t n, uint16_t* out) {
-  ragmi::clear_error();
-  if (!h || !out || row0 < 0 || n < 0 || row0 + n > h->cap_rows)
-    return ragmi::fail(RAG_EINVAL, "bad export range");
-  if (n == 0) return RAG_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RAG_HIP(hipSetDevice(h->device));
-  const size_t bytes = (size_t)n * h->dim * 2;
-  int rc = ensure_stage(h, bytes);
-  if (rc) return rc;
-  RAG_HIP(hipDeviceSynchronize());
-  RAG_DISPATCH_DIM(h->dim, launch_export, h, row0, n, static_cast<half8*>(h->stage), nullptr);
-  RAG_HIP(hipGetLastError());
-  RAG_HIP(hipDeviceSynchronize());
-  RAG_HIP(hipMemcpy(out, h->stage, bytes, hipMemcpyDeviceToHost));
-  return RAG_OK;
-}
-
-int rag_index_import_rows(rag_index_t* h, int64_t row0, int64_t n, const uint16_t* rows,
-                          const uint32_t* tags, int64_t new_count) {
-  ragmi::clear_error();
-  if (!h || (n > 0 && !rows) || row0 < 0 || n < 0 || row0 + n > h->cap_rows)
-    return ragmi::fail(RAG_EINVAL, "bad import range (reserve capacity first)");
-  if (h->rows32)
-    return ragmi::fail(RAG_EINVAL, "fp32-storage index: load its fp32 rows (rag_index_import_rows32)");
-  if (new_count < 0 || new_count > h->cap_rows)
-    return ragmi::fail(RAG_ERANGE, "new_count exceeds capacity");
-  std::lock_guard<std::mutex> lk(h->mu);
-  RAG_HIP(hipSetDevice(h->device));
-  if (n > 0) {
+  return export_range(h, out, row0, n, false, [&]() -> int {
     const size_t bytes = (size_t)n * h->dim * 2;
     int rc = ensure_stage(h, bytes);
     if (rc) return rc;
     RAG_HIP(hipDeviceSynchronize());
-    RAG_HIP(hipMemcpy(h->stage, rows, bytes, hipMemcpyHostToDevice));
-    RAG_DISPATCH_DIM(h->dim, launch_import, h, static_cast<const half8*>(h->stage), row0, n,
-                     nullptr);
+    rc = with_dim(h->dim, [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      const int blocks = (int)((n * (D / 8) + 255) / 256);
+      ragmi::export_kernel<D><<<dim3(blocks), dim3(256), 0, nullptr>>>(
+          h->corpus, row0, n, static_cast<half8*>(h->stage));
+      return RAG_OK;
+    });
+    if (rc) return rc;
     RAG_HIP(hipGetLastError());
-    if (tags)
-      RAG_HIP(hipMemcpy(h->tags + row0, tags, (size_t)n * 4, hipMemcpyHostToDevice));
     RAG_HIP(hipDeviceSynchronize());
-  }
-  h->count = new_count;
-  return RAG_OK;
+    RAG_HIP(hipMemcpy(out, h->stage, bytes, hipMemcpyDeviceToHost));
+    return RAG_OK;
+  });
+}
+
+int rag_index_import_rows(rag_index_t* h, int64_t row0, int64_t n, const uint16_t* rows,
+                          const uint32_t* tags, int64_t new_count) {
+  return import_rows(h, row0, n, rows, tags, new_count);
 }
 
 int rag_index_storage(const rag_index_t* h) { return h ? h->storage : -1; }
 
 int rag_index_export_rows32(rag_index_t* h, int64_t row0, int64_t n, float* out) {
-  ragmi::clear_error();
-  if (!h || !out || row0 < 0 || n < 0 || row0 + n > h->cap_rows)
-    return ragmi::fail(RAG_EINVAL, "bad export range");
-  if (!h->rows32) return ragmi::fail(RAG_EINVAL, "index has fp16 storage (no fp32 rows)");
-  if (n == 0) return RAG_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RAG_HIP(hipSetDevice(h->device));
-  RAG_HIP(hipDeviceSynchronize());
-  RAG_HIP(hipMemcpy(out, h->rows32 + row0 * h->dim, (size_t)n * h->dim * 4,
-                    hipMemcpyDeviceToHost));
-  return RAG_OK;
+  return export_range(h, out, row0, n, true, [&]() -> int {
+    RAG_HIP(hipDeviceSynchronize());
+    RAG_HIP(hipMemcpy(out, h->rows32 + row0 * h->dim, (size_t)n * h->dim * 4,
+                      hipMemcpyDeviceToHost));
+    return RAG_OK;
+  });
 }
 
 int rag_index_import_rows32(rag_index_t* h, int64_t row0, int64_t n, const float* rows,
                             const uint32_t* tags, int64_t new_count) {
-  ragmi::clear_error();
-  if (!h || (n > 0 && !rows) || row0 < 0 || n < 0 || row0 + n > h->cap_rows)
-    return ragmi::fail(RAG_EINVAL, "bad import range (reserve capacity first)");
-  if (!h->rows32) return ragmi::fail(RAG_EINVAL, "index has fp16 storage (no fp32 rows)");
-  if (new_count < 0 || new_count > h->cap_rows)
-    return ragmi::fail(RAG_ERANGE, "new_count exceeds capacity");
-  std::lock_guard<std::mutex> lk(h->mu);
-  RAG_HIP(hipSetDevice(h->device));
-  if (n > 0) {
-    const size_t bytes = (size_t)n * h->dim * 4;
-    int rc = ensure_stage(h, bytes);
-    if (rc) return rc;
-    RAG_HIP(hipDeviceSynchronize());
-    RAG_HIP(hipMemcpy(h->stage, rows, bytes, hipMemcpyHostToDevice));
-    RAG_DISPATCH_DIM(h->dim, launch_import32, h, static_cast<const float*>(h->stage), row0, n,
-                     nullptr);
-    RAG_HIP(hipGetLastError());
-    if (tags)
-      RAG_HIP(hipMemcpy(h->tags + row0, tags, (size_t)n * 4, hipMemcpyHostToDevice));
-    RAG_HIP(hipDeviceSynchronize());
-  }
-  h->count = new_count;
-  return RAG_OK;
+  return import_rows(h, row0, n, rows, tags, new_count);
 }
 
 int rag_index_export_tags(rag_index_t* h, int64_t row0, int64_t n, uint32_t* out) {
-  ragmi::clear_error();
-  if (!h || !out || row0 < 0 || n < 0 || row0 + n > h->cap_rows)
-    return ragmi::fail(RAG_EINVAL, "bad export range");
-  if (n == 0) return RAG_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RAG_HIP(hipSetDevice(h->device));
-  RAG_HIP(hipDeviceSynchronize());
-  RAG_HIP(hipMemcpy(out, h->tags + row0, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return RAG_OK;
+  return export_range(h, out, row0, n, false, [&]() -> int {
+    RAG_HIP(hipDeviceSynchronize());
+    RAG_HIP(hipMemcpy(out, h->tags + row0, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RAG_OK;
+  });
 }
 
 int rag_merge_topk(const float* in_s, const int64_t* in_i, int n_lists, int B, int k,
@@ -1373,18 +1393,8 @@ int rag_merge_topk(const float* in_s, const int64_t* in_i, int n_lists, int B, i
   ragmi::clear_error();
   if (n_lists < 1 || B < 0 || k < 1)
     return ragmi::fail(RAG_EINVAL, "bad merge args");
-  if (B == 0) return RAG_OK;
-  if (k > RAG_MAX_K_LARGE)
-    return merge_any_k<false>(in_s, in_i, n_lists, B, k, out_s, out_i,
-                              static_cast<hipStream_t>(stream));
-  if (k > RAG_MAX_K)
-    ragmi::merge_large_kernel<false><<<dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream)>>>(
-        in_s, in_i, n_lists, B, k, out_s, out_i);
-  else
-    ragmi::merge_exact_kernel<false><<<dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream)>>>(
-        in_s, in_i, n_lists, B, k, out_s, out_i);
-  RAG_HIP(hipGetLastError());
-  return RAG_OK;
+  return merge_topk<false>(in_s, in_i, n_lists, B, k, out_s, out_i,
+                           static_cast<hipStream_t>(stream));
 }
 
 int rag_merge_topk_packed(const int32_t* in_packed, int n_lists, int B, int k, float* out_s,
@@ -1392,18 +1402,8 @@ int rag_merge_topk_packed(const int32_t* in_packed, int n_lists, int B, int k, f
   ragmi::clear_error();
   if (n_lists < 1 || B < 0 || k < 1 || (B > 0 && !in_packed))
     return ragmi::fail(RAG_EINVAL, "bad merge args");
-  if (B == 0) return RAG_OK;
-  if (k > RAG_MAX_K_LARGE)
-    return merge_any_k<true>(reinterpret_cast<const float*>(in_packed), nullptr, n_lists, B, k,
-                             out_s, out_i, static_cast<hipStream_t>(stream));
-  if (k > RAG_MAX_K)
-    ragmi::merge_large_kernel<true><<<dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream)>>>(
-        reinterpret_cast<const float*>(in_packed), nullptr, n_lists, B, k, out_s, out_i);
-  else
-    ragmi::merge_exact_kernel<true><<<dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream)>>>(
-        reinterpret_cast<const float*>(in_packed), nullptr, n_lists, B, k, out_s, out_i);
-  RAG_HIP(hipGetLastError());
-  return RAG_OK;
+  return merge_topk<true>(reinterpret_cast<const float*>(in_packed), nullptr, n_lists, B, k,
+                          out_s, out_i, static_cast<hipStream_t>(stream));
 }
 
 int rag_merge_topk_gather(const int32_t* const* lists, int n_lists, int B, int k, int64_t id_mul,
@@ -1500,18 +1500,10 @@ static int shardset_search_locked(rag_shardset* set, const float* q, int B, int 
                            hipStream_t st) {
   const int n = set->n;
   const bool packed = !full && k <= RAG_MAX_K_LARGE;
-  SetSlot* sp = nullptr;
-  for (auto& s : set->slot)
-    if (s.used && s.owner == st) { sp = &s; break; }
-  if (!sp)
-    for (auto& s : set->slot)
-      if (!s.used) { sp = &s; break; }
-  if (!sp) {
-    sp = &set->slot[0];
-    for (auto& s : set->slot)
-      if (s.tick < sp->tick) sp = &s;
-  }
-  SetSlot& sl = *sp;
+  // all slots busy: the least recently used one, after its `done` event (below)
+  SetSlot* lru = nullptr;
+  SetSlot* sp = pick_slot(set->slot, st, lru);
+  SetSlot& sl = sp ? *sp : *lru;
   RAG_HIP(hipSetDevice(set->dev0));
   if (sl.used && sl.owner != st) RAG_HIP(hipStreamWaitEvent(st, sl.done, 0));
   // stack: packed [n][B][k][2] int32, or scores [n][B][k] fp32 then ids [n][B][k] int64
@@ -1713,6 +1705,7 @@ int rag_bench_scan(rag_index_t* h, const float* queries_dev, int B, int variant,
     return ragmi::fail(RAG_EINVAL, "bad bench args");
   std::lock_guard<std::mutex> lk(h->mu);
   RAG_HIP(hipSetDevice(h->device));
+  // (not with_dim: each dim has its own probe, built for that dim alone)
   if (h->dim == 1024) {
     if (variant > 4) return ragmi::fail(RAG_EINVAL, "dim 1024: wide scan variants 0..4");
     return bench_wide<1024>(h, queries_dev, B, variant, reps, avg_ms);
