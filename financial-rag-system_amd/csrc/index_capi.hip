@@ -20,6 +20,7 @@
 #include "../../include/ragmi.h"
 #include "common_host.hpp"
 #include "scan_kernels.hip"
+#include "rows_kernels.hip"
 
 #include <hipcub/hipcub.hpp>
 
@@ -1087,6 +1088,42 @@ int bench_wide(rag_index* h, const float* q, int B, int mode, int reps, double* 
   return RAG_OK;
 }
 
+// The three indexed row copies behind move / gather / scatter: the shared argument checks,
+// then one copy_rows_kernel launch on `st` under the handle's lock. pk32 goes with fp32
+// storage exactly; new_count < 0 leaves the count alone (gather).
+template <int MODE>
+int copy_rows(rag_index* h, const int64_t* src_rows, const int64_t* dst_rows, int64_t n,
+              half8* pk16, float* pk32, uint32_t* pktags, int64_t new_count, void* stream) {
+  constexpr bool packed = MODE != ragmi::kRowsMove;
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
+  if (n < 0 || (n > 0 && ((MODE != ragmi::kRowsScatter && !src_rows) ||
+                          (MODE != ragmi::kRowsGather && !dst_rows))))
+    return ragmi::fail(RAG_EINVAL, "bad row list (n < 0, or n > 0 with NULL rows)");
+  if (packed && n > 0 && (!pk16 || !pktags))
+    return ragmi::fail(RAG_EINVAL, "packed fp16 rows and tags are required");
+  if (packed && n > 0 && (pk32 != nullptr) != (h->rows32 != nullptr))
+    return ragmi::fail(RAG_EINVAL, "packed fp32 rows go with fp32 storage, and only with it");
+  if (n > h->cap_rows) return ragmi::fail(RAG_ERANGE, "more rows than the index has slots");
+  if (new_count > h->cap_rows)
+    return ragmi::fail(RAG_ERANGE, "new_count exceeds capacity (call rag_index_reserve)");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  if (n > 0) {
+    const int rc = with_dim(h->dim, [&](auto d) {
+      const dim3 grid((unsigned)((n + ragmi::kRowsGroup - 1) / ragmi::kRowsGroup));
+      ragmi::copy_rows_kernel<decltype(d)::value, MODE><<<grid, dim3(ragmi::kRowsBlock), 0, st>>>(
+          h->corpus, h->rows32, h->tags, src_rows, dst_rows, n, h->cap_rows, pk16, pk32, pktags);
+      return RAG_OK;
+    });
+    if (rc) return rc;
+    RAG_HIP(hipGetLastError());
+  }
+  if (new_count >= 0) h->count = new_count;
+  return RAG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1386,6 +1423,64 @@ int rag_index_export_tags(rag_index_t* h, int64_t row0, int64_t n, uint32_t* out
     RAG_HIP(hipMemcpy(out, h->tags + row0, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RAG_OK;
   });
+}
+
+// ---- row removal: select, move, gather, scatter (rows_kernels.hip) ----
+
+int rag_index_select_rows(rag_index_t* h, uint32_t tag_mask, uint32_t tag_value,
+                          int64_t* out_rows, int64_t cap, int64_t* out_n, void* stream) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
+  if (!out_n || cap < 0 || (cap > 0 && !out_rows))
+    return ragmi::fail(RAG_EINVAL, "bad select args (out_n NULL, or cap > 0 without out_rows)");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  const int64_t count = h->count;
+  const int nb = (int)((count + ragmi::kSelChunk - 1) / ragmi::kSelChunk);
+  if (nb == 0) {
+    RAG_HIP(hipMemsetAsync(out_n, 0, sizeof(int64_t), st));
+    return RAG_OK;
+  }
+  StreamScratch offsets(st);   // matches per chunk, then their exclusive prefix sums
+  RAG_HIP(offsets.alloc((size_t)nb * sizeof(int64_t)));
+  int64_t* const off = reinterpret_cast<int64_t*>(offsets.p);
+  ragmi::select_count_kernel<<<dim3((unsigned)nb), dim3(ragmi::kSelBlock), 0, st>>>(
+      h->tags, count, tag_mask, tag_value, off);
+  ragmi::select_scan_kernel<<<dim3(1), dim3(ragmi::kSelScanBlock), 0, st>>>(off, nb, out_n);
+  if (cap > 0)
+    ragmi::select_emit_kernel<<<dim3((unsigned)nb), dim3(ragmi::kSelBlock), 0, st>>>(
+        h->tags, count, tag_mask, tag_value, off, out_rows, cap);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+int rag_index_move_rows(rag_index_t* h, const int64_t* src_rows, const int64_t* dst_rows,
+                        int64_t n, int64_t new_count, void* stream) {
+  if (new_count < 0) {
+    ragmi::clear_error();
+    return ragmi::fail(h ? RAG_ERANGE : RAG_EINVAL, h ? "new_count is negative" : "index is NULL");
+  }
+  return copy_rows<ragmi::kRowsMove>(h, src_rows, dst_rows, n, nullptr, nullptr, nullptr,
+                                     new_count, stream);
+}
+
+int rag_index_gather_rows(rag_index_t* h, const int64_t* rows, int64_t n, uint16_t* out_f16,
+                          float* out_f32, uint32_t* out_tags, void* stream) {
+  return copy_rows<ragmi::kRowsGather>(h, rows, nullptr, n, reinterpret_cast<half8*>(out_f16),
+                                       out_f32, out_tags, -1, stream);
+}
+
+int rag_index_scatter_rows(rag_index_t* h, const int64_t* rows, int64_t n, const uint16_t* in_f16,
+                           const float* in_f32, const uint32_t* in_tags, int64_t new_count,
+                           void* stream) {
+  if (new_count < 0) {
+    ragmi::clear_error();
+    return ragmi::fail(h ? RAG_ERANGE : RAG_EINVAL, h ? "new_count is negative" : "index is NULL");
+  }
+  return copy_rows<ragmi::kRowsScatter>(
+      h, nullptr, rows, n, reinterpret_cast<half8*>(const_cast<uint16_t*>(in_f16)),
+      const_cast<float*>(in_f32), const_cast<uint32_t*>(in_tags), new_count, stream);
 }
 
 int rag_merge_topk(const float* in_s, const int64_t* in_i, int n_lists, int B, int k,

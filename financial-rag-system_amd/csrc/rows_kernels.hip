@@ -1,0 +1,221 @@
+// rows_kernels.hip — row removal for the flat index (included by index_capi.hip after
+// scan_kernels.hip): the ordered tag select and the indexed row copies behind
+// rag_index_select_rows / move_rows / gather_rows / scatter_rows (include/ragmi.h).
+//
+// A deleted row is physically removed: a surviving row from the tail takes its slot in every
+// stored form (the fp16 tile16 pieces, the fp32 row of an fp32-storage index, the tag), bit
+// for bit, and the count shrinks. The index stays dense, so the scan, select, large-k and
+// full-pass kernels never learn that a delete happened ("Deleting points").
+// No reference counterpart beyond QdrantClient.delete itself: the reference only ever upserts
+// (ingest.py:171-175) and leaves removal to the Qdrant server.
+namespace ragmi {
+
+// ----------------------------------------------------------------------------------------
+// select: rows r < count with (tag[r] & mask) == value, ascending — an ordered stream
+// compaction over the tag array in three launches:
+//   select_count_kernel   matches per chunk of kSelChunk rows (one workgroup per chunk)
+//   select_scan_kernel    exclusive prefix sum over the chunks (one workgroup), total -> *out_n
+//   select_emit_kernel    each chunk re-reads its tags (L2 / Infinity Cache warm) and writes
+//                         its matches from its offset, in row order, while the offset < cap
+// Every position is a pure function of the tags: no atomics, the same output on every run.
+// A lane reads 4 consecutive tags as one dwordx4 (a wave 1 KiB per load).
+// ----------------------------------------------------------------------------------------
+constexpr int kSelBlock = 256;
+constexpr int kSelIters = 4;
+constexpr int kSelChunk = kSelBlock * 4 * kSelIters;   // rows per workgroup
+constexpr int kSelScanBlock = 1024;
+
+// f[j] = row r + j matches; r is a multiple of 4 and the tag array holds a multiple of 16
+// rows, so the 16-byte load stays inside it whenever r < count
+__device__ __forceinline__ void select_flags(const uint32_t* __restrict__ tags, int64_t r,
+                                             int64_t count, uint32_t mask, uint32_t value,
+                                             bool (&f)[4]) {
+  f[0] = f[1] = f[2] = f[3] = false;
+  if (r < count) {
+    const uint4 t = *reinterpret_cast<const uint4*>(tags + r);
+    f[0] = (t.x & mask) == value;
+    f[1] = r + 1 < count && (t.y & mask) == value;
+    f[2] = r + 2 < count && (t.z & mask) == value;
+    f[3] = r + 3 < count && (t.w & mask) == value;
+  }
+}
+
+__global__ __launch_bounds__(kSelBlock) void select_count_kernel(
+    const uint32_t* __restrict__ tags, int64_t count, uint32_t mask, uint32_t value,
+    int64_t* __restrict__ counts) {
+  __shared__ int wsum[kSelBlock / 64];
+  const int tid = threadIdx.x;
+  int c = 0;   // wave-uniform
+  for (int it = 0; it < kSelIters; ++it) {
+    const int64_t r = (int64_t)blockIdx.x * kSelChunk + it * (kSelBlock * 4) + tid * 4;
+    bool f[4];
+    select_flags(tags, r, count, mask, value, f);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c += __popcll(__ballot(f[j]));
+  }
+  if ((tid & 63) == 0) wsum[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) {
+    int s = 0;
+    for (int w = 0; w < kSelBlock / 64; ++w) s += wsum[w];
+    counts[blockIdx.x] = s;
+  }
+}
+
+// counts[0..nb) -> exclusive prefix sums in place; *out_n = the total
+__global__ __launch_bounds__(kSelScanBlock) void select_scan_kernel(int64_t* __restrict__ counts,
+                                                                    int nb,
+                                                                    int64_t* __restrict__ out_n) {
+  constexpr int kWaves = kSelScanBlock / 64;
+  __shared__ int wtot[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int64_t carry = 0;
+  for (int b0 = 0; b0 < nb; b0 += kSelScanBlock) {
+    const int i = b0 + tid;
+    const int v = i < nb ? (int)counts[i] : 0;   // <= kSelChunk each
+    int x = v;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(x, o);
+      if (lane >= o) x += y;
+    }
+    if (lane == 63) wtot[w] = x;
+    __syncthreads();
+    int wbase = 0, tot = 0;
+    for (int u = 0; u < kWaves; ++u) {
+      const int t = wtot[u];
+      if (u < w) wbase += t;
+      tot += t;
+    }
+    if (i < nb) counts[i] = carry + wbase + x - v;
+    carry += tot;
+    __syncthreads();
+  }
+  if (tid == 0) *out_n = carry;
+}
+
+__global__ __launch_bounds__(kSelBlock) void select_emit_kernel(
+    const uint32_t* __restrict__ tags, int64_t count, uint32_t mask, uint32_t value,
+    const int64_t* __restrict__ offsets, int64_t* __restrict__ out, int64_t cap) {
+  __shared__ int wcnt[kSelBlock / 64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int64_t base = offsets[blockIdx.x];
+  if (base >= cap) return;   // the whole chunk lies past the output (uniform)
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int it = 0; it < kSelIters; ++it) {
+    const int64_t r = (int64_t)blockIdx.x * kSelChunk + it * (kSelBlock * 4) + tid * 4;
+    bool f[4];
+    select_flags(tags, r, count, mask, value, f);
+    int pre = 0, wc = 0;   // matches in lower lanes / in the wave: lanes own rows in order
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned long long b = __ballot(f[j]);
+      pre += __popcll(b & below);
+      wc += __popcll(b);
+    }
+    if (lane == 0) wcnt[w] = wc;
+    __syncthreads();
+    int wbase = 0, tot = 0;
+    for (int u = 0; u < kSelBlock / 64; ++u) {
+      const int t = wcnt[u];
+      if (u < w) wbase += t;
+      tot += t;
+    }
+    int64_t pos = base + wbase + pre;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (f[j]) {
+        if (pos < cap) out[pos] = r + j;   // never past cap
+        ++pos;
+      }
+    base += tot;
+    __syncthreads();
+  }
+}
+
+// ----------------------------------------------------------------------------------------
+// indexed row copies. One workgroup per group of 16 (source, destination) pairs — a tile's
+// worth, and the movers of a delete are mostly a contiguous tail, the holes often a
+// contiguous run — copying every stored form of the rows:
+//   kRowsMove     index row src[i] -> index row dst[i]        (in place; sets disjoint)
+//   kRowsGather   index row rows[i] -> packed staging row i   (rows = src_rows)
+//   kRowsScatter  packed staging row i -> index row rows[i]   (rows = dst_rows)
+// Packed staging is row-major: pk16 [n][D/8] half8, pk32 [n][D] float, pktags [n].
+// Lane order of the fp16 pieces: a wave takes one 32-dim k-step of the 16 rows, which in the
+// tile is one contiguous 1 KiB when the rows are a tile (lane = hh * 16 + r, the layout's own
+// order, for the move; for the packed forms the 4 pieces of a row's k-step go to neighbouring
+// lanes, 64 contiguous bytes on the packed side and the same 1 KiB on the tile side).
+// The fp32 rows are row-major on both sides: a wave copies 1 KiB of one row per instruction.
+// An index row outside [0, cap_rows) is never dereferenced: its pair is skipped.
+// ----------------------------------------------------------------------------------------
+constexpr int kRowsBlock = 256;
+constexpr int kRowsGroup = 16;
+enum { kRowsMove = 0, kRowsGather = 1, kRowsScatter = 2 };
+
+// half8 slot of piece c (halves 8c .. 8c+7) of row `row` in the tile16 layout
+template <int D>
+__device__ __forceinline__ int64_t tile_slot(int64_t row, int c) {
+  return (row >> 4) * (steps<D>() * 64) + (c >> 2) * 64 + (c & 3) * 16 + (row & 15);
+}
+
+template <int D, int MODE>
+__global__ __launch_bounds__(kRowsBlock) void copy_rows_kernel(
+    half8* corpus, float* rows32, uint32_t* tags, const int64_t* __restrict__ src_rows,
+    const int64_t* __restrict__ dst_rows, int64_t n, int64_t cap_rows, half8* pk16, float* pk32,
+    uint32_t* pktags) {
+  __shared__ int64_t s_src[kRowsGroup], s_dst[kRowsGroup];
+  const int tid = threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * kRowsGroup;
+  if (tid < kRowsGroup) {
+    const int64_t i = base + tid;
+    int64_t s = -1, d = -1;
+    if (i < n) {
+      s = MODE == kRowsScatter ? i : src_rows[i];
+      d = MODE == kRowsGather ? i : dst_rows[i];
+      const bool s_ok = MODE == kRowsScatter || (s >= 0 && s < cap_rows);
+      const bool d_ok = MODE == kRowsGather || (d >= 0 && d < cap_rows);
+      if (!s_ok || !d_ok) s = d = -1;
+    }
+    s_src[tid] = s;
+    s_dst[tid] = d;
+  }
+  __syncthreads();
+  constexpr int kPieces = D / 8;
+  for (int e = tid; e < kRowsGroup * kPieces; e += kRowsBlock) {
+    int j, c;
+    if (MODE == kRowsMove) {
+      j = e & 15;
+      c = e >> 4;
+    } else {
+      j = (e >> 2) & 15;
+      c = ((e >> 6) << 2) | (e & 3);
+    }
+    const int64_t s = s_src[j], d = s_dst[j];
+    if (s < 0) continue;
+    const half8 v = MODE == kRowsScatter ? pk16[s * kPieces + c] : corpus[tile_slot<D>(s, c)];
+    if (MODE == kRowsGather)
+      pk16[d * kPieces + c] = v;
+    else
+      corpus[tile_slot<D>(d, c)] = v;
+  }
+  if (rows32) {
+    constexpr int kQuads = D / 4;
+    for (int e = tid; e < kRowsGroup * kQuads; e += kRowsBlock) {
+      const int j = e / kQuads, c = e % kQuads;
+      const int64_t s = s_src[j], d = s_dst[j];
+      if (s < 0) continue;
+      const float4* from = reinterpret_cast<const float4*>((MODE == kRowsScatter ? pk32 : rows32) + s * D);
+      float4* to = reinterpret_cast<float4*>((MODE == kRowsGather ? pk32 : rows32) + d * D);
+      to[c] = from[c];
+    }
+  }
+  if (tid < kRowsGroup && s_src[tid] >= 0) {
+    const int64_t s = s_src[tid], d = s_dst[tid];
+    const uint32_t t = MODE == kRowsScatter ? pktags[s] : tags[s];
+    if (MODE == kRowsGather)
+      pktags[d] = t;
+    else
+      tags[d] = t;
+  }
+}
+
+}  // namespace ragmi

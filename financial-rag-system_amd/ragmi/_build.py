@@ -14,7 +14,8 @@ ARCH = "gfx950"
 
 # translation units of libragmi.so
 SOURCES = ["index_capi.hip", "bert_capi.hip", "wordpiece_capi.cpp"]
-HEADERS = ["device_common.hpp", "common_host.hpp", "scan_kernels.hip", "bert_kernels.hip"]
+HEADERS = ["device_common.hpp", "common_host.hpp", "scan_kernels.hip", "rows_kernels.hip",
+           "bert_kernels.hip"]
 
 
 def _inputs():

@@ -111,6 +111,14 @@ INDEX_API = {
     "rag_index_export_tags": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_u32p]),
     "rag_index_import_rows": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int64, c_u16p,
                                              c_u32p, ctypes.c_int64]),
+    "rag_index_select_rows": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, c_vp,
+                                             ctypes.c_int64, c_vp, c_vp]),
+    "rag_index_move_rows": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64,
+                                           c_vp]),
+    "rag_index_gather_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp,
+                                             c_vp]),
+    "rag_index_scatter_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp,
+                                              ctypes.c_int64, c_vp]),
     "rag_merge_topk": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       c_vp, c_vp, c_vp]),
     "rag_merge_topk_packed": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

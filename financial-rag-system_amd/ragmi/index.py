@@ -38,6 +38,26 @@ def _as_dev(x, dtype, device) -> torch.Tensor:
     return t.contiguous()
 
 
+def plan_removal(count: int, rows):
+    """The removal rule, the one place every layer takes it from (FlatIndex.remove_rows,
+    ShardSet.remove_rows, Collection.delete). `rows`: the rows to delete, in [0, count),
+    duplicates allowed. With D the distinct deleted rows and n1 = count - |D|: the holes
+    D ∩ [0, n1), ascending, receive the survivors of the tail [n1, count) \\ D, ascending, pair
+    by pair; no other row moves. Returns (src, dst, n1): row src[i] moves to slot dst[i]
+    (int64 arrays, both ascending, src >= n1 > dst) and n1 is the new count. At most |D| rows
+    move, so a delete costs what it deletes, not what the collection holds. Pure host code."""
+    count = int(count)
+    d = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
+    if d.size and (d[0] < 0 or d[-1] >= count):
+        raise IndexError(f"rows to remove must lie in [0, {count})")
+    n1 = count - int(d.size)
+    dst = d[d < n1]
+    stays = np.ones(count - n1, dtype=bool)
+    stays[d[d >= n1] - n1] = False
+    src = n1 + np.nonzero(stays)[0].astype(np.int64)
+    return src, dst, n1
+
+
 class FlatIndex:
     """In-HBM flat index with exact (score desc, row asc) top-k search. storage "fp16": the
     fp16 rows only (what the scan streams); "fp32": the normalised fp32 rows too, which the
@@ -170,6 +190,88 @@ class FlatIndex:
         # staging tensors (q, f) go back to torch's stream-ordered caching allocator: any
         # reuse is enqueued on this same stream after our kernels, so no sync is needed.
         return out_s, out_i
+
+    # ---------------------------------------------------------------- row removal
+    def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None,
+                    out: torch.Tensor | None = None):
+        """Rows r < count with (tag[r] & tag_mask) == tag_value, ascending
+        (rag_index_select_rows): (rows int64 cuda tensor, total). At most `cap` rows are
+        written (default: every match), the first ones; `total` counts every match. cap = 0 is
+        a pure count. `out`: an int64 cuda tensor of at least `cap` elements to write into.
+        Synchronises the current stream (the total is read back)."""
+        if cap is None:
+            cap = self.count if out is None else min(self.count, out.numel())
+        cap = int(cap)
+        if cap < 0:
+            raise ValueError("cap must be >= 0")
+        if out is None:
+            out = torch.empty((cap,), dtype=torch.int64, device=self.device)
+        elif out.dtype != torch.int64 or out.device != self.device or out.numel() < cap \
+                or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int64 tensor of >= cap elements on the "
+                             "index's device")
+        n = torch.empty((1,), dtype=torch.int64, device=self.device)
+        check(self._L.rag_index_select_rows(self._h, int(tag_mask) & 0xFFFFFFFF,
+                                            int(tag_value) & 0xFFFFFFFF,
+                                            out.data_ptr() if cap else None, cap, n.data_ptr(),
+                                            _stream_ptr(self.device)))
+        total = int(n.item())
+        return out[:min(total, cap)], total
+
+    def move_rows(self, src, dst, new_count: int) -> None:
+        """Copy every stored form of row src[i] into slot dst[i], bit for bit, then set the
+        count (rag_index_move_rows). The src and dst sets must be disjoint."""
+        s = _as_dev(src, torch.int64, self.device).reshape(-1)
+        d = _as_dev(dst, torch.int64, self.device).reshape(-1)
+        if s.shape != d.shape:
+            raise ValueError("src and dst must pair up")
+        check(self._L.rag_index_move_rows(self._h, s.data_ptr() if s.numel() else None,
+                                          d.data_ptr() if s.numel() else None, s.numel(),
+                                          int(new_count), _stream_ptr(self.device)))
+
+    def gather_rows(self, rows):
+        """The stored forms of `rows` (any slots below capacity) packed row-major on the
+        device: (fp16 bits int16 [n, dim], fp32 [n, dim] or None on fp16 storage, tags int32
+        [n]) — rag_index_gather_rows, the staging form scatter_rows takes."""
+        r = _as_dev(rows, torch.int64, self.device).reshape(-1)
+        n = r.numel()
+        f16 = torch.empty((n, self.dim), dtype=torch.int16, device=self.device)
+        f32 = (torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+               if self.storage == "fp32" else None)
+        tags = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if n:
+            check(self._L.rag_index_gather_rows(self._h, r.data_ptr(), n, f16.data_ptr(),
+                                                f32.data_ptr() if f32 is not None else None,
+                                                tags.data_ptr(), _stream_ptr(self.device)))
+        return f16, f32, tags
+
+    def scatter_rows(self, rows, f16, f32, tags, new_count: int) -> None:
+        """Write packed rows (gather_rows' form, tensors on this device) to the distinct
+        slots `rows`, bit for bit, then set the count (rag_index_scatter_rows)."""
+        r = _as_dev(rows, torch.int64, self.device).reshape(-1)
+        n = r.numel()
+        f16 = _as_dev(f16, torch.int16, self.device)
+        tags = _as_dev(tags, torch.int32, self.device)
+        if (f32 is not None) != (self.storage == "fp32"):
+            raise ValueError("fp32 rows go with fp32 storage, and only with it")
+        if f32 is not None:
+            f32 = _as_dev(f32, torch.float32, self.device)
+            if tuple(f32.shape) != (n, self.dim):
+                raise ValueError(f"f32 must be [n, {self.dim}]")
+        if tuple(f16.shape) != (n, self.dim) or tuple(tags.shape) != (n,):
+            raise ValueError(f"f16 must be [n, {self.dim}] and tags [n]")
+        check(self._L.rag_index_scatter_rows(
+            self._h, r.data_ptr() if n else None, n, f16.data_ptr() if n else None,
+            f32.data_ptr() if n and f32 is not None else None, tags.data_ptr() if n else None,
+            int(new_count), _stream_ptr(self.device)))
+
+    def remove_rows(self, rows):
+        """Delete `rows` (host integers in [0, count), duplicates allowed): plan_removal, then
+        one move_rows. Returns the plan (src, dst, new_count) for the caller's own per-row
+        state. Enqueued on the current stream."""
+        src, dst, n1 = plan_removal(self.count, rows)
+        self.move_rows(src, dst, n1)
+        return src, dst, n1
 
     # ---------------------------------------------------------------- introspection
     def export_rows(self, row0: int = 0, n: int | None = None) -> np.ndarray:

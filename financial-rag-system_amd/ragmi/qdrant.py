@@ -8,7 +8,7 @@ Drop-in for the calls the reference makes on `qdrant_client.QdrantClient`:
   query_points(name, query, limit, query_filter) -> .points[i].{id,score,payload}
                                           main.py:232-237, main2.py:163
 plus query_batch_points (one GPU scan for a whole micro-batch; main2.py:281-295 stage 2),
-count, retrieve and delete_collection.
+count (also filtered), retrieve, delete (by ids or by filter) and delete_collection.
 
 `url` is accepted and ignored: the collection lives in this process's GPU memory (the
 Qdrant service of docker-compose.yml:22 is replaced, not contacted). `path=` plays the role
@@ -144,8 +144,13 @@ class Coalescer:
     to that long to gather more callers. Results are bit-identical to individual calls: every
     query's top-k is exact, independent of its batch-mates (tests/test_qdrant_gpu.py)."""
 
-    def __init__(self, col: "Collection", window_s: float = 0.0, max_batch: int = 32):
+    def __init__(self, col: "Collection", window_s: float = 0.0, max_batch: int = 32,
+                 search=None):
         self.col = col
+        # what a leader calls for its batch: col.search (rows and scores), or for a Collection
+        # its search_points, whose hits are resolved to points before the collection's lock is
+        # released — a rider must not look rows up after a delete may have moved them
+        self.search_fn = search
         self.window = float(window_s)
         self.max_batch = int(max_batch)
         self.lock = threading.Lock()
@@ -182,8 +187,9 @@ class Coalescer:
                 batch = self.pending[:self.max_batch]
                 del self.pending[:self.max_batch]
                 self.batches += 1
-            hits = self.col.search(np.stack([r.q for r in batch]),
-                                   max(r.limit for r in batch), [r.filt for r in batch])
+            hits = (self.search_fn or self.col.search)(
+                np.stack([r.q for r in batch]), max(r.limit for r in batch),
+                [r.filt for r in batch])
             for r, h in zip(batch, hits):
                 r.result = h[:r.limit]
         except BaseException as e:                 # every rider sees the failure
@@ -211,6 +217,25 @@ class Coalescer:
         if req.exc is not None:
             raise req.exc
         return req.result
+
+
+def parse_selector(points_selector):
+    """The `points_selector` of QdrantClient.delete -> ("ids", [normalised ids]) or
+    ("filter", Filter): a plain list of ids, a PointIdsList, a FilterSelector or a bare
+    Filter."""
+    sel = points_selector
+    if isinstance(sel, models.FilterSelector):
+        if sel.filter is None:
+            raise ValueError("FilterSelector needs a filter")
+        return "filter", sel.filter
+    if isinstance(sel, models.Filter):
+        return "filter", sel
+    if isinstance(sel, models.PointIdsList):
+        sel = sel.points
+    if isinstance(sel, (str, bytes, dict)) or not hasattr(sel, "__iter__"):
+        raise ValueError("points_selector must be a list of ids, a PointIdsList, a "
+                         "FilterSelector or a Filter")
+    return "ids", [_norm_id(pid) for pid in sel]
 
 
 def _storage_of(vectors_config) -> str:
@@ -249,7 +274,8 @@ class Collection:
         self.rescued = 0         # queries re-answered on the full exact pass (stats)
         self.lock = threading.RLock()
         # 32 queries per scan pass at D = 384, 4 groups of 32 at D = 1024 (ragmi.h)
-        self.coalescer = Coalescer(self, 0.0, 32 if dim <= 384 else 128)
+        self.coalescer = Coalescer(self, 0.0, 32 if dim <= 384 else 128,
+                                   search=self.search_points)
 
     def compile_filter(self, flt):
         return self.tags.compile(flt)
@@ -291,7 +317,66 @@ class Collection:
                                   np.asarray(tags, dtype=np.uint32), new_count=new_count)
             return self.op
 
+    def delete(self, points_selector) -> int:
+        """Remove the selected points (parse_selector). Unknown ids are ignored, duplicates
+        collapse, a filter on a never-ingested value selects nothing; a filter is resolved on
+        the device (select_rows over the tags), never by walking the payloads. The rows are
+        removed from the index by the removal rule (ragmi.index.plan_removal) and the same
+        (src, dst) moves are applied to the host maps: a moved point keeps its id, payload
+        and version. Returns the operation id. The device work has finished on return."""
+        kind, what = parse_selector(points_selector)
+        with self.lock:
+            flt = self.tags.compile(what) if kind == "filter" else None   # may refuse the filter
+            self.op += 1
+            if kind == "ids":
+                found = {self.id_to_row[pid] for pid in what if pid in self.id_to_row}
+                rows = np.fromiter(found, dtype=np.int64, count=len(found))
+            else:
+                if flt is None or not self.row_ids:
+                    rows = np.empty(0, np.int64)
+                elif flt == (0, 0):
+                    rows = np.arange(len(self.row_ids), dtype=np.int64)
+                else:
+                    rows = self.index.select_rows(flt[0], flt[1])[0].cpu().numpy()
+            if rows.size:
+                src, dst, n1 = self.index.remove_rows(rows)
+                self._apply_removal(rows, src, dst, n1)
+                torch.cuda.current_stream(self.index.device).synchronize()
+            return self.op
+
+    def _apply_removal(self, rows, src, dst, n1: int) -> None:
+        """The host side of a removal: forget the deleted rows' ids, give every moved row's
+        id, payload and version its new slot, truncate to the new count."""
+        for r in rows.tolist():
+            del self.id_to_row[self.row_ids[r]]
+        for s, d in zip(src.tolist(), dst.tolist()):
+            pid = self.row_ids[s]
+            self.row_ids[d] = pid
+            self.payloads[d] = self.payloads[s]
+            self.versions[d] = self.versions[s]
+            self.id_to_row[pid] = d
+        del self.row_ids[n1:], self.payloads[n1:], self.versions[n1:]
+
     # ---------------------------------------------------------------- reads
+    def count_matching(self, flt) -> int:
+        """Points a Filter matches, counted on the device (select_rows with cap = 0)."""
+        with self.lock:
+            c = self.tags.compile(flt)
+            if c is None or not self.row_ids:
+                return 0
+            if c == (0, 0):
+                return len(self.row_ids)
+            return self.index.select_rows(c[0], c[1], cap=0)[1]
+
+    def search_points(self, queries, limit: int, filters: list, with_vectors=False):
+        """search with every hit resolved to its ScoredPoint (payload attached) under the same
+        hold of the lock as the search that produced it: a delete moves rows, so a row number
+        means a point only while the lock is held. What query_points, query_batch_points and
+        the coalescer's leaders call."""
+        with self.lock:
+            return [[self.point(r, s, True, with_vectors) for r, s in h]
+                    for h in self.search(queries, limit, filters)]
+
     def search(self, queries, limit: int, filters: list):
         """queries [B, dim]; filters: per query compiled filter ((mask, value) or None)."""
         with self.lock:
@@ -349,6 +434,14 @@ class Collection:
                    self.index.export_rows(row, 1)[0].view(np.float16).astype(np.float32)).tolist()
         return models.ScoredPoint(id=self.row_ids[row], version=self.versions[row],
                                   score=score, payload=payload, vector=vec)
+
+
+def _payloads(points: list, with_payload) -> list:
+    """search_points' hits (each call's own objects) as the caller asked for them."""
+    if not with_payload:
+        for p in points:
+            p.payload = None
+    return points
 
 
 class QdrantClient:
@@ -454,18 +547,30 @@ class QdrantClient:
         op = col.upsert(ids, vecs, pls)
         return models.UpdateResult(operation_id=op, status=models.UpdateStatus.COMPLETED)
 
-    def count(self, collection_name: str, **kwargs) -> models.CountResult:
-        return models.CountResult(count=len(self._col(collection_name).row_ids))
+    def delete(self, collection_name: str, points_selector, wait: bool = True,
+               **kwargs) -> models.UpdateResult:
+        """Remove points: `points_selector` is a list of ids, a PointIdsList, a
+        FilterSelector or a bare Filter (the `must` class query_points supports)."""
+        op = self._col(collection_name).delete(points_selector)
+        return models.UpdateResult(operation_id=op, status=models.UpdateStatus.COMPLETED)
+
+    def count(self, collection_name: str, count_filter: models.Filter | None = None,
+              exact: bool = True, **kwargs) -> models.CountResult:
+        col = self._col(collection_name)
+        if count_filter is None:
+            return models.CountResult(count=len(col.row_ids))
+        return models.CountResult(count=col.count_matching(count_filter))
 
     def retrieve(self, collection_name: str, ids, with_payload=True, with_vectors=False,
                  **kwargs):
         col = self._col(collection_name)
         out = []
-        for pid in ids:
-            r = col.id_to_row.get(_norm_id(pid))
-            if r is not None:
-                p = col.point(r, 0.0, with_payload, with_vectors)
-                out.append(models.Record(id=p.id, payload=p.payload, vector=p.vector))
+        with col.lock:                    # rows move under a delete
+            for pid in ids:
+                r = col.id_to_row.get(_norm_id(pid))
+                if r is not None:
+                    p = col.point(r, 0.0, with_payload, with_vectors)
+                    out.append(models.Record(id=p.id, payload=p.payload, vector=p.vector))
         return out
 
     def query_points(self, collection_name: str, query=None, limit: int = 10,
@@ -473,20 +578,19 @@ class QdrantClient:
                      with_vectors=False, **kwargs) -> models.QueryResponse:
         col = self._col(collection_name)
         flt = col.compile_filter(query_filter)
-        if self.coalesce and 1 <= int(limit) <= MAX_K:
+        if self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
             q = (query.detach().float().cpu().numpy() if isinstance(query, torch.Tensor)
                  else np.asarray(query, dtype=np.float32))
             if q.shape != (col.dim,):
                 q = q.reshape(-1)
                 if q.shape != (col.dim,):
                     raise ValueError(f"query must be one {col.dim}-dim vector")
-            hits = col.coalescer.search(q, int(limit), flt)
+            pts = col.coalescer.search(q, int(limit), flt)
         else:
             q = query if isinstance(query, torch.Tensor) else np.asarray(query, dtype=np.float32)
             q = q.reshape(1, -1)
-            hits = col.search(q, int(limit), [flt])[0]
-        return models.QueryResponse(points=[col.point(r, s, with_payload, with_vectors)
-                                            for r, s in hits])
+            pts = col.search_points(q, int(limit), [flt], with_vectors)[0]
+        return models.QueryResponse(points=_payloads(pts, with_payload))
 
     def query_batch_points(self, collection_name: str, requests: list,
                            **kwargs) -> list[models.QueryResponse]:
@@ -499,9 +603,8 @@ class QdrantClient:
         Q = torch.stack([x if isinstance(x, torch.Tensor) else
                          torch.as_tensor(np.asarray(x, np.float32)) for x in qs]) \
             if any(isinstance(x, torch.Tensor) for x in qs) else np.asarray(qs, np.float32)
-        hits = col.search(Q, limit, [col.compile_filter(r.filter) for r in requests])
-        return [models.QueryResponse(points=[col.point(i, s, r.with_payload)
-                                             for i, s in h[:int(r.limit)]])
+        hits = col.search_points(Q, limit, [col.compile_filter(r.filter) for r in requests])
+        return [models.QueryResponse(points=_payloads(h[:int(r.limit)], r.with_payload))
                 for r, h in zip(requests, hits)]
 
     def search(self, collection_name: str, query_vector, limit: int = 10,

@@ -79,6 +79,20 @@ class Filter:
 
 
 @dataclass
+class PointIdsList:
+    """Points selector of QdrantClient.delete: the points with these ids."""
+    points: list = field(default_factory=list)
+    shard_key: Any = None
+
+
+@dataclass
+class FilterSelector:
+    """Points selector of QdrantClient.delete: the points a Filter matches."""
+    filter: Optional[Filter] = None
+    shard_key: Any = None
+
+
+@dataclass
 class ScoredPoint:
     id: ExtendedPointId
     version: int

@@ -50,6 +50,20 @@ def shard_count(count: int, shard: int, n: int) -> int:
     return max(0, -((shard - count) // n))
 
 
+def shard_moves(src, dst, n: int) -> dict:
+    """A removal plan in global rows (plan_removal's src -> dst pairs) split by shards:
+    {(source shard, destination shard): (local source rows, local destination rows)}, pairs in
+    plan order, only the shard pairs that occur."""
+    src = np.asarray(src, dtype=np.int64)
+    dst = np.asarray(dst, dtype=np.int64)
+    ss, ds = shard_of(src, n), shard_of(dst, n)
+    out = {}
+    for s, d in sorted(set(zip(ss.tolist(), ds.tolist()))):
+        sel = (ss == s) & (ds == d)
+        out[(s, d)] = (local_of(src[sel], n), local_of(dst[sel], n))
+    return out
+
+
 def parse_devices(spec, device_count: int | None = None) -> list[int] | None:
     """The `devices` argument of QdrantClient / the RAGMI_DEVICES variable -> device indices.
     None or "" -> None (one FlatIndex on one device, no shard set); "all" -> every visible
@@ -251,6 +265,51 @@ class ShardSet:
                 shard.set_count(cnt)
             self._settle(shard)
         self._count = int(new_count)
+
+    # ---------------------------------------------------------------- row removal
+    @_keeps_device
+    def remove_rows(self, global_rows):
+        """FlatIndex.remove_rows in global rows: the one plan (plan_removal), each (src, dst)
+        pair mapped to (shard, local row) by shard_moves. Pairs inside a shard are one
+        move_rows there; pairs between two shards are gathered on the source, the packed
+        staging tensors copied to the destination's device (no kernel reads another GPU's
+        memory) and scattered there. Local sources lie at or past their shard's new count and
+        local destinations below it, so no pair waits for another. Returns the global plan
+        (src, dst, new_count)."""
+        from .index import plan_removal
+        src, dst, n1 = plan_removal(self._count, global_rows)
+        for (s, d), (ls, ld) in shard_moves(src, dst, self.n).items():
+            cnt = shard_count(n1, d, self.n)
+            if s == d:
+                self.shards[s].move_rows(ls, ld, cnt)
+            else:
+                f16, f32, tags = self.shards[s].gather_rows(ls)
+                to = self.shards[d].device
+                self.shards[d].scatter_rows(ld, f16.to(to), f32.to(to) if f32 is not None
+                                            else None, tags.to(to), cnt)
+        for s, shard in enumerate(self.shards):
+            cnt = shard_count(n1, s, self.n)
+            if shard.count != cnt:
+                shard.set_count(cnt)
+            self._settle(shard)
+        self._count = n1
+        return src, dst, n1
+
+    @_keeps_device
+    def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None):
+        """FlatIndex.select_rows over the set: each shard's selection mapped to global rows,
+        merged ascending on the merge device: (rows int64 cuda tensor, total). The first
+        `cap` global matches lie among each shard's first `cap`."""
+        parts, total = [], 0
+        for s, shard in enumerate(self.shards):
+            rows, n = shard.select_rows(tag_mask, tag_value, cap)
+            total += n
+            if rows.numel():
+                parts.append((rows * self.n + s).to(self.device))
+        if not parts:
+            return torch.empty((0,), dtype=torch.int64, device=self.device), total
+        merged = torch.sort(torch.cat(parts)).values
+        return (merged if cap is None else merged[:int(cap)]), total
 
     # ---------------------------------------------------------------- search
     @_keeps_device

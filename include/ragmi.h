@@ -183,6 +183,43 @@ int rag_index_import_rows32(rag_index_t* index, int64_t row0, int64_t n, const f
 /* Copy stored tags of rows [row0, row0+n) to host. */
 int rag_index_export_tags(rag_index_t* index, int64_t row0, int64_t n, uint32_t* out_host);
 
+/* Row removal (QdrantClient.delete; the reference itself only upserts, ingest.py:171-175, and
+ * leaves deletion to the Qdrant server it talks to). A deleted row is physically removed: a
+ * surviving row from the tail is moved into its slot and the count shrinks, so the index stays
+ * dense and every search kernel runs unchanged. Removal rule (ragmi.index.plan_removal, the
+ * one every layer follows): with D the distinct deleted rows and n1 = count - |D|, the holes
+ * D ∩ [0, n1) ascending receive the survivors of [n1, count) ascending, pair by pair; no other
+ * row moves; the new count is n1. All four calls are asynchronous on `stream`, take the
+ * handle's lock and never dereference a row index outside [0, capacity): such a pair is
+ * skipped.
+ *
+ * rag_index_select_rows: the rows r < count with (tag[r] & tag_mask) == tag_value, ascending,
+ * into out_rows_dev (int64, device) — at most `cap` of them, the first `cap` matches, nothing
+ * past out_rows_dev[cap - 1] — and the total number of matches into *out_n_dev (int64,
+ * device), also when it exceeds `cap`. cap = 0 with out_rows_dev NULL is a pure count; (0, 0)
+ * selects every row. The order of the output is deterministic (count / prefix sum / emit). */
+int rag_index_select_rows(rag_index_t* index, uint32_t tag_mask, uint32_t tag_value,
+                          int64_t* out_rows_dev, int64_t cap, int64_t* out_n_dev, void* stream);
+/* Copy every stored form of row src_rows_dev[i] into slot dst_rows_dev[i] (int64 [n], device):
+ * the fp16 tile16 pieces, the fp32 row of an fp32-storage index and the tag, bit for bit (no
+ * renormalisation), one read and one write per byte; then count = new_count.
+ * Precondition: the src and dst sets are disjoint (a row is never both read and written). */
+int rag_index_move_rows(rag_index_t* index, const int64_t* src_rows_dev,
+                        const int64_t* dst_rows_dev, int64_t n, int64_t new_count, void* stream);
+/* The same copy through a packed row-major staging form, for moves between the shards of a set:
+ * [n][dim] fp16 bits, [n][dim] fp32, [n] tags (device). gather reads rows rows_dev[i] (at any
+ * slot below capacity, the count is not consulted or changed) into staging row i; scatter
+ * writes staging row i to slot rows_dev[i] (distinct slots) and sets count = new_count. The
+ * f32 pointer is required exactly when storage is RAG_STORE_FP32 (NULL otherwise); the fp16
+ * and tag pointers always. The indexed, device-side counterparts of rag_index_export_rows /
+ * rag_index_import_rows. */
+int rag_index_gather_rows(rag_index_t* index, const int64_t* rows_dev, int64_t n,
+                          uint16_t* out_f16_dev, float* out_f32_dev, uint32_t* out_tags_dev,
+                          void* stream);
+int rag_index_scatter_rows(rag_index_t* index, const int64_t* rows_dev, int64_t n,
+                           const uint16_t* in_f16_dev, const float* in_f32_dev,
+                           const uint32_t* in_tags_dev, int64_t new_count, void* stream);
+
 /* Merge n_lists per-shard result lists (each [B][k] sorted by (score desc, id asc), device;
  * laid out [n_lists][B][k]; padding: id -1) into the global top-k [B][k] (device) by (score
  * desc, id asc), padding -inf / -1 past the valid entries. Any k >= 1 (k > RAG_MAX_K_LARGE:
