@@ -78,9 +78,66 @@ class Knob {
   std::atomic<bool> warned_{false};
 };
 
+// ---- device buffers of the host layers (index_capi.hip, bert_capi.hip) ---------------------
+// a hipMalloc buffer freed on every return path; release() hands it to a longer-lived owner
+template <typename T>
+struct DeviceBuf {
+  T* p = nullptr;
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf&) = delete;
+  ~DeviceBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t bytes) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+  T* release() {
+    T* r = p;
+    p = nullptr;
+    return r;
+  }
+};
+
+// One device buffer of a workspace: where its pointer lives, its size (0: not part of this
+// configuration), zeroed at creation or not. A group of buffers that live and grow together
+// is a table of these (a std::array returned by one function), in allocation order.
+struct WsBuf {
+  void** p;
+  size_t bytes;
+  bool zero;
+};
+template <typename T>
+WsBuf ws_buf(T*& p, size_t bytes, bool zero = false) {
+  return {reinterpret_cast<void**>(&p), bytes, zero};
+}
+
+// frees what the table's buffers hold and nulls them
+template <typename Bufs>
+void ws_free_all(const Bufs& bufs) {
+  for (const WsBuf& b : bufs) {
+    if (*b.p) (void)hipFree(*b.p);
+    *b.p = nullptr;
+  }
+}
+
+// One hipMalloc per buffer, in the table's order (the buffers hold nothing before), then the
+// memsets. All or none: a failure frees what was allocated, so a group is never half-filled.
+template <typename Bufs>
+hipError_t ws_alloc_all(const Bufs& bufs) {
+  hipError_t e = hipSuccess;
+  for (const WsBuf& b : bufs)
+    if (b.bytes && e == hipSuccess && (e = hipMalloc(b.p, b.bytes)) != hipSuccess) *b.p = nullptr;
+  for (const WsBuf& b : bufs)
+    if (b.zero && e == hipSuccess) e = hipMemset(*b.p, 0, b.bytes);
+  if (e != hipSuccess) ws_free_all(bufs);
+  return e;
+}
+
 }  // namespace ragmi
 
-#define RAG_HIP(expr)                                                                   \
+#define RAG_HIP(expr)                                                                  \
   do {                                                                                  \
     hipError_t _e = (expr);                                                             \
     if (_e != hipSuccess)                                                               \

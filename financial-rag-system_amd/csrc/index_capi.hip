@@ -25,6 +25,9 @@
 #include <hipcub/hipcub.hpp>
 
 using ragmi::half8;
+using ragmi::DeviceBuf;
+using ragmi::WsBuf;
+using ragmi::ws_buf;
 
 namespace {
 
@@ -140,27 +143,6 @@ struct StreamScratch {
   hipError_t alloc(size_t bytes) { return hipMallocAsync(reinterpret_cast<void**>(&p), bytes, st); }
 };
 
-// a hipMalloc buffer; release() hands it to a longer-lived owner
-template <typename T>
-struct DeviceBuf {
-  T* p = nullptr;
-  DeviceBuf() = default;
-  DeviceBuf(const DeviceBuf&) = delete;
-  ~DeviceBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) {
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes);
-    if (e != hipSuccess) p = nullptr;
-    return e;
-  }
-  T* release() {
-    T* r = p;
-    p = nullptr;
-    return r;
-  }
-};
-
 // a pair of timing events
 struct EventPair {
   hipEvent_t a = nullptr, b = nullptr;
@@ -189,17 +171,6 @@ int time_launches(int reps, F&& one, float* ms) {
   RAG_HIP(hipEventSynchronize(ev.b));
   RAG_HIP(hipEventElapsedTime(ms, ev.a, ev.b));
   return RAG_OK;
-}
-
-// One device buffer of a Workspace: where its pointer lives, its size, zeroed at creation or not
-struct WsBuf {
-  void** p;
-  size_t bytes;
-  bool zero;
-};
-template <typename T>
-WsBuf ws_buf(T*& p, size_t bytes, bool zero = false) {
-  return {reinterpret_cast<void**>(&p), bytes, zero};
 }
 
 // The large-k buffers, allocated together on first use (ensure_lk)
@@ -605,19 +576,11 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
 // query's candidate list overflowed in the previous one.
 int ensure_lk(Workspace& w) {
   if (w.lk_cand) return RAG_OK;
-  // all seven or none: each buffer is allocated into a local and the workspace takes them only
-  // when every allocation succeeded (a partial set would be re-allocated, and leaked, by the
-  // next large-k call)
-  const auto bufs = lk_buffers(w);
-  void* p[bufs.size()] = {};
-  for (size_t i = 0; i < bufs.size(); ++i) {
-    if (hipMalloc(&p[i], bufs[i].bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      for (size_t j = 0; j < i; ++j) (void)hipFree(p[j]);
-      return ragmi::fail(RAG_ENOMEM, "large-k workspace allocation failed");
-    }
+  // all seven or none (a partial set would be re-allocated, and leaked, by the next large-k call)
+  if (ragmi::ws_alloc_all(lk_buffers(w)) != hipSuccess) {
+    (void)hipGetLastError();
+    return ragmi::fail(RAG_ENOMEM, "large-k workspace allocation failed");
   }
-  for (size_t i = 0; i < bufs.size(); ++i) *bufs[i].p = p[i];
   return RAG_OK;
 }
 
@@ -1178,12 +1141,7 @@ int rag_index_create_ex(int dim, int64_t capacity_rows, int device, int storage,
   h->groups = dim > 384 ? kMaxGroups : 1;
   for (auto& w : h->ws) {
     // one hipMalloc per buffer, in the table's order (see ragmi/dist.py on allocation placement)
-    const auto bufs = ws_buffers(h, w);
-    bool ok = true;
-    for (const WsBuf& b : bufs) ok = ok && hipMalloc(b.p, b.bytes) == hipSuccess;
-    for (const WsBuf& b : bufs)
-      if (b.zero) ok = ok && hipMemset(*b.p, 0, b.bytes) == hipSuccess;
-    if (!ok) {
+    if (ragmi::ws_alloc_all(ws_buffers(h, w)) != hipSuccess) {
       rag_index_destroy(h);
       return ragmi::fail(RAG_ENOMEM, "workspace allocation failed");
     }
@@ -1217,10 +1175,8 @@ int rag_index_destroy(rag_index_t* h) {
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
   for (auto& w : h->ws) {
-    for (const WsBuf& b : ws_buffers(h, w))
-      if (*b.p) (void)hipFree(*b.p);
-    for (const WsBuf& b : lk_buffers(w))
-      if (*b.p) (void)hipFree(*b.p);
+    ragmi::ws_free_all(ws_buffers(h, w));
+    ragmi::ws_free_all(lk_buffers(w));
     if (w.ev_in) (void)hipEventDestroy(w.ev_in);
     if (w.ev_out) (void)hipEventDestroy(w.ev_out);
   }
