@@ -1439,6 +1439,35 @@ int rag_index_scatter_rows(rag_index_t* h, const int64_t* rows, int64_t n, const
       const_cast<float*>(in_f32), const_cast<uint32_t*>(in_tags), new_count, stream);
 }
 
+// ---- MMR re-selection (mmr_kernel, scan_kernels.hip) ----
+
+int rag_index_mmr(rag_index_t* h, const float* cand_s, const int64_t* cand_r, int B, int C, int k,
+                  const float* diversity, const int32_t* ncand, float* out_s, int64_t* out_i,
+                  int32_t* out_pos, void* stream) {
+  ragmi::clear_error();
+  static_assert(ragmi::kMmrMaxC == RAG_MMR_MAX_CANDIDATES, "mmr_kernel's LDS lists");
+  if (C < 1 || C > RAG_MMR_MAX_CANDIDATES)
+    return ragmi::fail(RAG_ERANGE, "mmr: C must be in [1, RAG_MMR_MAX_CANDIDATES=1024]");
+  if (k < 1) return ragmi::fail(RAG_ERANGE, "mmr: k must be >= 1");
+  if (B < 0) return ragmi::fail(RAG_EINVAL, "mmr: B must be >= 0");
+  if (!h) return ragmi::fail(RAG_EINVAL, "mmr: index is NULL");
+  if (B > 0 && (!cand_s || !cand_r || !diversity || !out_s || !out_i))
+    return ragmi::fail(RAG_EINVAL, "mmr: a NULL candidate, diversity or output pointer");
+  if (B == 0) return RAG_OK;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  const int rc = with_dim(h->dim, [&](auto d) {
+    ragmi::mmr_kernel<decltype(d)::value><<<dim3((unsigned)B), dim3(ragmi::kMmrBlock), 0, st>>>(
+        h->corpus, h->rows32, h->cap_rows, cand_s, cand_r, C, k, diversity, ncand, out_s, out_i,
+        out_pos);
+    return RAG_OK;
+  });
+  if (rc) return rc;
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
 int rag_merge_topk(const float* in_s, const int64_t* in_i, int n_lists, int B, int k,
                    float* out_s, int64_t* out_i, void* stream) {
   ragmi::clear_error();

@@ -3229,6 +3229,164 @@ __global__ __launch_bounds__(256) void lk_rescore_kernel(const half8* __restrict
   }
 }
 
+// ----------------------------------------------------------------------------------------
+// MMR (maximal marginal relevance): k diverse hits re-selected from a query's exact top-C
+// list (rag_index_mmr). One workgroup of kMmrBlock threads per query walks the
+// greedy steps; the candidate list and the running maxima stay in LDS.
+//   n       = min(ncand[b], C, leading candidates whose row lies in [0, cap_rows))
+//   step 0  selects j = 0
+//   after selecting s: maxsim[j] = max(maxsim[j], sim(s, j)) for every unselected j, where
+//           sim(s, j) is the canonical exact score (exact_scores_wave: fp64 fma per lane chunk,
+//           xor butterfly, one rounding) of stored row r_j against stored row r_s as fp32
+//   step t  selects the unselected j with the largest
+//           val[j] = (double)(1.0f - div) * rel[j] - (double)div * maxsim[j]
+//           (both products exact in fp64, one rounding), ties to the smallest j
+// Per step: the selected row is de-tiled into LDS as row-major fp32; each wave scores 8
+// unselected candidates per memory round trip against it, folds them into maxsim and keeps
+// its best (val, j); the waves' bests meet in LDS. Two barriers per step, no global traffic
+// but the candidate rows. A selected candidate's row slot in LDS is set to -1, which is what
+// exact_scores_wave skips. Output in selection order: global row, rel[j], j; -1 / -inf / -1
+// past the n-th pick.
+// ----------------------------------------------------------------------------------------
+constexpr int kMmrBlock = 512;
+constexpr int kMmrWaves = kMmrBlock / 64;
+constexpr int kMmrMaxC = 1024;    // RAG_MMR_MAX_CANDIDATES
+
+template <int D>
+__global__ __launch_bounds__(kMmrBlock) void mmr_kernel(const half8* __restrict__ corpus,
+                                                        const float* __restrict__ rows32,
+                                                        int64_t cap_rows,
+                                                        const float* __restrict__ cand_s,
+                                                        const int64_t* __restrict__ cand_r,
+                                                        int C, int k,
+                                                        const float* __restrict__ diversity,
+                                                        const int32_t* __restrict__ ncand,
+                                                        float* __restrict__ out_s,
+                                                        int64_t* __restrict__ out_i,
+                                                        int32_t* __restrict__ out_pos) {
+  constexpr int S = steps<D>();
+  constexpr int NC = 8;
+  __shared__ __attribute__((aligned(16))) float sel_row[D];   // the selected row, fp32
+  __shared__ float rel[kMmrMaxC];
+  __shared__ float maxsim[kMmrMaxC];
+  __shared__ int row_of[kMmrMaxC];       // candidate's stored row; -1 once selected / absent
+  __shared__ double wbest_v[kMmrWaves];
+  __shared__ int wbest_j[kMmrWaves];
+  __shared__ int n_sh;
+
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const float* cs = cand_s + (int64_t)b * C;
+  const int64_t* cr = cand_r + (int64_t)b * C;
+  const int limit = max(0, min(C, ncand ? ncand[b] : C));
+  if (tid == 0) n_sh = limit;
+  __syncthreads();
+  for (int j = tid; j < C; j += kMmrBlock) {
+    const int64_t r = j < limit ? cr[j] : -1;
+    const bool ok = r >= 0 && r < cap_rows;
+    row_of[j] = ok ? (int)r : -1;
+    rel[j] = cs[j];
+    maxsim[j] = kNegInf;
+    if (j < limit && !ok) atomicMin(&n_sh, j);   // the list ends at its first absent row
+  }
+  __syncthreads();
+  const int n = n_sh;
+  const int picks = min(k, n);
+  const float div = diversity[b];
+  const float lam = 1.0f - div;
+
+  int s = 0, made = picks;
+  for (int t = 0; t < picks; ++t) {
+    // every thread knows s; its row is still in row_of (cleared after the barrier below)
+    const int srow = row_of[s];
+    if (tid == 0) {
+      out_s[(int64_t)b * k + t] = rel[s];
+      out_i[(int64_t)b * k + t] = cr[s];
+      if (out_pos) out_pos[(int64_t)b * k + t] = s;
+    }
+    if (t + 1 == picks) break;
+    if (rows32) {
+      for (int d = tid; d < D; d += kMmrBlock) sel_row[d] = rows32[(int64_t)srow * D + d];
+    } else {
+      for (int c = tid; c < D / 8; c += kMmrBlock) {
+        const half8 x =
+            corpus[(int64_t)(srow >> 4) * (S * 64) + (c >> 2) * 64 + (c & 3) * 16 + (srow & 15)];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sel_row[8 * c + e] = (float)x[e];
+      }
+    }
+    __syncthreads();                  // sel_row complete; everyone has read row_of[s]
+    if (tid == 0) row_of[s] = -1;     // seen past this step's last barrier; until then j == s
+                                      // is skipped by index below
+    double best_v = -__builtin_inf();
+    int best_j = 0x7fffffff;
+    for (int j0 = wid * NC; j0 < n; j0 += kMmrWaves * NC) {
+      int rows[NC];
+      bool any = false;
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        rows[i] = j0 + i < n && j0 + i != s ? row_of[j0 + i] : -1;
+        any |= rows[i] >= 0;
+      }
+      if (!any) continue;             // wave-uniform: row_of is read at wave-uniform indices
+      float sc[NC];
+      exact_scores_wave<D, NC>(corpus, rows, sel_row, lane, sc, rows32);
+      float mine = kNegInf;
+      int my_row = -1;
+#pragma unroll
+      for (int i = 0; i < NC; ++i)
+        if (lane == i) {
+          mine = sc[i];
+          my_row = rows[i];
+        }
+      if (lane < NC && my_row >= 0) {
+        const int j = j0 + lane;
+        const float m = fmaxf(maxsim[j], mine);
+        maxsim[j] = m;
+        const double v = (double)lam * (double)rel[j] - (double)div * (double)m;
+        if (v > best_v) {             // a lane meets its j in ascending order
+          best_v = v;
+          best_j = j;
+        }
+      }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      const double ov = __shfl_xor(best_v, d, 64);
+      const int oj = __shfl_xor(best_j, d, 64);
+      if (ov > best_v || (ov == best_v && oj < best_j)) {
+        best_v = ov;
+        best_j = oj;
+      }
+    }
+    if (lane == 0) {
+      wbest_v[wid] = best_v;
+      wbest_j[wid] = best_j;
+    }
+    __syncthreads();
+    best_v = wbest_v[0];
+    best_j = wbest_j[0];
+#pragma unroll
+    for (int w = 1; w < kMmrWaves; ++w) {
+      const double ov = wbest_v[w];
+      const int oj = wbest_j[w];
+      if (ov > best_v || (ov == best_v && oj < best_j)) {
+        best_v = ov;
+        best_j = oj;
+      }
+    }
+    if (best_j >= n) {                // only if no val compared (NaN scores handed in): stop
+      made = t + 1;
+      break;
+    }
+    s = best_j;
+  }
+  for (int t = made + tid; t < k; t += kMmrBlock) {
+    out_s[(int64_t)b * k + t] = kNegInf;
+    out_i[(int64_t)b * k + t] = -1;
+    if (out_pos) out_pos[(int64_t)b * k + t] = -1;
+  }
+}
+
 template <int D>
 __global__ __launch_bounds__(256) void lk_final_kernel(const half8* __restrict__ corpus,
                                                        const float* __restrict__ qn, int k,

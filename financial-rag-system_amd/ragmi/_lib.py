@@ -119,6 +119,8 @@ INDEX_API = {
                                              c_vp]),
     "rag_index_scatter_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp,
                                               ctypes.c_int64, c_vp]),
+    "rag_index_mmr": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rag_merge_topk": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       c_vp, c_vp, c_vp]),
     "rag_merge_topk_packed": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

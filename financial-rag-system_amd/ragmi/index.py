@@ -21,6 +21,7 @@ MAX_K = 32          # RAG_MAX_K in include/ragmi.h: the scan's certified top-k p
 MAX_K_LARGE = 4096  # RAG_MAX_K_LARGE: k in (32, 4096] takes the exact large-k pass; larger k
                     # the full exact pass (and the packed exchange form stops here)
 QUERY_TILE = 32     # RAG_QUERY_TILE
+MMR_MAX_CANDIDATES = 1024   # RAG_MMR_MAX_CANDIDATES: the longest list rag_index_mmr re-selects from
 STORAGE = {"fp16": 0, "fp32": 1}   # RAG_STORE_FP16 / RAG_STORE_FP32
 CREATE_DIAGNOSTIC = 0x100          # RAG_CREATE_DIAGNOSTIC: honour the RAGMI_* A/B knobs
 
@@ -36,6 +37,18 @@ def _as_dev(x, dtype, device) -> torch.Tensor:
         t = torch.from_numpy(np.ascontiguousarray(np.asarray(x))).to(dtype=dtype)
         t = t.to(device=device, non_blocking=False)
     return t.contiguous()
+
+
+def per_query(x, B: int, dtype, what: str) -> np.ndarray:
+    """A scalar or one value per query -> a contiguous [B] host array of `dtype`."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    a = np.asarray(x)
+    if a.ndim == 0:
+        a = np.full((B,), a)
+    if a.shape != (B,):
+        raise ValueError(f"{what} must be a scalar or one value per query")
+    return np.ascontiguousarray(a.astype(dtype))
 
 
 def plan_removal(count: int, rows):
@@ -190,6 +203,58 @@ class FlatIndex:
         # staging tensors (q, f) go back to torch's stream-ordered caching allocator: any
         # reuse is enqueued on this same stream after our kernels, so no sync is needed.
         return out_s, out_i
+
+    # ---------------------------------------------------------------- MMR
+    def mmr(self, cand_scores, cand_rows, k: int, diversity, ncand=None,
+            with_pos: bool = False):
+        """Maximal marginal relevance over exact candidate lists (rag_index_mmr): k diverse
+        hits re-selected from each query's top-C list `cand_scores` fp32 [B, C] / `cand_rows`
+        int64 [B, C] (rows of this index, -1 = none; search(k=C)'s result). `diversity`: a
+        scalar or one value per query in [0, 1] (0: the plain top-k, 1: similarity to the
+        picks alone); `ncand`: None, a scalar or one value per query — only the first ncand[b]
+        candidates of query b take part. Returns (scores fp32 [B, k], rows int64 [B, k]) in
+        selection order, the score being the candidate's score to the query, -inf / -1 past
+        the last pick; with_pos=True adds each pick's position in its list (int32 [B, k]).
+        Enqueued on the current stream."""
+        s = _as_dev(cand_scores, torch.float32, self.device)
+        r = _as_dev(cand_rows, torch.int64, self.device)
+        if s.dim() != 2 or s.shape != r.shape:
+            raise ValueError("cand_scores and cand_rows must both be [B, C]")
+        B, C = s.shape
+        if not 1 <= C <= MMR_MAX_CANDIDATES:
+            raise ValueError(f"C must be in [1, {MMR_MAX_CANDIDATES}] candidates")
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        div = per_query(diversity, B, np.float32, "diversity")
+        if B and not ((div >= 0) & (div <= 1)).all():        # also refuses NaN
+            raise ValueError("diversity must lie in [0, 1]")
+        d = torch.from_numpy(div).to(self.device)
+        n = None
+        if ncand is not None:
+            n = torch.from_numpy(per_query(ncand, B, np.int32, "ncand")).to(self.device)
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        pos = torch.empty((B, k), dtype=torch.int32, device=self.device) if with_pos else None
+        check(self._L.rag_index_mmr(self._h, s.data_ptr(), r.data_ptr(), B, C, int(k),
+                                    d.data_ptr(), n.data_ptr() if n is not None else None,
+                                    out_s.data_ptr(), out_i.data_ptr(),
+                                    pos.data_ptr() if pos is not None else None,
+                                    _stream_ptr(self.device)))
+        return (out_s, out_i, pos) if with_pos else (out_s, out_i)
+
+    def search_mmr(self, queries, k: int, diversity, candidates, filters=None):
+        """search(k=C) followed by mmr, C = the largest of `candidates` (a scalar or one value
+        per query: how many nearest candidates each query re-selects from), all on the device
+        and the current stream. Returns (scores [B, k], rows [B, k]) as mmr does."""
+        q, B, f = self._search_args(queries, k, filters)
+        nc = per_query(candidates, B, np.int32, "candidates")
+        if B and int(nc.min()) < 1:
+            raise ValueError("candidates must be >= 1")
+        C = int(nc.max()) if B else 1
+        if C > MMR_MAX_CANDIDATES:
+            raise ValueError(f"at most {MMR_MAX_CANDIDATES} MMR candidates per query")
+        s, r = self.search(q, C, f)
+        return self.mmr(s, r, k, diversity, None if B and (nc == C).all() else nc)
 
     # ---------------------------------------------------------------- row removal
     def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None,

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import qdrant_models as models
-from .index import MAX_K, FlatIndex
+from .index import MAX_K, MMR_MAX_CANDIDATES, FlatIndex
 from .shardset import ShardSet, parse_devices
 
 DEFAULT_TAG_FIELDS = ("ticker", "document_type")
@@ -391,40 +391,89 @@ class Collection:
             out = [[] for _ in range(B)]
             if not live or self.index.count == 0:
                 return out
-            q = queries if isinstance(queries, torch.Tensor) else np.asarray(queries, np.float32)
-            q = q[live] if len(live) != B else q
-            fl = np.asarray([filters[i] for i in live], dtype=np.uint32).reshape(-1, 2)
-            use = fl if fl.any() else None
-            sharded = isinstance(self.index, ShardSet)
-            if sharded:
-                # a shard that left a query unanswered hands the merge an all -1 list, which
-                # the merged top-k does not show: the set reads its per-shard flags and
-                # re-answers those queries itself (ShardSet.search, rescue)
-                before = self.index.rescued
-                s, ids = self.index.search(q, k, filters=use, rescue=True)
-                self.rescued += self.index.rescued - before
-            else:
-                s, ids = self.index.search(q, k, filters=use)
+            q, use = self._live_queries(queries, filters, live)
+            s, ids = self._exact_lists(q, k, use)
             s = s.cpu().numpy()
             ids = ids.cpu().numpy()
-            if not sharded and (ids < 0).any():
-                # a -1 is padding (fewer matching points than k) unless the pass left the
-                # query unanswered (tier 3: more than 16384 rows tied within the error band
-                # of its k-th best on the large-k pass). Only then, re-run those queries on
-                # the full exact pass: an unanswered query must never read as "no documents"
-                # (ADVICE r5).
-                n_un = self.index.unanswered()
-                if n_un > self._unanswered:
-                    redo = np.nonzero((ids < 0).any(axis=1))[0].tolist()
-                    s2, i2 = self.index.search(q[redo], k, filters=use[redo] if use is not None
-                                               else None, full=True)
-                    s[redo] = s2.cpu().numpy()
-                    ids[redo] = i2.cpu().numpy()
-                    self.rescued += len(redo)
-                self._unanswered = n_un
             for j, i in enumerate(live):
                 out[i] = [(int(r), float(sc)) for r, sc in zip(ids[j], s[j]) if r >= 0]
             return out
+
+    @staticmethod
+    def _live_queries(queries, filters: list, live: list):
+        """The queries of the `live` requests and their compiled filters as the index takes
+        them ([n, 2] uint32, or None when no request filters)."""
+        q = queries if isinstance(queries, torch.Tensor) else np.asarray(queries, np.float32)
+        q = q[live] if len(live) != len(filters) else q
+        fl = np.asarray([filters[i] for i in live], dtype=np.uint32).reshape(-1, 2)
+        return q, (fl if fl.any() else None)
+
+    def _exact_lists(self, q, k: int, use):
+        """The exact top-k lists (scores, rows) of queries `q`, as the index's tensors, with
+        every query a large-k pass left unanswered re-answered on the full exact pass. What
+        search reports and what the MMR path re-selects from. Called under the lock."""
+        if isinstance(self.index, ShardSet):
+            # a shard that left a query unanswered hands the merge an all -1 list, which
+            # the merged top-k does not show: the set reads its per-shard flags and
+            # re-answers those queries itself (ShardSet.search, rescue)
+            before = self.index.rescued
+            s, ids = self.index.search(q, k, filters=use, rescue=True)
+            self.rescued += self.index.rescued - before
+            return s, ids
+        s, ids = self.index.search(q, k, filters=use)
+        short = (ids < 0).any(dim=1)
+        if bool(short.any()):
+            # a -1 is padding (fewer matching points than k) unless the pass left the
+            # query unanswered (tier 3: more than 16384 rows tied within the error band
+            # of its k-th best on the large-k pass). Only then, re-run those queries on
+            # the full exact pass: an unanswered query must never read as "no documents"
+            # (ADVICE r5).
+            n_un = self.index.unanswered()
+            if n_un > self._unanswered:
+                redo = torch.nonzero(short).reshape(-1).tolist()
+                s2, i2 = self.index.search(q[redo], k, filters=use[redo] if use is not None
+                                           else None, full=True)
+                s[redo] = s2
+                ids[redo] = i2
+                self.rescued += len(redo)
+            self._unanswered = n_un
+        return s, ids
+
+    def search_mmr(self, queries, limits, filters: list, diversity, candidates):
+        """search with MMR re-selection, per request b: limits[b] hits chosen at diversity[b]
+        from its candidates[b] nearest points (clamped to the collection's count) — one
+        search at C = the largest of them, one MMR launch with per-query candidate counts.
+        A request at diversity 0 with candidates = its limit is the plain search. Returns
+        per request [(row, score)] in selection order."""
+        with self.lock:
+            B = len(filters)
+            out = [[] for _ in range(B)]
+            count = self.index.count
+            live = [i for i, f in enumerate(filters) if f is not None and limits[i] >= 1]
+            if not live or count == 0:
+                return out
+            ncand = np.minimum(np.asarray([candidates[i] for i in live], np.int64), count)
+            ncand = np.maximum(ncand, 1).astype(np.int32)
+            lim = [int(limits[i]) for i in live]
+            C = int(ncand.max())
+            k = min(max(lim), C)
+            q, use = self._live_queries(queries, filters, live)
+            s, ids = self._exact_lists(q, C, use)
+            s, ids = self.index.mmr(s, ids, k, np.asarray([diversity[i] for i in live],
+                                                          np.float32), ncand)
+            s = s.cpu().numpy()
+            ids = ids.cpu().numpy()
+            for j, i in enumerate(live):
+                out[i] = [(int(r), float(sc)) for r, sc in zip(ids[j], s[j]) if r >= 0][:lim[j]]
+            return out
+
+    def search_points_mmr(self, queries, limits, filters: list, diversity, candidates,
+                          with_vectors=False):
+        """search_mmr with every hit resolved to its ScoredPoint under the same hold of the
+        lock (see search_points)."""
+        with self.lock:
+            return [[self.point(r, s, True, with_vectors) for r, s in h]
+                    for h in self.search_mmr(queries, limits, filters, diversity, candidates)]
 
     def point(self, row: int, score: float, with_payload=True, with_vectors=False):
         payload = self.payloads[row] if with_payload else None
@@ -434,6 +483,38 @@ class Collection:
                    self.index.export_rows(row, 1)[0].view(np.float16).astype(np.float32)).tolist()
         return models.ScoredPoint(id=self.row_ids[row], version=self.versions[row],
                                   score=score, payload=payload, vector=vec)
+
+
+MMR_DIVERSITY = 0.5          # Mmr(diversity=None)
+MMR_CANDIDATES = 100         # Mmr(candidates_limit=None): max(limit, this)
+
+
+def nearest_of(query):
+    """A query argument -> (vector, Mmr or None): a NearestQuery is unwrapped, anything else is
+    the vector itself."""
+    if isinstance(query, models.NearestQuery):
+        return query.nearest, query.mmr
+    return query, None
+
+
+def mmr_params(mmr: models.Mmr, limit) -> tuple[float, int]:
+    """(diversity, candidates) of an MMR request with the defaults filled in, or ValueError:
+    the limit must be an int, diversity must lie in [0, 1], and the candidates (given, or the
+    default max(limit, 100)) may not exceed RAG_MMR_MAX_CANDIDATES."""
+    if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)):
+        raise ValueError("an MMR query needs an int limit")
+    div = MMR_DIVERSITY if mmr.diversity is None else float(mmr.diversity)
+    if not 0.0 <= div <= 1.0:                                   # NaN fails too
+        raise ValueError(f"Mmr.diversity must lie in [0, 1], got {mmr.diversity!r}")
+    cand = mmr.candidates_limit
+    if cand is None:
+        cand = max(int(limit), MMR_CANDIDATES)
+    elif isinstance(cand, bool) or not isinstance(cand, (int, np.integer)) or cand < 1:
+        raise ValueError("Mmr.candidates_limit must be an int >= 1")
+    if cand > MMR_MAX_CANDIDATES:
+        raise ValueError(f"MMR re-selects from at most {MMR_MAX_CANDIDATES} candidates "
+                         f"(candidates_limit, or a limit above it): got {int(cand)}")
+    return div, int(cand)
 
 
 def _payloads(points: list, with_payload) -> list:
@@ -577,8 +658,15 @@ class QdrantClient:
                      query_filter: models.Filter | None = None, with_payload=True,
                      with_vectors=False, **kwargs) -> models.QueryResponse:
         col = self._col(collection_name)
+        query, mmr = nearest_of(query)
         flt = col.compile_filter(query_filter)
-        if self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
+        if mmr is not None:
+            # an MMR request never rides the coalescer: its candidate search is its own pass
+            div, cand = mmr_params(mmr, limit)
+            q = query if isinstance(query, torch.Tensor) else np.asarray(query, dtype=np.float32)
+            pts = col.search_points_mmr(q.reshape(1, -1), [int(limit)], [flt], [div], [cand],
+                                        with_vectors)[0]
+        elif self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
             q = (query.detach().float().cpu().numpy() if isinstance(query, torch.Tensor)
                  else np.asarray(query, dtype=np.float32))
             if q.shape != (col.dim,):
@@ -594,16 +682,40 @@ class QdrantClient:
 
     def query_batch_points(self, collection_name: str, requests: list,
                            **kwargs) -> list[models.QueryResponse]:
-        """One GPU scan for the whole batch (per-query filters ride along in the kernel)."""
+        """One GPU scan for the whole batch (per-query filters ride along in the kernel). With
+        MMR requests in it (QueryRequest.query = NearestQuery(..., mmr=Mmr(...))): one search
+        at the batch's largest candidate count and one MMR launch, the plain requests riding
+        at diversity 0 with their own limit as candidate count — unless a plain limit exceeds
+        RAG_MMR_MAX_CANDIDATES, in which case the plain requests are searched on their own."""
         col = self._col(collection_name)
         if not requests:
             return []
-        limit = max(int(r.limit) for r in requests)
-        qs = [r.query for r in requests]
+        unwrapped = [nearest_of(r.query) for r in requests]
+        qs = [v for v, _ in unwrapped]
         Q = torch.stack([x if isinstance(x, torch.Tensor) else
                          torch.as_tensor(np.asarray(x, np.float32)) for x in qs]) \
             if any(isinstance(x, torch.Tensor) for x in qs) else np.asarray(qs, np.float32)
-        hits = col.search_points(Q, limit, [col.compile_filter(r.filter) for r in requests])
+        filters = [col.compile_filter(r.filter) for r in requests]
+        if all(m is None for _, m in unwrapped):
+            hits = col.search_points(Q, max(int(r.limit) for r in requests), filters)
+        else:
+            par = [mmr_params(m, r.limit) if m is not None else (0.0, max(int(r.limit), 1))
+                   for (_, m), r in zip(unwrapped, requests)]
+            limits = [int(r.limit) for r in requests]
+            if max(c for _, c in par) <= MMR_MAX_CANDIDATES:
+                hits = col.search_points_mmr(Q, limits, filters, [d for d, _ in par],
+                                             [c for _, c in par])
+            else:
+                plain = [i for i, (_, m) in enumerate(unwrapped) if m is None]
+                rest = [i for i, (_, m) in enumerate(unwrapped) if m is not None]
+                hits = [None] * len(requests)
+                for i, h in zip(plain, col.search_points(
+                        Q[plain], max(limits[i] for i in plain), [filters[i] for i in plain])):
+                    hits[i] = h
+                for i, h in zip(rest, col.search_points_mmr(
+                        Q[rest], [limits[i] for i in rest], [filters[i] for i in rest],
+                        [par[i][0] for i in rest], [par[i][1] for i in rest])):
+                    hits[i] = h
         return [models.QueryResponse(points=_payloads(h[:int(r.limit)], r.with_payload))
                 for r, h in zip(requests, hits)]
 

@@ -144,8 +144,26 @@ class CountResult:
 
 
 @dataclass
+class Mmr:
+    """Maximal marginal relevance parameters of a NearestQuery (Qdrant's query API). None
+    fields take the defaults of QdrantClient.query_points: diversity 0.5, candidates_limit
+    max(limit, 100)."""
+    diversity: Optional[float] = None
+    candidates_limit: Optional[int] = None
+
+
+@dataclass
+class NearestQuery:
+    """query_points(query=NearestQuery(nearest=vector, mmr=Mmr(...))): the nearest points to
+    `nearest`, re-selected for diversity when `mmr` is set; without it, the plain query."""
+    nearest: Any
+    mmr: Optional[Mmr] = None
+
+
+@dataclass
 class QueryRequest:
-    """Batched query entry for query_batch_points (one per request of a micro-batch)."""
+    """Batched query entry for query_batch_points (one per request of a micro-batch); `query`
+    is a vector or a NearestQuery."""
     query: Any
     filter: Optional[Filter] = None
     limit: int = 10

@@ -123,26 +123,43 @@ def _filter(ticker, document_type=None):
     return models.Filter(must=must)
 
 
-def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEVE_LIMIT):
+def _query(vector, diversity, candidates):
+    """The `query` argument of a retrieval: the vector itself (the reference's call), or with
+    `diversity` / `candidates` set, a NearestQuery that re-selects the hits by MMR."""
+    if diversity is None and candidates is None:
+        return vector
+    return models.NearestQuery(nearest=vector,
+                               mmr=models.Mmr(diversity=diversity, candidates_limit=candidates))
+
+
+def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEVE_LIMIT, *,
+                         diversity=None, candidates=None):
+    """diversity / candidates (keyword-only, not in the reference): MMR re-selection of the
+    `limit` hits from the `candidates` nearest (Mmr's defaults where one is None), so
+    near-duplicate chunks do not fill the list; both None is the reference's call."""
     if _testing():
         return type("obj", (object,), {"points": []})
     # the reference's swallow-to-empty (main.py:232-239) unchanged: query_points answers any
     # limit exactly (large limits on the full exact pass), so an exception here is a real
     # failure, as it is for the reference's Qdrant call
     try:
-        return get_qdrant().query_points(collection_name=COLLECTION_NAME, query=query_vector,
+        return get_qdrant().query_points(collection_name=COLLECTION_NAME,
+                                         query=_query(query_vector, diversity, candidates),
                                          limit=limit,
                                          query_filter=_filter(ticker, document_type))
     except Exception:
         return type("obj", (object,), {"points": []})
 
 
-def retrieve_batch(query_vectors, tickers, document_types=None, limit=RETRIEVE_LIMIT):
-    """One GPU scan for a whole micro-batch (main2.py:281-295 + 228), per-request filters."""
+def retrieve_batch(query_vectors, tickers, document_types=None, limit=RETRIEVE_LIMIT, *,
+                   diversity=None, candidates=None):
+    """One GPU scan for a whole micro-batch (main2.py:281-295 + 228), per-request filters;
+    diversity / candidates as in retrieve_from_qdrant, for every request of the batch."""
     if _testing():
         return [type("obj", (object,), {"points": []}) for _ in tickers]
     document_types = document_types or [None] * len(tickers)
-    reqs = [models.QueryRequest(query=v, limit=limit, filter=_filter(t, d))
+    reqs = [models.QueryRequest(query=_query(v, diversity, candidates), limit=limit,
+                                filter=_filter(t, d))
             for v, t, d in zip(query_vectors, tickers, document_types)]
     return get_qdrant().query_batch_points(COLLECTION_NAME, reqs)
 

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import threading
 
 import numpy as np
 import torch
@@ -175,6 +176,9 @@ class ShardSet:
         self.storage = storage
         self.shards: list = []
         self._h = None
+        self._scratch = None              # mmr's scratch index on the merge device
+        self._scratch_lock = threading.Lock()
+        self._scratch_done = None         # event behind the last launch that read the scratch
         per = -(-int(capacity) // self.n)
         try:
             for d in devs:
@@ -199,6 +203,9 @@ class ShardSet:
         self._h = None
         for s in getattr(self, "shards", []):
             s.close()
+        if getattr(self, "_scratch", None) is not None:
+            self._scratch.close()
+            self._scratch = None
 
     def __del__(self):
         try:
@@ -345,6 +352,68 @@ class ShardSet:
                 out_i[sel] = i2
                 self.rescued += int(redo.sum())
         return out_s, out_i
+
+    # ---------------------------------------------------------------- MMR
+    def _mmr_scratch(self, slots: int):
+        """The scratch FlatIndex on the merge device that mmr copies the candidates' rows into
+        (same dim and storage as the shards), created on first use and grown on demand."""
+        from .index import FlatIndex
+        if self._scratch is None:
+            self._scratch = FlatIndex(self.dim, slots, self.device, self.storage)
+        elif self._scratch.capacity < slots:
+            self._scratch.reserve(slots)
+        return self._scratch
+
+    @_keeps_device
+    def mmr(self, cand_scores, cand_rows, k: int, diversity, ncand=None,
+            with_pos: bool = False):
+        """FlatIndex.mmr in global rows, composed of existing primitives: every shard gathers
+        its own candidates' stored rows (gather_rows skips the -1 it is given for the others),
+        the packed rows are copied to the merge device and scattered, bit for bit, into a
+        scratch FlatIndex at slot b * C + j; rag_index_mmr runs there over the slots and its
+        positions are mapped back to global rows. The rows travel unchanged, so the result is
+        FlatIndex.mmr's on the same rows bit for bit. On the merge device's current stream."""
+        from .index import _as_dev
+        s = _as_dev(cand_scores, torch.float32, self.device)
+        g = _as_dev(cand_rows, torch.int64, self.device)
+        if s.dim() != 2 or s.shape != g.shape:
+            raise ValueError("cand_scores and cand_rows must both be [B, C]")
+        B, C = g.shape
+        flat = g.reshape(-1)
+        valid = (flat >= 0) & (flat < self.capacity)
+        slot = torch.arange(B * C, dtype=torch.int64, device=self.device)
+        with self._scratch_lock:
+            scratch = self._mmr_scratch(max(B * C, 1))
+            stream = torch.cuda.current_stream(self.device)
+            if self._scratch_done is not None:
+                # the previous call's launch may still read the slots, on another stream
+                stream.wait_event(self._scratch_done)
+            for sh, shard in enumerate(self.shards):
+                own = valid & (shard_of(flat, self.n) == sh)
+                local = torch.where(own, local_of(flat, self.n), -1)
+                f16, f32, tags = shard.gather_rows(local.to(shard.device))
+                scratch.scatter_rows(torch.where(own, slot, -1), f16.to(self.device),
+                                     f32.to(self.device) if f32 is not None else None,
+                                     tags.to(self.device), B * C)
+            out_s, _, pos = scratch.mmr(s, torch.where(valid, slot, -1).reshape(B, C), k,
+                                        diversity, ncand, with_pos=True)
+            self._scratch_done = stream.record_event()
+        picked = torch.gather(g, 1, pos.clamp(min=0).to(torch.int64))
+        rows = torch.where(pos >= 0, picked, -1)
+        return (out_s, rows, pos) if with_pos else (out_s, rows)
+
+    def search_mmr(self, queries, k: int, diversity, candidates, filters=None):
+        """FlatIndex.search_mmr over the set: search at k = C (global rows), then mmr."""
+        from .index import MMR_MAX_CANDIDATES, per_query
+        q, B, f = self.shards[0]._search_args(queries, k, filters)
+        nc = per_query(candidates, B, np.int32, "candidates")
+        if B and int(nc.min()) < 1:
+            raise ValueError("candidates must be >= 1")
+        C = int(nc.max()) if B else 1
+        if C > MMR_MAX_CANDIDATES:
+            raise ValueError(f"at most {MMR_MAX_CANDIDATES} MMR candidates per query")
+        s, g = self.search(q, C, f)
+        return self.mmr(s, g, k, diversity, None if B and (nc == C).all() else nc)
 
     @_keeps_device
     def unanswered(self) -> int:

@@ -220,6 +220,31 @@ int rag_index_scatter_rows(rag_index_t* index, const int64_t* rows_dev, int64_t 
                            const uint16_t* in_f16_dev, const float* in_f32_dev,
                            const uint32_t* in_tags_dev, int64_t new_count, void* stream);
 
+/* MMR (maximal marginal relevance): re-select k diverse hits from each query's exact top-C
+ * candidate list (rag_index_search at k = C: cand_scores_dev fp32 [B][C], cand_rows_dev int64
+ * [B][C] rows of THIS index, -1 = none). The candidates of query b are the first n_b entries,
+ * n_b = min(ncand_dev[b] (NULL = C), the leading entries whose row lies in [0, capacity)): a
+ * row outside that range counts as absent, ends the list and is never dereferenced; rows are
+ * read at any slot below capacity, as rag_index_gather_rows reads them. Step 0 selects
+ * candidate 0. After selecting s, maxsim[j] = max(maxsim[j], sim(s, j)) in fp32 for every
+ * unselected j (from -inf), sim(s, j) being the canonical exact score of stored row r_j against
+ * the stored row r_s as an fp32 vector (fp16 storage: the halves widened) — the arithmetic of
+ * every exact score here, fp64 fma in the canonical order and one rounding to fp32. Step t >= 1
+ * selects the unselected j with the largest
+ *     val[j] = (double)(1.0f - div) * (double)score[j] - (double)div * (double)maxsim[j],
+ * div = diversity_dev[b] (fp32, in [0, 1]: the caller's check), ties to the smallest j. It
+ * stops after k picks or n_b. Outputs in selection order, [B][k]: the candidate's score,
+ * its row, and (out_pos_dev, may be NULL) its position j in the list; -inf / -1 / -1 past the
+ * last pick. Diversity 0 returns the first k candidates unchanged; the first k' picks of a run
+ * at k are the run at k'. 1 <= C <= RAG_MMR_MAX_CANDIDATES, k >= 1, B >= 0; argument errors
+ * are refused on the host before any HIP call. Asynchronous on `stream`. Qdrant's counterpart
+ * is NearestQuery(nearest, mmr=Mmr(diversity, candidates_limit)); the reference never asks for
+ * it, and parity with Qdrant's own MMR arithmetic is unpinned. */
+#define RAG_MMR_MAX_CANDIDATES 1024
+int rag_index_mmr(rag_index_t* index, const float* cand_scores_dev, const int64_t* cand_rows_dev,
+                  int B, int C, int k, const float* diversity_dev, const int32_t* ncand_dev,
+                  float* out_scores_dev, int64_t* out_ids_dev, int32_t* out_pos_dev, void* stream);
+
 /* Merge n_lists per-shard result lists (each [B][k] sorted by (score desc, id asc), device;
  * laid out [n_lists][B][k]; padding: id -1) into the global top-k [B][k] (device) by (score
  * desc, id asc), padding -inf / -1 past the valid entries. Any k >= 1 (k > RAG_MAX_K_LARGE:
