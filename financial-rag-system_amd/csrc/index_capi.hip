@@ -1468,6 +1468,56 @@ int rag_index_mmr(rag_index_t* h, const float* cand_s, const int64_t* cand_r, in
   return RAG_OK;
 }
 
+// ---- grouped search: tag gather and group selection (rows_kernels.hip) ----
+
+int rag_index_gather_tags(rag_index_t* h, const int64_t* rows, int64_t n, uint32_t* out_tags,
+                          void* stream) {
+  ragmi::clear_error();
+  if (n < 0) return ragmi::fail(RAG_EINVAL, "gather_tags: n must be >= 0");
+  if (n > 0 && (!rows || !out_tags))
+    return ragmi::fail(RAG_EINVAL, "gather_tags: a NULL rows or output pointer");
+  if (!h) return ragmi::fail(RAG_EINVAL, "gather_tags: index is NULL");
+  if (n == 0) return RAG_OK;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  const dim3 grid((unsigned)((n + ragmi::kTagBlock - 1) / ragmi::kTagBlock));
+  ragmi::gather_tags_kernel<<<grid, dim3(ragmi::kTagBlock), 0, st>>>(h->tags, rows, n, h->cap_rows,
+                                                                     out_tags);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+int rag_group_select(const float* cand_s, const int64_t* cand_r, const uint32_t* cand_t,
+                     const int32_t* ncand, int B, int C, uint32_t key_mask, int G, int S,
+                     uint32_t* out_keys, int32_t* out_fill, float* out_s, int64_t* out_r,
+                     int32_t* out_pos, int32_t* out_count, void* stream) {
+  ragmi::clear_error();
+  static_assert(ragmi::kGrpMaxC == RAG_GROUPS_MAX_CANDIDATES && ragmi::kGrpMaxG == RAG_GROUPS_MAX &&
+                    ragmi::kGrpMaxCells == RAG_GROUPS_MAX_CELLS &&
+                    RAG_GROUPS_MAX_CANDIDATES == RAG_MAX_K_LARGE,
+                "group_select_kernel's LDS arrays");
+  if (C < 1 || C > RAG_GROUPS_MAX_CANDIDATES)
+    return ragmi::fail(RAG_ERANGE, "group_select: C must be in [1, RAG_GROUPS_MAX_CANDIDATES=4096]");
+  if (G < 1 || G > RAG_GROUPS_MAX)
+    return ragmi::fail(RAG_ERANGE, "group_select: G must be in [1, RAG_GROUPS_MAX=1024]");
+  if (S < 1) return ragmi::fail(RAG_ERANGE, "group_select: S must be >= 1");
+  if ((int64_t)G * S > RAG_GROUPS_MAX_CELLS)
+    return ragmi::fail(RAG_ERANGE, "group_select: G * S must be <= RAG_GROUPS_MAX_CELLS=4096");
+  if (key_mask == 0) return ragmi::fail(RAG_EINVAL, "group_select: key_mask is 0");
+  if (B < 0) return ragmi::fail(RAG_EINVAL, "group_select: B must be >= 0");
+  if (B > 0 && (!cand_s || !cand_r || !cand_t || !out_keys || !out_fill || !out_s || !out_r ||
+                !out_count))
+    return ragmi::fail(RAG_EINVAL, "group_select: a NULL candidate or output pointer");
+  if (B == 0) return RAG_OK;
+  ragmi::group_select_kernel<<<dim3((unsigned)B), dim3(ragmi::kGrpBlock), 0,
+                               static_cast<hipStream_t>(stream)>>>(
+      cand_s, cand_r, cand_t, ncand, C, key_mask, G, S, out_keys, out_fill, out_s, out_r, out_pos,
+      out_count);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
 int rag_merge_topk(const float* in_s, const int64_t* in_i, int n_lists, int B, int k,
                    float* out_s, int64_t* out_i, void* stream) {
   ragmi::clear_error();

@@ -121,6 +121,10 @@ INDEX_API = {
                                               ctypes.c_int64, c_vp]),
     "rag_index_mmr": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rag_index_gather_tags": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
+    "rag_group_select": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_uint32, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rag_merge_topk": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       c_vp, c_vp, c_vp]),
     "rag_merge_topk_packed": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -10,6 +10,7 @@ torch tensors (used in place).
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -22,6 +23,9 @@ MAX_K_LARGE = 4096  # RAG_MAX_K_LARGE: k in (32, 4096] takes the exact large-k p
                     # the full exact pass (and the packed exchange form stops here)
 QUERY_TILE = 32     # RAG_QUERY_TILE
 MMR_MAX_CANDIDATES = 1024   # RAG_MMR_MAX_CANDIDATES: the longest list rag_index_mmr re-selects from
+GROUPS_MAX_CANDIDATES = 4096   # RAG_GROUPS_MAX_CANDIDATES: the longest list rag_group_select walks
+GROUPS_MAX = 1024              # RAG_GROUPS_MAX: groups per query
+GROUPS_MAX_CELLS = 4096        # RAG_GROUPS_MAX_CELLS: groups x hits per group
 STORAGE = {"fp16": 0, "fp32": 1}   # RAG_STORE_FP16 / RAG_STORE_FP32
 CREATE_DIAGNOSTIC = 0x100          # RAG_CREATE_DIAGNOSTIC: honour the RAGMI_* A/B knobs
 
@@ -255,6 +259,27 @@ class FlatIndex:
             raise ValueError(f"at most {MMR_MAX_CANDIDATES} MMR candidates per query")
         s, r = self.search(q, C, f)
         return self.mmr(s, r, k, diversity, None if B and (nc == C).all() else nc)
+
+    # ---------------------------------------------------------------- grouped search
+    def gather_tags(self, rows) -> torch.Tensor:
+        """The tags of `rows` (int64, any shape; rag_index_gather_tags): an int32 tensor of the
+        same shape holding the uint32 tag bits, 0 for a row outside [0, capacity) — such a row
+        is never dereferenced. Enqueued on the current stream."""
+        r = _as_dev(rows, torch.int64, self.device)
+        out = torch.empty(r.shape, dtype=torch.int32, device=self.device)
+        if r.numel():
+            check(self._L.rag_index_gather_tags(self._h, r.data_ptr(), r.numel(), out.data_ptr(),
+                                                _stream_ptr(self.device)))
+        return out
+
+    def group_select(self, cand_scores, cand_rows, key_mask: int, G: int, S: int, ncand=None,
+                     with_pos: bool = False) -> "GroupSelection":
+        """The grouped walk over exact candidate lists (search(k=C)'s result; rows of this
+        index): gather_tags of the rows, then rag_group_select, both on the current stream.
+        See group_select_tags for the result."""
+        r = _as_dev(cand_rows, torch.int64, self.device)
+        return group_select_tags(_as_dev(cand_scores, torch.float32, self.device), r,
+                                 self.gather_tags(r), key_mask, G, S, ncand, with_pos)
 
     # ---------------------------------------------------------------- row removal
     def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None,
@@ -531,6 +556,60 @@ def busy_union_ms(start_ms, end_ms) -> float:
     if cur_b is not None:
         busy += cur_b - cur_a
     return busy
+
+
+class GroupSelection(NamedTuple):
+    """rag_group_select's outputs (cuda tensors): keys int32 [B, G] holding the uint32 key bits
+    in opening order (0 past the last group), fill int32 [B, G], scores fp32 [B, G, S] (-inf
+    padding), rows int64 [B, G, S] (-1 padding), count int32 [B, 2] = (groups, n_b), and pos
+    int32 [B, G, S] (each hit's position in its list) or None."""
+    keys: torch.Tensor
+    fill: torch.Tensor
+    scores: torch.Tensor
+    rows: torch.Tensor
+    count: torch.Tensor
+    pos: torch.Tensor | None
+
+
+def group_select_tags(cand_scores: torch.Tensor, cand_rows: torch.Tensor,
+                      cand_tags: torch.Tensor, key_mask: int, G: int, S: int, ncand=None,
+                      with_pos: bool = False) -> GroupSelection:
+    """rag_group_select over candidate lists on one device (fp32 / int64 / int32 tag bits, all
+    [B, C]): per query the first G groups of candidates sharing the key tag & key_mask (key 0:
+    no group), each with its first S hits, in list order — include/ragmi.h. `ncand`: None, a
+    scalar or one value per query. Index-free; enqueued on the current stream."""
+    dev = cand_scores.device
+    s = cand_scores.contiguous()
+    r = cand_rows.contiguous()
+    t = cand_tags.contiguous()
+    if s.dim() != 2 or s.shape != r.shape or s.shape != t.shape:
+        raise ValueError("cand_scores, cand_rows and cand_tags must all be [B, C]")
+    if s.dtype != torch.float32 or r.dtype != torch.int64 or t.dtype != torch.int32:
+        raise ValueError("candidates must be fp32 scores, int64 rows and int32 tag bits")
+    B, C = s.shape
+    G, S, key_mask = int(G), int(S), int(key_mask) & 0xFFFFFFFF
+    if not 1 <= C <= GROUPS_MAX_CANDIDATES:
+        raise ValueError(f"C must be in [1, {GROUPS_MAX_CANDIDATES}] candidates")
+    if not 1 <= G <= GROUPS_MAX or S < 1 or G * S > GROUPS_MAX_CELLS:
+        raise ValueError(f"G must be in [1, {GROUPS_MAX}], S >= 1 and G * S <= {GROUPS_MAX_CELLS}")
+    if key_mask == 0:
+        raise ValueError("key_mask must name the tag bits of the group_by field")
+    n = None
+    if ncand is not None:
+        n = torch.from_numpy(per_query(ncand, B, np.int32, "ncand")).to(dev)
+    keys = torch.empty((B, G), dtype=torch.int32, device=dev)
+    fill = torch.empty((B, G), dtype=torch.int32, device=dev)
+    out_s = torch.empty((B, G, S), dtype=torch.float32, device=dev)
+    out_r = torch.empty((B, G, S), dtype=torch.int64, device=dev)
+    pos = torch.empty((B, G, S), dtype=torch.int32, device=dev) if with_pos else None
+    count = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):      # index-free: the launch goes to the current device
+        check(_lib.load().rag_group_select(
+            s.data_ptr(), r.data_ptr(), t.data_ptr(), n.data_ptr() if n is not None else None,
+            B, C, key_mask, G, S, keys.data_ptr(), fill.data_ptr(), out_s.data_ptr(),
+            out_r.data_ptr(), pos.data_ptr() if pos is not None else None, count.data_ptr(),
+            _stream_ptr(dev)))
+    return GroupSelection(keys, fill, out_s, out_r, count, pos)
 
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int):

@@ -20,6 +20,7 @@ keyed by row; the keyword payload fields used by the reference's `must` filter (
 """
 from __future__ import annotations
 
+import itertools
 import os
 import shutil
 import threading
@@ -30,8 +31,9 @@ from typing import Any, Iterable
 import numpy as np
 import torch
 
+from . import groups
 from . import qdrant_models as models
-from .index import MAX_K, MMR_MAX_CANDIDATES, FlatIndex
+from .index import GROUPS_MAX, GROUPS_MAX_CELLS, MAX_K, MMR_MAX_CANDIDATES, FlatIndex
 from .shardset import ShardSet, parse_devices
 
 DEFAULT_TAG_FIELDS = ("ticker", "document_type")
@@ -80,6 +82,15 @@ class PayloadTags:
             c = len(table) + 1          # 0 = field absent
             table[value] = c
         return c
+
+    def value_of(self, f: int, code: int):
+        """The payload value behind code `code` of field f, the reverse of `code`: codes are
+        handed out in insertion order (1, 2, ...) and a dict keeps that order, so no second
+        table is kept."""
+        table = self.codes[f]
+        if not 1 <= code <= len(table):
+            raise KeyError(f"no value with code {code} for {self.fields[f]}")
+        return next(itertools.islice(table, code - 1, None))
 
     def tag(self, payload: dict | None) -> int:
         tag = 0
@@ -272,6 +283,7 @@ class Collection:
         self.op = 0
         self._unanswered = 0     # index.unanswered() as last read (Collection.search)
         self.rescued = 0         # queries re-answered on the full exact pass (stats)
+        self.group_stats = {}    # routes grouped searches took (ragmi.groups.search_groups)
         self.lock = threading.RLock()
         # 32 queries per scan pass at D = 384, 4 groups of 32 at D = 1024 (ragmi.h)
         self.coalescer = Coalescer(self, 0.0, 32 if dim <= 384 else 128,
@@ -474,6 +486,48 @@ class Collection:
         with self.lock:
             return [[self.point(r, s, True, with_vectors) for r, s in h]
                     for h in self.search_mmr(queries, limits, filters, diversity, candidates)]
+
+    def search_groups(self, queries, group_by: str, limit: int, group_size: int, filters: list,
+                      with_vectors=False, candidates: int | None = None,
+                      widen: int | None = None):
+        """Grouped search (ragmi.groups.search_groups): per request the `limit`
+        best groups of points sharing a value of tag field `group_by`, each with its
+        `group_size` best hits — exact, whatever `candidates` / `widen` (policy) say. Returns
+        per request a list of PointGroup (id = the payload value) whose hits are resolved to
+        ScoredPoints under the same hold of the lock (see search_points). The route counters
+        accumulate in `group_stats`."""
+        if group_by not in self.tags.fields:
+            raise UnsupportedFilter(
+                f"group_by {group_by!r} is not an indexed keyword field {self.tags.fields}; "
+                "create the collection with payload_tag_fields")
+        f = self.tags.fields.index(group_by)
+        shift = 16 * f
+        key_mask = 0xFFFF << shift
+        with self.lock:
+            B = len(filters)
+            out = [[] for _ in range(B)]
+            count = self.index.count
+            codes = self.tags.codes[f]
+            live = [i for i, fl in enumerate(filters) if fl is not None]
+            if limit < 1 or group_size < 1 or not live or count == 0 or not codes:
+                return out
+            # neither clamp can change a result: there are no more groups than codes, no
+            # more hits than points
+            G, S = min(int(limit), len(codes)), min(int(group_size), count)
+            if G > GROUPS_MAX or G * S > GROUPS_MAX_CELLS:
+                raise ValueError(f"grouped search: at most {GROUPS_MAX} groups and "
+                                 f"{GROUPS_MAX_CELLS} hits in all (limit x group_size)")
+            every = [c << shift for c in codes.values()]
+            possible = [[filters[i][1] & key_mask] if filters[i][0] & key_mask else every
+                        for i in live]
+            q, use = self._live_queries(queries, filters, live)
+            res = groups.search_groups(self.index, q, use, key_mask, possible, G, S, candidates,
+                                       widen, search=self._exact_lists, stats=self.group_stats)
+            for i, found in zip(live, res):
+                out[i] = [models.PointGroup(
+                    hits=[self.point(r, s, True, with_vectors) for r, s in hits],
+                    id=self.tags.value_of(f, key >> shift)) for key, hits in found]
+            return out
 
     def point(self, row: int, score: float, with_payload=True, with_vectors=False):
         payload = self.payloads[row] if with_payload else None
@@ -718,6 +772,39 @@ class QdrantClient:
                     hits[i] = h
         return [models.QueryResponse(points=_payloads(h[:int(r.limit)], r.with_payload))
                 for r, h in zip(requests, hits)]
+
+    def query_points_groups(self, collection_name: str, query=None, group_by: str | None = None,
+                            limit: int = 10, group_size: int = 3,
+                            query_filter: models.Filter | None = None, with_payload=True,
+                            with_vectors=False, **kwargs) -> models.GroupsResult:
+        """Qdrant's grouped search: the `limit` best groups of points sharing a value of
+        payload field `group_by` (one of the collection's payload_tag_fields), each with its
+        `group_size` best hits; points without the field belong to no group. Exact: `limit`
+        groups unless the filtered collection holds fewer values, `group_size` hits unless the
+        group holds fewer points. A grouped request never rides the coalescer."""
+        col = self._col(collection_name)
+        if group_by is None:
+            raise ValueError("query_points_groups needs group_by, a payload field")
+        if kwargs.get("with_lookup") is not None:
+            raise NotImplementedError("with_lookup (a join on another collection) is not supported")
+        query, mmr = nearest_of(query)
+        if mmr is not None:
+            raise ValueError("a grouped query cannot be an MMR query (NearestQuery.mmr)")
+        flt = col.compile_filter(query_filter)
+        q = query if isinstance(query, torch.Tensor) else np.asarray(query, dtype=np.float32)
+        found = col.search_groups(q.reshape(1, -1), group_by, int(limit), int(group_size), [flt],
+                                  with_vectors)[0]
+        for g in found:
+            _payloads(g.hits, with_payload)
+        return models.GroupsResult(groups=found)
+
+    def search_groups(self, collection_name: str, query_vector, group_by: str,
+                      query_filter=None, limit: int = 10, group_size: int = 1,
+                      with_payload=True, with_vectors=False, **kwargs) -> models.GroupsResult:
+        """Legacy qdrant_client.search_groups: query_points_groups."""
+        return self.query_points_groups(collection_name, query_vector, group_by, limit,
+                                        group_size, query_filter, with_payload, with_vectors,
+                                        **kwargs)
 
     def search(self, collection_name: str, query_vector, limit: int = 10,
                query_filter=None, with_payload=True, **kwargs):

@@ -118,6 +118,20 @@ class QueryResponse:
 
 
 @dataclass
+class PointGroup:
+    """One group of query_points_groups: the hits (ScoredPoints, best first) sharing the value
+    `id` of the group_by payload field."""
+    hits: list
+    id: Any
+    lookup: Any = None
+
+
+@dataclass
+class GroupsResult:
+    groups: list = field(default_factory=list)
+
+
+@dataclass
 class CollectionDescription:
     name: str
 

@@ -415,6 +415,34 @@ class ShardSet:
         s, g = self.search(q, C, f)
         return self.mmr(s, g, k, diversity, None if B and (nc == C).all() else nc)
 
+    # ---------------------------------------------------------------- grouped search
+    @_keeps_device
+    def gather_tags(self, global_rows) -> torch.Tensor:
+        """FlatIndex.gather_tags in global rows: every shard gathers the tags of its own rows
+        (it is given -1 for the others, which the gather answers with 0), the per-shard results
+        are copied to the merge device and combined. int32 tag bits, the shape of the rows,
+        0 for a row outside [0, capacity)."""
+        from .index import _as_dev
+        g = _as_dev(global_rows, torch.int64, self.device)
+        valid = (g >= 0) & (g < self.capacity)
+        out = torch.zeros(g.shape, dtype=torch.int32, device=self.device)
+        for sh, shard in enumerate(self.shards):
+            own = valid & (shard_of(g, self.n) == sh)
+            local = torch.where(own, local_of(g, self.n), -1)
+            out |= shard.gather_tags(local.to(shard.device)).to(self.device)
+        return out
+
+    @_keeps_device
+    def group_select(self, cand_scores, cand_rows, key_mask: int, G: int, S: int, ncand=None,
+                     with_pos: bool = False):
+        """FlatIndex.group_select in global rows: gather_tags over the shards, then the same
+        rag_group_select on the merge device. The selection reads only the lists, and global
+        rows travel unchanged, so the result is the one-index result bit for bit."""
+        from .index import _as_dev, group_select_tags
+        g = _as_dev(cand_rows, torch.int64, self.device)
+        return group_select_tags(_as_dev(cand_scores, torch.float32, self.device), g,
+                                 self.gather_tags(g), key_mask, G, S, ncand, with_pos)
+
     @_keeps_device
     def unanswered(self) -> int:
         """Sum of the shards' FlatIndex.unanswered()."""

@@ -245,6 +245,47 @@ int rag_index_mmr(rag_index_t* index, const float* cand_scores_dev, const int64_
                   int B, int C, int k, const float* diversity_dev, const int32_t* ncand_dev,
                   float* out_scores_dev, int64_t* out_ids_dev, int32_t* out_pos_dev, void* stream);
 
+/* Grouped search (Qdrant's query_points_groups(group_by, limit = G, group_size = S)): the G best
+ * groups of rows sharing a key, each with its S best hits. The key of row r is
+ * tag[r] & key_mask, key_mask being the 16 tag bits of the group_by field; key 0 (field absent)
+ * belongs to no group. Definition, for one query with filter (mask, value): the ranked list is
+ * every row r < count that passes the filter and has key(r) != 0, ordered by (canonical exact
+ * score desc, row asc) — rag_index_search's order and scores. Walk it in order: a row whose key
+ * was not seen yet opens the next group while fewer than G are open; a row of an open group with
+ * fewer than S hits is appended to it; every other row is skipped. Result: the groups in opening
+ * order (by best hit), each with its hits in list order. The ladder that makes this exact from
+ * candidate lists (ragmi.groups) is host logic over these two calls and
+ * rag_index_search. The reference never groups (it over-fetches a flat top-15, main.py:215), and
+ * parity with a Qdrant server's own grouped search, which is best-effort, is unpinned.
+ *
+ * rag_index_gather_tags: out_tags_dev[i] = tag[rows_dev[i]] (int64 [n] -> uint32 [n], device)
+ * for rows in [0, capacity), 0 otherwise: a row index outside that range is never dereferenced.
+ * Asynchronous on `stream`, under the handle's lock.
+ *
+ * rag_group_select: the walk above over candidate lists — cand_scores_dev fp32 [B][C],
+ * cand_rows_dev int64 [B][C] (-1 = none), cand_tags_dev uint32 [B][C] (rag_index_gather_tags of
+ * the rows). Index-free like rag_merge_topk: it reads only its input arrays and runs on the
+ * calling thread's current device. The candidates of query b are the first n_b entries, n_b =
+ * min(ncand_dev[b] (NULL = C; clamped to [0, C]), the leading entries with row >= 0). Outputs,
+ * every element written by the launch: out_keys_dev uint32 [B][G], the groups' keys in opening
+ * order, 0 past the last group; out_fill_dev int32 [B][G], hits per group; out_scores_dev fp32
+ * [B][G][S] (-inf padding), out_rows_dev int64 [B][G][S] (-1 padding) and out_pos_dev int32
+ * [B][G][S] (the hit's position j in its list, -1 padding; may be NULL); out_count_dev int32
+ * [B][2] = (number of groups, n_b). Deterministic, equal to the sequential walk. Limits, refused
+ * on the host before any HIP call: 1 <= C <= RAG_GROUPS_MAX_CANDIDATES, 1 <= G <= RAG_GROUPS_MAX,
+ * S >= 1, G * S <= RAG_GROUPS_MAX_CELLS (RAG_ERANGE); key_mask != 0, B >= 0, non-NULL pointers
+ * (RAG_EINVAL); B = 0 launches nothing. Asynchronous on `stream`. */
+#define RAG_GROUPS_MAX_CANDIDATES 4096 /* = RAG_MAX_K_LARGE */
+#define RAG_GROUPS_MAX 1024
+#define RAG_GROUPS_MAX_CELLS 4096
+int rag_index_gather_tags(rag_index_t* index, const int64_t* rows_dev, int64_t n,
+                          uint32_t* out_tags_dev, void* stream);
+int rag_group_select(const float* cand_scores_dev, const int64_t* cand_rows_dev,
+                     const uint32_t* cand_tags_dev, const int32_t* ncand_dev, int B, int C,
+                     uint32_t key_mask, int G, int S, uint32_t* out_keys_dev, int32_t* out_fill_dev,
+                     float* out_scores_dev, int64_t* out_rows_dev, int32_t* out_pos_dev,
+                     int32_t* out_count_dev, void* stream);
+
 /* Merge n_lists per-shard result lists (each [B][k] sorted by (score desc, id asc), device;
  * laid out [n_lists][B][k]; padding: id -1) into the global top-k [B][k] (device) by (score
  * desc, id asc), padding -inf / -1 past the valid entries. Any k >= 1 (k > RAG_MAX_K_LARGE:
