@@ -284,4 +284,14 @@ __device__ __forceinline__ float canon_scale(float x, double norm) {
   return norm > 0.0 ? (float)((double)x / norm) : 0.0f;
 }
 
+// order-preserving uint32 key of a float (larger float -> larger key; -inf smallest finite):
+// the radix selects and sorts of the large-k / full passes and of the any-k merge
+__device__ __forceinline__ uint32_t fkey(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float fkey_inv(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
 }  // namespace ragmi

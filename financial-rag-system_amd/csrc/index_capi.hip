@@ -19,7 +19,14 @@
 
 #include "../../include/ragmi.h"
 #include "common_host.hpp"
+// the device layer, one header per pass, in dependency order
+#include "prep_kernels.hip"
 #include "scan_kernels.hip"
+#include "seed_kernels.hip"
+#include "certify_kernels.hip"
+#include "merge_kernels.hip"
+#include "largek_kernels.hip"
+#include "reselect_kernels.hip"
 #include "rows_kernels.hip"
 
 #include <hipcub/hipcub.hpp>
@@ -283,7 +290,7 @@ int ensure_stage(rag_index* h, size_t bytes) {
   return RAG_OK;
 }
 
-// qprep's extra error-bound term for fp32 storage (scan_kernels.hip qprep_kernel): the exact
+// qprep's extra error-bound term for fp32 storage (prep_kernels.hip qprep_kernel): the exact
 // score reads the fp32 row c32, the scan its fp16 rounding c: |sum (c - c32) qn| <=
 // ||c - c32|| ||qn|| <= (2^-11 ||c32|| + 2^-25 sqrt(D)) (1 + 2^-20), ||c32|| <= 1 + 2^-20
 double store_eps(const rag_index* h) {
@@ -570,7 +577,7 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   return RAG_OK;
 }
 
-// One search pass of <= 32 queries for RAG_MAX_K < k <= RAG_MAX_K_LARGE (scan_kernels.hip,
+// One search pass of <= 32 queries for RAG_MAX_K < k <= RAG_MAX_K_LARGE (largek_kernels.hip,
 // "Exact top-k for RAG_MAX_K < k"): qprep, a sample of the shard's tiles for the bound, then
 // kLkRounds (collect, final) launch pairs; rounds after the first return at once unless a
 // query's candidate list overflowed in the previous one.
@@ -584,7 +591,7 @@ int ensure_lk(Workspace& w) {
   return RAG_OK;
 }
 
-// One search pass of <= 32 queries by the full exact path (scan_kernels.hip "Exact top-k
+// One search pass of <= 32 queries by the full exact path (largek_kernels.hip "Exact top-k
 // for ANY k"): k > RAG_MAX_K_LARGE, or rag_index_search_full. Per query: exact scores of every
 // row, a stable descending radix sort of (key, row), the first k emitted. The sort buffers
 // (16 B per row + hipcub's scratch) are stream-ordered allocations released at the pass's end.
@@ -655,7 +662,7 @@ int launch_full_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_t 
 }
 
 // k > RAG_MAX_K_LARGE: per query, three stable radix sorts over the n_lists * k entries
-// (scan_kernels.hip merge_any_*; the full pass's SortPairsDescending<uint32, int>, no other
+// (merge_kernels.hip merge_any_*; the full pass's SortPairsDescending<uint32, int>, no other
 // hipcub instantiation); stream-ordered scratch released at the end
 template <bool PACKED>
 int merge_any_k(const float* in_s, const int64_t* in_i, int n_lists, int B, int k, float* out_s,
@@ -1439,7 +1446,7 @@ int rag_index_scatter_rows(rag_index_t* h, const int64_t* rows, int64_t n, const
       const_cast<float*>(in_f32), const_cast<uint32_t*>(in_tags), new_count, stream);
 }
 
-// ---- MMR re-selection (mmr_kernel, scan_kernels.hip) ----
+// ---- MMR re-selection (mmr_kernel, reselect_kernels.hip) ----
 
 int rag_index_mmr(rag_index_t* h, const float* cand_s, const int64_t* cand_r, int B, int C, int k,
                   const float* diversity, const int32_t* ncand, float* out_s, int64_t* out_i,
@@ -1468,7 +1475,7 @@ int rag_index_mmr(rag_index_t* h, const float* cand_s, const int64_t* cand_r, in
   return RAG_OK;
 }
 
-// ---- grouped search: tag gather and group selection (rows_kernels.hip) ----
+// ---- grouped search: tag gather (rows_kernels.hip) and group selection (reselect_kernels.hip) ----
 
 int rag_index_gather_tags(rag_index_t* h, const int64_t* rows, int64_t n, uint32_t* out_tags,
                           void* stream) {

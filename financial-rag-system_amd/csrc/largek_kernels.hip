@@ -1,0 +1,477 @@
+// largek_kernels.hip — the exact passes for k beyond the scan's 32 per-wave candidates
+// (included by index_capi.hip after seed_kernels.hip and certify_kernels.hip): the radix
+// select, the large-k pass (lk_bound / lk_collect / lk_rescore / lk_final) and the full exact
+// pass for any k (full_score / full_emit).
+namespace ragmi {
+
+// ----------------------------------------------------------------------------------------
+// Exact top-k for RAG_MAX_K < k <= RAG_MAX_K_LARGE (round 5): Qdrant's
+// query_points takes any `limit` (reference main.py:215,232-237); the scan's per-wave lists
+// hold 32. A pass of <= 32 queries runs, after qprep:
+//  1. sample_kernel over n_sample tiles spread over the shard (per tile and query the max MFMA
+//     score a of its matching rows) and lk_bound_kernel: T = the k-th largest of those maxima.
+//     They come from k distinct rows, each with exact score e >= a - eps (qprep's bound), so
+//     the k-th best exact score e_k >= T - eps and every exact top-k row has
+//     a >= e - eps >= T - 2 eps = thr. (Fewer than k finite maxima: thr = -inf.)
+//  2. lk_collect_kernel: every tile MFMA-scored; each matching row with a >= thr is appended
+//     to its query's candidate list (at most kLkCap kept; the counter counts them all).
+//  3. lk_final_kernel: per query, the candidates are rescored exactly (exact_scores_wave: the
+//     canonical fp64 order of select / the oracle) and the k best by (score desc, row asc) are
+//     emitted. They contain the exact top-k, so the result is exact. If the list overflowed,
+//     the k-th best exact score e' among the kept candidates (real rows: e_k >= e') gives a
+//     tighter thr = e' - eps, and steps 2-3 run again for that query (kLkRounds launches in
+//     all; later ones return at once unless a query was marked). A query still overflowing in
+//     the last round (more than kLkCap rows tied within 2 eps of its k-th best) is recorded
+//     as unanswered (tier 3, rag_index_unanswered), never silently truncated.
+// ----------------------------------------------------------------------------------------
+constexpr int kLkMax = 4096;       // largest k (ragmi.h RAG_MAX_K_LARGE)
+constexpr int kLkCap = 16384;      // candidates kept per query and round (exact scores in LDS)
+constexpr int kLkRounds = 3;
+constexpr int kLkSampleMax = 16384;
+
+// the kk-th largest of the n keys key(i), 1 <= kk <= n (multiplicity counted; 256 threads):
+// a radix select over 8-bit digits, most significant first — each pass an LDS histogram of the
+// keys that match the digits chosen so far, then wave 0 scans the 256 bins from the top (a
+// wave-wide prefix sum) for the digit where the count reaches kk. 4 passes where a bisection
+// over the 32 key bits took 32 (round 5: lk_bound 166 us for 16384 keys).
+template <typename KeyFn>
+__device__ uint32_t radix_kth_key(KeyFn key, int n, int kk, int* hist, int* sh) {
+  uint32_t prefix = 0, mask = 0;
+  int need = kk;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      const uint32_t v = key(i);
+      if ((v & mask) == prefix) atomicAdd(&hist[(v >> shift) & 255u], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+      // lane l holds digits 255 - 4l .. 252 - 4l (descending); inclusive scan over lanes
+      const int l = threadIdx.x;
+      int bv[4], sl = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        bv[j] = hist[255 - 4 * l - j];
+        sl += bv[j];
+      }
+      int incl = sl;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (l >= o) incl += t;
+      }
+      const int excl = incl - sl;
+      if (excl < need && need <= incl) {       // exactly one lane
+        int c = excl, d = 255 - 4 * l;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          d = 255 - 4 * l - j;
+          if (c + bv[j] >= need) break;
+          c += bv[j];
+        }
+        sh[0] = d;
+        sh[1] = need - c;
+      }
+    }
+    __syncthreads();
+    prefix |= (uint32_t)sh[0] << shift;
+    mask |= 255u << shift;
+    need = sh[1];
+    __syncthreads();
+  }
+  return prefix;
+}
+
+// per query q < B: thr[q] from the sample maxima smax [32][n_sample]; resets the round state
+__global__ __launch_bounds__(256) void lk_bound_kernel(const float* __restrict__ smax,
+                                                       int n_sample, int k,
+                                                       const float* __restrict__ eps,
+                                                       float* __restrict__ thr,
+                                                       int* __restrict__ cnt,
+                                                       int* __restrict__ again,
+                                                       int* __restrict__ need) {
+  __shared__ uint32_t keys[kLkSampleMax];
+  __shared__ int red, hist[256], sh[2];
+  const int q = blockIdx.x;
+  int fin = 0;
+  for (int i = threadIdx.x; i < n_sample; i += 256) {
+    const float v = smax[(int64_t)q * n_sample + i];
+    keys[i] = fkey(v);
+    fin += v != kNegInf;
+  }
+  if (threadIdx.x == 0) red = 0;
+  __syncthreads();
+  atomicAdd(&red, fin);
+  __syncthreads();
+  const int n_fin = red;
+  __syncthreads();
+  float th = kNegInf;
+  if (n_fin >= k) {
+    const float T = fkey_inv(radix_kth_key([&](int i) { return keys[i]; }, n_sample, k, hist, sh));
+    const double d = (double)T - 2.0 * (double)eps[q];
+    th = (float)d;
+    if ((double)th > d) th = nextafterf(th, kNegInf);   // round toward -inf
+  }
+  if (threadIdx.x == 0) {
+    thr[q] = th;
+    cnt[q] = 0;
+    again[q] = 1;     // round 0 processes every query
+  }
+  if (q == 0 && threadIdx.x < kLkRounds) need[threadIdx.x] = threadIdx.x == 0 ? 1 : 0;
+}
+
+// every tile against the pass's queries: append matching rows with a >= thr[q]. One wave per
+// tile per step (grid-stride). round > 0: only if the previous round marked a query, and only
+// the marked queries.
+template <int D, bool FILTER>
+__global__ __launch_bounds__(256) void lk_collect_kernel(const half8* __restrict__ corpus,
+                                                         const uint32_t* __restrict__ tags,
+                                                         const uint32_t* __restrict__ filt,
+                                                         const half8* __restrict__ qfrag,
+                                                         int n_rows, int n_tiles, int B,
+                                                         const float* __restrict__ thr,
+                                                         int* __restrict__ cnt,
+                                                         int* __restrict__ cand,
+                                                         const int* __restrict__ again,
+                                                         const int* __restrict__ need, int round) {
+  constexpr int S = steps<D>();
+  if (!need[round]) return;
+  const int lane = threadIdx.x & 63;
+  const int nw = gridDim.x * 4;
+  const int w0 = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // this lane's two queries: (l & 15) and 16 + (l & 15)
+  const int qa = lane & 15, qb = 16 + (lane & 15);
+  const bool la = qa < B && again[qa], lb = qb < B && again[qb];
+  const float ta = la ? thr[qa] : __builtin_inff(), tb = lb ? thr[qb] : __builtin_inff();
+  uint32_t fma_ = 0, fva = 0, fmb = 0, fvb = 0;
+  if constexpr (FILTER) {
+    fma_ = filt[2 * qa];
+    fva = filt[2 * qa + 1];
+    fmb = filt[2 * qb];
+    fvb = filt[2 * qb + 1];
+  }
+  // D <= 384: the two query groups' fragments stay in registers for the whole launch (24
+  // half8); reloading them per tile tripled the vector-memory instructions per tile
+  // (k = 33 collect 1.34 ms vs the scan's 1.08 over the same 10M rows, round 5)
+  constexpr bool QREG = S <= 12;
+  half8 qra[QREG ? S : 1], qrb[QREG ? S : 1];
+  if constexpr (QREG) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      qra[s] = qfrag[s * 64 + lane];
+      qrb[s] = qfrag[(S + s) * 64 + lane];
+    }
+  }
+  for (int t = w0; t < n_tiles; t += nw) {
+    const half8* p = corpus + (int64_t)t * (S * 64) + lane;
+    floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (QREG) {
+      half8 a[S];
+#pragma unroll
+      for (int s = 0; s < S; ++s) a[s] = __builtin_nontemporal_load(p + s * 64);
+      tile_mfma<S>(a, qra, qrb, acc0, acc1);
+    } else {
+      tile_scores_chunked<S, 8>(p, qfrag, lane, acc0, acc1);
+    }
+    const int rbase = t * kTileRows + 4 * (lane >> 4);
+    uint4 tg = {0u, 0u, 0u, 0u};
+    if constexpr (FILTER) tg = *reinterpret_cast<const uint4*>(tags + rbase);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = rbase + r;
+      if (row >= n_rows) break;
+      bool oka = acc0[r] >= ta, okb = acc1[r] >= tb;
+      if constexpr (FILTER) {
+        const uint32_t tr = r == 0 ? tg.x : r == 1 ? tg.y : r == 2 ? tg.z : tg.w;
+        oka = oka && ((tr & fma_) == fva);
+        okb = okb && ((tr & fmb) == fvb);
+      }
+      if (oka) {
+        const int pos = atomicAdd(&cnt[qa], 1);
+        if (pos < kLkCap) cand[qa * kLkCap + pos] = row;
+      }
+      if (okb) {
+        const int pos = atomicAdd(&cnt[qb], 1);
+        if (pos < kLkCap) cand[qb * kLkCap + pos] = row;
+      }
+    }
+  }
+}
+
+// per query (workgroup q < B): exact rescoring of the candidates, then the top-k by
+// (score desc, row asc) -> output; on overflow a tighter thr and another round (see above).
+// 3a. exact scores of query q's kept candidates (lk_collect's list), 256 candidates per
+// workgroup, grid (kLkCap / 256, B): the same canonical fp64 order as select / the oracle
+// (exact_scores_wave), 8 rows per wave per round trip. One workgroup per query rescored
+// ~1,300 candidates at k = 33 in ~0.6 ms of serial round trips (round 5).
+template <int D>
+__global__ __launch_bounds__(256) void lk_rescore_kernel(const half8* __restrict__ corpus,
+                                                         const float* __restrict__ qn,
+                                                         const int* __restrict__ cnt,
+                                                         const int* __restrict__ cand,
+                                                         const int* __restrict__ again,
+                                                         const int* __restrict__ need, int round,
+                                                         float* __restrict__ es_g,
+                                                         const float* __restrict__ rows32) {
+  const int q = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (!need[round] || !again[q]) return;
+  const int n = min(cnt[q], kLkCap);
+  const int c0 = blockIdx.x * 256, c1 = min(n, c0 + 256);
+  if (c0 >= c1) return;
+  const int* cq = cand + (int64_t)q * kLkCap;
+  const float* qq = qn + (int64_t)q * D;
+  constexpr int NC = 8;
+  for (int i0 = c0 + wid * NC; i0 < c1; i0 += 4 * NC) {
+    int rows[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) rows[j] = i0 + j < c1 ? cq[i0 + j] : -1;
+    float sc[NC];
+    exact_scores_wave<D, NC>(corpus, rows, qq, lane, sc, rows32);
+    if (lane == 0)
+#pragma unroll
+      for (int j = 0; j < NC; ++j)
+        if (i0 + j < c1) es_g[(int64_t)q * kLkCap + i0 + j] = sc[j];
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void lk_final_kernel(const half8* __restrict__ corpus,
+                                                       const float* __restrict__ qn, int k,
+                                                       int* __restrict__ cnt,
+                                                       const int* __restrict__ cand,
+                                                       const float* __restrict__ es_g,
+                                                       const float* __restrict__ eps,
+                                                       float* __restrict__ thr,
+                                                       int* __restrict__ again,
+                                                       int* __restrict__ need, int round,
+                                                       int* __restrict__ tier,
+                                                       unsigned long long* __restrict__ fb_cnt,
+                                                       int64_t id_offset,
+                                                       float* __restrict__ out_s,
+                                                       int64_t* __restrict__ out_i,
+                                                       int32_t* __restrict__ out_packed,
+                                                       const float* __restrict__ rows32) {
+  __shared__ float es[kLkCap];            // exact scores of the kept candidates
+  __shared__ float ss[kLkMax];            // the selected entries (sorted in place)
+  __shared__ int si[kLkMax];
+  __shared__ int red, red2, verdict, hist[256], sh[2];
+  const int q = blockIdx.x;
+  if (!need[round] || !again[q]) return;
+  const int total = cnt[q];
+  const int n = min(total, kLkCap);
+  const int* cq = cand + (int64_t)q * kLkCap;
+  // 1. the kept candidates' exact scores (lk_rescore_kernel, spread over many workgroups)
+  for (int i = threadIdx.x; i < n; i += 256) es[i] = es_g[(int64_t)q * kLkCap + i];
+  __syncthreads();
+  // block-wide count of the candidates passing pred(i)
+  auto count_if = [&](auto pred) -> int {
+    int m = 0;
+    for (int i = threadIdx.x; i < n; i += 256) m += pred(i) ? 1 : 0;
+    if (threadIdx.x == 0) red = 0;
+    __syncthreads();
+    atomicAdd(&red, m);
+    __syncthreads();
+    const int r = red;
+    __syncthreads();
+    return r;
+  };
+  // 2. tkey = the key of the kk-th best exact score among the kept candidates
+  const int kk = min(k, n);
+  uint32_t tkey = 0;
+  if (kk > 0) tkey = radix_kth_key([&](int i) { return fkey(es[i]); }, n, kk, hist, sh);
+  if (total > kLkCap) {
+    // overflow: the kept candidates are real rows, so e_k >= fkey_inv(tkey) and every exact
+    // top-k row has a >= that - eps: a tighter threshold for the next round
+    if (threadIdx.x == 0) {
+      verdict = 0;                            // 0: unanswered, 1: another round
+      if (round + 1 < kLkRounds && n >= k) {
+        const double d = (double)fkey_inv(tkey) - (double)eps[q];
+        float th = (float)d;
+        if ((double)th > d) th = nextafterf(th, kNegInf);
+        if (th > thr[q]) {
+          thr[q] = th;
+          cnt[q] = 0;
+          need[round + 1] = 1;                // (again[q] stays 1)
+          verdict = 1;
+        }
+      }
+      if (!verdict) {                         // no progress possible: tier 3
+        tier[q] = 3;
+        atomicAdd(&fb_cnt[2], 1ull);
+        again[q] = 0;
+      }
+    }
+    __syncthreads();
+    if (verdict) return;
+    for (int j = threadIdx.x; j < k; j += 256) {
+      if (out_packed) {
+        out_packed[((int64_t)q * k + j) * 2] = __float_as_int(kNegInf);
+        out_packed[((int64_t)q * k + j) * 2 + 1] = -1;
+      } else {
+        out_s[(int64_t)q * k + j] = kNegInf;
+        out_i[(int64_t)q * k + j] = -1;
+      }
+    }
+    return;
+  }
+  // 3. the selected set: every candidate with key > tkey, then the ties (key == tkey) by row
+  //    ascending up to kk — rcut = the largest admitted tie row
+  const int gt = kk > 0 ? count_if([&](int i) { return fkey(es[i]) > tkey; }) : 0;
+  const int need_eq = kk - gt;
+  int rcut = -1;
+  if (need_eq > 0) {
+    // the largest r with #{ties with row < r} < need_eq: then row r is a tie row and exactly
+    // need_eq ties have row <= r (rows are distinct within a round)
+    uint32_t r = 0;
+    for (int bit = 30; bit >= 0; --bit) {
+      const uint32_t c = r | (1u << bit);
+      if (count_if([&](int i) { return fkey(es[i]) == tkey && (uint32_t)cq[i] < c; }) < need_eq)
+        r = c;
+    }
+    rcut = (int)r;
+  }
+  if (threadIdx.x == 0) red2 = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float s = es[i];
+    const uint32_t key = fkey(s);
+    const int row = cq[i];
+    if (kk > 0 && (key > tkey || (key == tkey && row <= rcut))) {
+      const int p = atomicAdd(&red2, 1);
+      if (p < kLkMax) {
+        ss[p] = s;
+        si[p] = row;
+      }
+    }
+  }
+  __syncthreads();
+  // 4. bitonic sort of the kk selected entries by (score desc, row asc), padded to P
+  int P = 1;
+  while (P < kk) P <<= 1;
+  for (int i = kk + threadIdx.x; i < P; i += 256) {
+    ss[i] = kNegInf;
+    si[i] = kIdNone32;
+  }
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = threadIdx.x; i < P; i += 256) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const bool best_first = (i & size) == 0;
+          const float a = ss[i], b = ss[j];
+          const int ia = si[i], ib = si[j];
+          const bool a_better = (a > b) || (a == b && ia < ib);
+          if (best_first != a_better) {
+            ss[i] = b;
+            ss[j] = a;
+            si[i] = ib;
+            si[j] = ia;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  for (int j = threadIdx.x; j < k; j += 256) {
+    const bool ok = j < kk;
+    const float s = ok ? ss[j] : kNegInf;
+    const int id = ok ? si[j] : -1;
+    if (out_packed) {
+      out_packed[((int64_t)q * k + j) * 2] = __float_as_int(s);
+      out_packed[((int64_t)q * k + j) * 2 + 1] = ok ? (int32_t)(id + id_offset) : -1;
+    } else {
+      out_s[(int64_t)q * k + j] = s;
+      out_i[(int64_t)q * k + j] = ok ? (int64_t)id + id_offset : (int64_t)-1;
+    }
+  }
+  if (threadIdx.x == 0) {
+    tier[q] = 0;
+    again[q] = 0;
+  }
+}
+
+// ----------------------------------------------------------------------------------------
+// Exact top-k for ANY k (round 6, VERDICT r5 item 7 / ADVICE r5): Qdrant's query_points
+// answers any `limit` (reference main.py:215,232-239, whose `except Exception` would turn a
+// refusal into "no documents"). For k > RAG_MAX_K_LARGE — and for a large-k query that more
+// than kLkCap near-ties left unanswered — one query at a time:
+//  1. full_score_kernel: every row scored exactly (exact_scores_wave, the canonical fp64
+//     order of select / lk_final / the oracle); key = fkey(score) for a row that passes the
+//     query's filter, 0 (below every real score's key) for one that does not; value = row.
+//  2. a stable radix sort of (key, row) pairs, keys descending (hipcub): equal keys keep
+//     their row-ascending input order, i.e. (score desc, row asc) — the oracle's order.
+//  3. full_emit_kernel: the first k entries (the n_match matching rows first), -inf / -1
+//     padding past n_match.
+// A rare path by construction (≈3 ms per query at 10M rows); no candidate list, no
+// threshold, so nothing can overflow.
+// ----------------------------------------------------------------------------------------
+template <int D, bool FILTER>
+__global__ __launch_bounds__(256) void full_score_kernel(const half8* __restrict__ corpus,
+                                                         const uint32_t* __restrict__ tags,
+                                                         const uint32_t* __restrict__ filt,
+                                                         const float* __restrict__ qq,
+                                                         int n_rows,
+                                                         const float* __restrict__ rows32,
+                                                         uint32_t* __restrict__ keys,
+                                                         int* __restrict__ vals,
+                                                         int* __restrict__ n_match) {
+  constexpr int NC = 8;
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int nw = gridDim.x * 4;
+  uint32_t fm = 0, fv = 0;
+  if constexpr (FILTER) {
+    fm = filt[0];
+    fv = filt[1];
+  }
+  int m = 0;
+  for (int r0 = wave * NC; r0 < n_rows; r0 += nw * NC) {
+    int rows[NC];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) rows[i] = r0 + i < n_rows ? r0 + i : -1;
+    float sc[NC];
+    exact_scores_wave<D, NC>(corpus, rows, qq, lane, sc, rows32);
+    float s = sc[0];
+#pragma unroll
+    for (int i = 1; i < NC; ++i)
+      if (lane == i) s = sc[i];
+    const int row = r0 + lane;
+    if (lane < NC && row < n_rows) {
+      bool ok = true;
+      if constexpr (FILTER) ok = (tags[row] & fm) == fv;
+      if (s == 0.0f) s = 0.0f;               // -0 and +0 compare equal: one key for both
+      keys[row] = ok ? fkey(s) : 0u;
+      vals[row] = row;
+      m += ok ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) m += __shfl_xor(m, d, 64);
+  if (lane == 0 && m > 0) atomicAdd(n_match, m);
+}
+
+__global__ __launch_bounds__(256) void full_emit_kernel(const uint32_t* __restrict__ keys,
+                                                        const int* __restrict__ vals,
+                                                        const int* __restrict__ n_match, int k,
+                                                        int64_t id_offset,
+                                                        float* __restrict__ out_s,
+                                                        int64_t* __restrict__ out_i,
+                                                        int32_t* __restrict__ out_packed) {
+  const int m = *n_match;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < k;
+       j += (int64_t)gridDim.x * 256) {
+    const bool ok = j < m;
+    const float s = ok ? fkey_inv(keys[j]) : kNegInf;
+    const int64_t id = ok ? (int64_t)vals[j] + id_offset : (int64_t)-1;
+    if (out_packed) {
+      out_packed[2 * j] = __float_as_int(s);
+      out_packed[2 * j + 1] = (int32_t)id;
+    } else {
+      out_s[j] = s;
+      out_i[j] = id;
+    }
+  }
+}
+
+}  // namespace ragmi

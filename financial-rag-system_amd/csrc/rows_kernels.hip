@@ -1,7 +1,8 @@
-// rows_kernels.hip — row removal for the flat index (included by index_capi.hip after
-// scan_kernels.hip): the ordered tag select and the indexed row copies behind
-// rag_index_select_rows / move_rows / gather_rows / scatter_rows, and the grouped search's tag
-// gather and group selection behind rag_index_gather_tags / rag_group_select (include/ragmi.h).
+// rows_kernels.hip — row-wise access to the flat index (included by index_capi.hip last; it
+// needs only the tile16 layout of prep_kernels.hip): the ordered tag select and the indexed row
+// copies behind rag_index_select_rows / move_rows / gather_rows / scatter_rows, the grouped
+// search's tag gather behind rag_index_gather_tags (include/ragmi.h), and the export / import
+// of rows between tile16 and row-major (persistence).
 //
 // A deleted row is physically removed: a surviving row from the tail takes its slot in every
 // stored form (the fp16 tile16 pieces, the fp32 row of an fp32-storage index, the tag), bit
@@ -134,7 +135,8 @@ __global__ __launch_bounds__(kSelBlock) void select_emit_kernel(
 }
 
 // ----------------------------------------------------------------------------------------
-// grouped search (rag_index_gather_tags, rag_group_select).
+// grouped search (rag_index_gather_tags; the group selection it feeds is
+// group_select_kernel, reselect_kernels.hip).
 // gather_tags_kernel: out[i] = tag[rows[i]] for rows in [0, cap_rows), 0 otherwise; a row index
 // outside that range is never dereferenced.
 // ----------------------------------------------------------------------------------------
@@ -147,149 +149,6 @@ __global__ __launch_bounds__(kTagBlock) void gather_tags_kernel(
   if (i >= n) return;
   const int64_t r = rows[i];
   out[i] = (r >= 0 && r < cap_rows) ? tags[r] : 0u;
-}
-
-// group_select_kernel: the sequential walk of include/ragmi.h over one query's candidate list,
-// in parallel form. One workgroup per query; it reads only its input arrays (no index).
-//   key[j]   = tag[j] & key_mask, in LDS (16 KiB at C = 4096)
-//   rank[j]  = number of i < j with key[i] == key[j]
-//   first[j] = key[j] != 0 && rank[j] == 0; the group index of a key = the number of firsts
-//              before its own first
-//   emit iff key[j] != 0, group index < G, rank < S, at out[b][group][rank]
-// The list is walked in trips of kGrpBlock candidates, in order, against a table of the groups
-// opened so far (s_gkey, in opening order; s_cnt, their candidates seen in earlier trips). A
-// candidate looks its key up in the table (the earlier trips), then counts the earlier
-// candidates of its own trip with its key, so rank = s_cnt[group] + the in-trip count and a
-// trip costs ng / 4 + at most kGrpBlock / 4 LDS reads per lane however long the list is. A key
-// that is in neither is a first: it takes index ng + the number of this trip's earlier firsts
-// (ballot / popcount per wave, wave totals in LDS) and enters the table while that is < G; a
-// later candidate of the trip with the same key reads the index back from its first's lane
-// (s_tg). A candidate whose group already holds S hits, or whose key is unknown when G groups
-// are open, can never be emitted and takes no further part. Both loops read LDS four keys at a
-// time at a wave-uniform address (a broadcast: no bank conflict); the in-trip one runs to the
-// wave's last candidate and a lane masks off the entries at or past its own j.
-// Every position is a pure function of the inputs: integer LDS atomics only (min, add), whose
-// results do not depend on their order, so the output is the same on every run. Every output
-// element is written exactly once: the emitted entries in the trips, the padding (-inf / -1 /
-// -1, key 0, fill 0) after the last one from the counts.
-// ----------------------------------------------------------------------------------------
-constexpr int kGrpBlock = 512;
-constexpr int kGrpMaxC = 4096;      // RAG_GROUPS_MAX_CANDIDATES
-constexpr int kGrpMaxG = 1024;      // RAG_GROUPS_MAX
-constexpr int kGrpMaxCells = 4096;  // G * S
-
-__global__ __launch_bounds__(kGrpBlock) void group_select_kernel(
-    const float* __restrict__ cand_s, const int64_t* __restrict__ cand_r,
-    const uint32_t* __restrict__ cand_t, const int32_t* __restrict__ ncand, int C,
-    uint32_t key_mask, int G, int S, uint32_t* __restrict__ out_keys, int32_t* __restrict__ out_fill,
-    float* __restrict__ out_s, int64_t* __restrict__ out_r, int32_t* __restrict__ out_pos,
-    int32_t* __restrict__ out_count) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_key[kGrpMaxC];
-  __shared__ __attribute__((aligned(16))) uint32_t s_gkey[kGrpMaxG];   // keys of the open groups
-  __shared__ int s_cnt[kGrpMaxG];    // their candidates seen in the earlier trips
-  __shared__ int s_tg[kGrpBlock];    // group index of this trip's firsts, by lane
-  __shared__ int s_wcnt[kGrpBlock / 64];
-  __shared__ int s_n;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int64_t b = blockIdx.x;
-  cand_s += b * C;
-  cand_r += b * C;
-  cand_t += b * C;
-  const int64_t obase = b * G * S;
-
-  if (tid == 0) {
-    int n0 = C;
-    if (ncand) n0 = min(C, max(0, ncand[b]));
-    s_n = n0;
-  }
-  for (int g = tid; g < ((G + 3) & ~3); g += kGrpBlock) {   // <= kGrpMaxG; 0 matches no live key
-    s_gkey[g] = 0u;
-    s_cnt[g] = 0;
-  }
-  __syncthreads();
-  for (int j = tid; j < C; j += kGrpBlock) {
-    s_key[j] = cand_t[j] & key_mask;
-    if (cand_r[j] < 0) atomicMin(&s_n, j);   // the list ends at its first absent row
-  }
-  __syncthreads();
-  const int n = s_n;
-
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int ng = 0;   // open groups (uniform)
-  for (int base = 0; base < n; base += kGrpBlock) {
-    const int j = base + tid;
-    uint32_t key = j < n ? s_key[j] : 0u;
-    int g = -1, before = 0;
-    if (key != 0u) {
-      for (int e = 0; e < ng; e += 4) {
-        const uint4 k4 = *reinterpret_cast<const uint4*>(&s_gkey[e]);
-        g = k4.x == key ? e : k4.y == key ? e + 1 : k4.z == key ? e + 2 : k4.w == key ? e + 3 : g;
-      }
-      if (g >= 0) before = s_cnt[g];
-      // its group is full, or no group is left to open: never emitted (nor are its key's others)
-      if (g >= 0 ? before >= S : ng >= G) key = 0u;
-    }
-    int rank_in = 0, fin = -1;   // this trip's earlier candidates with the key; the first of them
-    if (key != 0u) {
-      const int lend = min(n, base + (w + 1) * 64);   // wave-uniform: the wave's last candidate
-      for (int i = base; i < lend; i += 4) {
-        const uint4 k4 = *reinterpret_cast<const uint4*>(&s_key[i]);
-        const bool m0 = i < j && k4.x == key;
-        const bool m1 = i + 1 < j && k4.y == key;
-        const bool m2 = i + 2 < j && k4.z == key;
-        const bool m3 = i + 3 < j && k4.w == key;
-        if (fin < 0) fin = m0 ? i : m1 ? i + 1 : m2 ? i + 2 : m3 ? i + 3 : -1;
-        rank_in += (int)m0 + (int)m1 + (int)m2 + (int)m3;
-      }
-    }
-    const bool first = key != 0u && g < 0 && rank_in == 0;
-    const unsigned long long fb = __ballot(first);
-    if (lane == 0) s_wcnt[w] = __popcll(fb);
-    __syncthreads();   // every lane has read the table and the counts
-    int wbase = 0, tot = 0;
-    for (int u = 0; u < kGrpBlock / 64; ++u) {
-      const int t = s_wcnt[u];
-      if (u < w) wbase += t;
-      tot += t;
-    }
-    if (first) {
-      g = ng + wbase + __popcll(fb & below);
-      s_tg[tid] = g;
-      if (g < G) s_gkey[g] = key;
-    }
-    __syncthreads();   // this trip's firsts are in s_tg
-    if (key != 0u && g < 0) g = s_tg[fin - base];
-    if (key != 0u && g < G) {
-      const int rank = before + rank_in;
-      if (first) out_keys[b * G + g] = key;
-      if (rank < S) {
-        const int64_t o = obase + (int64_t)g * S + rank;
-        out_s[o] = cand_s[j];
-        out_r[o] = cand_r[j];
-        if (out_pos) out_pos[o] = j;
-      }
-      atomicAdd(&s_cnt[g], 1);
-    }
-    ng = min(ng + tot, G);
-    __syncthreads();   // table, counts, s_tg and s_wcnt are settled for the next trip
-  }
-  for (int g = tid; g < G; g += kGrpBlock) {
-    out_fill[b * G + g] = min(s_cnt[g], S);
-    if (g >= ng) out_keys[b * G + g] = 0u;
-  }
-  const int cells = G * S;
-  for (int e = tid; e < cells; e += kGrpBlock) {
-    const int g = e / S, r = e - g * S;
-    if (r >= s_cnt[g]) {
-      out_s[obase + e] = kNegInf;
-      out_r[obase + e] = -1;
-      if (out_pos) out_pos[obase + e] = -1;
-    }
-  }
-  if (tid == 0) {
-    out_count[b * 2] = ng;
-    out_count[b * 2 + 1] = n;
-  }
 }
 
 // ----------------------------------------------------------------------------------------
@@ -310,12 +169,6 @@ __global__ __launch_bounds__(kGrpBlock) void group_select_kernel(
 constexpr int kRowsBlock = 256;
 constexpr int kRowsGroup = 16;
 enum { kRowsMove = 0, kRowsGather = 1, kRowsScatter = 2 };
-
-// half8 slot of piece c (halves 8c .. 8c+7) of row `row` in the tile16 layout
-template <int D>
-__device__ __forceinline__ int64_t tile_slot(int64_t row, int c) {
-  return (row >> 4) * (steps<D>() * 64) + (c >> 2) * 64 + (c & 3) * 16 + (row & 15);
-}
 
 template <int D, int MODE>
 __global__ __launch_bounds__(kRowsBlock) void copy_rows_kernel(
@@ -376,6 +229,54 @@ __global__ __launch_bounds__(kRowsBlock) void copy_rows_kernel(
     else
       tags[d] = t;
   }
+}
+
+// ----------------------------------------------------------------------------------------
+// export: tile16 -> row-major fp16 (one thread per 8-half chunk)
+// ----------------------------------------------------------------------------------------
+template <int D>
+__global__ void export_kernel(const half8* __restrict__ corpus, int64_t row0, int64_t n,
+                              half8* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * (D / 8)) return;
+  const int64_t i = idx / (D / 8);
+  const int c = (int)(idx % (D / 8));
+  out[idx] = corpus[tile_slot<D>(row0 + i, c)];
+}
+
+// ----------------------------------------------------------------------------------------
+// import: row-major fp16 -> tile16, stored bits unchanged (persistence: loading a saved shard
+// must not renormalise already-normalised rows)
+// ----------------------------------------------------------------------------------------
+template <int D>
+__global__ void import_kernel(const half8* __restrict__ in, int64_t row0, int64_t n,
+                              half8* __restrict__ corpus) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * (D / 8)) return;
+  const int64_t i = idx / (D / 8);
+  const int c = (int)(idx % (D / 8));
+  corpus[tile_slot<D>(row0 + i, c)] = in[idx];
+}
+
+// import, fp32 storage: row-major fp32 rows (already normalised) -> rows32 unchanged and the
+// scan's fp16 tile16 copy by the same RNE conversion as upsert (f32_to_f16), so a reloaded
+// index is bit-identical to the one that was saved
+template <int D>
+__global__ void import32_kernel(const float* __restrict__ in, int64_t row0, int64_t n,
+                                half8* __restrict__ corpus, float* __restrict__ rows32) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * (D / 8)) return;
+  const int64_t i = idx / (D / 8);
+  const int c = (int)(idx % (D / 8));
+  const int64_t row = row0 + i;
+  const float* src = in + i * D + 8 * c;
+  half8 h;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    rows32[row * D + 8 * c + j] = src[j];
+    h[j] = f32_to_f16(src[j]);
+  }
+  corpus[tile_slot<D>(row, c)] = h;
 }
 
 }  // namespace ragmi

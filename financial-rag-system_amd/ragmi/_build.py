@@ -14,8 +14,10 @@ ARCH = "gfx950"
 
 # translation units of libragmi.so
 SOURCES = ["index_capi.hip", "bert_capi.hip", "wordpiece_capi.cpp"]
-HEADERS = ["device_common.hpp", "common_host.hpp", "scan_kernels.hip", "rows_kernels.hip",
-           "bert_kernels.hip"]
+# what they include: every other .hip / .hpp of csrc/ (derived, so that a new header counts
+# for needs_build() without being listed)
+HEADERS = sorted(f for f in os.listdir(CSRC)
+                 if f.endswith((".hip", ".hpp")) and f not in SOURCES)
 
 
 def _inputs():

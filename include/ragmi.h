@@ -68,7 +68,7 @@ enum {
  * queries: a sampled certified lower bound of each query's k-th best score, every row whose
  * MFMA score can reach it collected, all of those re-scored exactly, the k best by (score
  * desc, row asc) emitted — the same exact result and canonical scores as the k <= 32 path
- * (scan_kernels.hip, "Exact top-k for RAG_MAX_K < k"). rag_index_search_packed accepts k
+ * (largek_kernels.hip, "Exact top-k for RAG_MAX_K < k"). rag_index_search_packed accepts k
  * up to this. rag_index_search itself takes ANY k >= 1: k > RAG_MAX_K_LARGE runs the full
  * exact pass (rag_index_search_full, round 6), and rag_merge_topk[_packed] merge any k (past
  * this by three stable radix sorts per query). */

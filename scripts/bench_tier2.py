@@ -1,11 +1,11 @@
-"""Latency of the certificate's tier 2 (the rescan pass, csrc/scan_kernels.hip rescan_kernel)
+"""Latency of the certificate's tier 2 (the rescan pass, csrc/certify_kernels.hip rescan_kernel)
 on a duplicate-heavy corpus (measure it at 1.25M and 10M rows).
 
 Corpus: torch randn rows (GPU generator), every `every`-th row replaced by base + 1e-5 noise
 (near-duplicates of one vector: each scan wave's list overflows inside the MFMA error band,
 so tier 1 cannot certify). Batch of 32: M queries near `base` (tier 2; M = 4 by default, and
 16 / 32 with --marked) + 32 - M random (tier 0). Round 4: all marked queries of a pass share
-one rescan launch (csrc/scan_kernels.hip rescan_kernel).
+one rescan launch (csrc/certify_kernels.hip rescan_kernel).
 Reports the device time of one search call with and without the tier-2 queries, the tiers,
 and the ids of the tier-2 queries checked against an fp64 exact top-15 of the duplicate rows
 (the duplicates dominate every tier-2 query's top-15)."""

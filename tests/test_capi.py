@@ -141,6 +141,9 @@ def test_ring_kernels_launch_through_launch_fixed():
     assert "__launch_bounds__(kPipeBlock<CFG>, 1) void gemm_pipe_kernel" in kern
     assert "__launch_bounds__(kWsBlock<CFG>, 1) void gemm_ws_kernel" in kern
     scan = open(os.path.join(csrc, "scan_kernels.hip")).read()
-    for b, k in (("kScanBlock, 2", "scan_kernel"), ("kLdsBlock, 1", "scan_lds_kernel"),
-                 ("kWideBlock, 1", "scan_wide_kernel"), ("kScanBlock, 2", "rescan_kernel")):
-        assert f"__launch_bounds__({b}) void {k}(" in scan
+    certify = open(os.path.join(csrc, "certify_kernels.hip")).read()
+    for b, k, text in (("kScanBlock, 2", "scan_kernel", scan),
+                       ("kLdsBlock, 1", "scan_lds_kernel", scan),
+                       ("kWideBlock, 1", "scan_wide_kernel", scan),
+                       ("kScanBlock, 2", "rescan_kernel", certify)):
+        assert f"__launch_bounds__({b}) void {k}(" in text

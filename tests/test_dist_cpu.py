@@ -54,7 +54,7 @@ class OracleShard:
 
 
 def np_merge_packed(p, k):
-    """numpy restatement of merge_exact_kernel<PACKED> (csrc/scan_kernels.hip): the union of
+    """numpy restatement of merge_exact_kernel<PACKED> (csrc/merge_kernels.hip): the union of
     the gathered lists' valid entries (row >= 0), ordered by (score desc, row asc), first k."""
     p = p.numpy()
     W, B = p.shape[:2]

@@ -1,7 +1,7 @@
 """Exact top-k for RAG_MAX_K < k <= RAG_MAX_K_LARGE (round 5): Qdrant's
 query_points takes any `limit` (/root/reference/main.py:215,232-237), and under the unchanged
 reference a refused limit would be swallowed into empty points (main.py:238-239). The large-k
-pass (scan_kernels.hip lk_* kernels) must return exactly the oracle's top-k — ids AND scores
+pass (largek_kernels.hip lk_* kernels) must return exactly the oracle's top-k — ids AND scores
 bit for bit (oracle/scan_ref.c, canonical fp64 order), ties by row ascending — at D = 384 and
 1024, with and without payload filters, with padding where fewer than k rows match, on
 near-duplicate clusters whose scores sit inside the MFMA error band, and when a query's first

@@ -262,6 +262,35 @@ def test_serial_scan_order_across_streams(gpu, dim, b):
     idx.close()
 
 
+@pytest.mark.parametrize("dim,b,serial", [(384, 20, 0), (384, 20, 1), (1024, 20, 0), (1024, 70, 0)],
+                         ids=["384-fused", "384-serial", "1024-b20", "1024-b70"])
+def test_seed_sample_odd_tail(gpu, dim, b, serial):
+    """The seed sample's tail: 1000 rows are 63 tiles, all sampled, so n_sample is odd (the last
+    sample wave has one tile, not two) and the last tile holds 8 rows. A seed that is not a true
+    lower bound prunes rows silently, so the results must equal the oracle's bit for bit, with
+    half of the queries filtered to a tag that about 1 row in 10 carries. Seed paths: D = 384 in
+    free scan order (qprep fused into the sample launch) and in serial order (the separate
+    sample launch); D = 1024 with one query group and with three, the last one partial."""
+    rng = np.random.default_rng(1000 + dim + b + serial)
+    n, k = 1000, 15
+    x = rng.standard_normal((n, dim)).astype(np.float32)
+    tags = np.where(rng.random(n) < 0.1, 7, 1).astype(np.uint32)
+    q = rng.standard_normal((b, dim)).astype(np.float32)
+    filt = np.zeros((b, 2), np.uint32)
+    filt[1::2] = (0xFFFF, 7)                      # odd queries: tag 7 only; even: every row
+    idx = make_index(gpu, x, tags)
+    idx.set_scan_order(serial)
+    s, i = search(idx, q, k, filters=filt)
+    enc = O.encode_rows(x)
+    s0, i0 = O.search(enc, q[0::2], k)
+    s1, i1 = O.search(enc, q[1::2], k, tags=tags, mask=0xFFFF, value=7, use_filter=True)
+    np.testing.assert_array_equal(i[0::2], i0)
+    np.testing.assert_array_equal(s[0::2], s0)
+    np.testing.assert_array_equal(i[1::2], i1)
+    np.testing.assert_array_equal(s[1::2], s1)
+    idx.close()
+
+
 # ---- D = 1024 (config 5: bge-large vectors; queries in LDS, scan_lds_kernel)
 @pytest.mark.parametrize("n,b,k", [(5003, 32, 15), (4096, 128, 15), (777, 45, 16), (33, 3, 5)])
 def test_search_d1024_vs_oracle(gpu, n, b, k):
