@@ -28,6 +28,7 @@
 #include "largek_kernels.hip"
 #include "reselect_kernels.hip"
 #include "rows_kernels.hip"
+#include "filter_kernels.hip"
 
 #include <hipcub/hipcub.hpp>
 
@@ -93,12 +94,25 @@ struct ProfPair {
   hipEvent_t a, b;
 };
 
+// A filter view column (rag_index_search_view), bound to the stream of its last call as a
+// Workspace is: calls on one stream are ordered by the stream, so the next view kernel
+// overwrites the column only after the previous call's passes have read it (acquire_view)
+struct ViewSlot {
+  uint32_t* p = nullptr;
+  size_t bytes = 0;
+  hipStream_t owner = nullptr;
+  bool used = false;
+  uint64_t tick = 0;
+};
+
 // One search pass's share of a search call: at most one pass's queries, their filters and the
-// output rows they fill (out_packed, or out_s and out_i)
+// output rows they fill (out_packed, or out_s and out_i); `tags` is the tag column every kernel
+// of the pass filters on: the stored tags, or a filter view of them (rag_index_search_view)
 struct PassArgs {
   const float* q;
   int Bq, k;
   const uint32_t* filt;
+  const uint32_t* tags;
   int64_t id_offset;
   float* out_s;
   int64_t* out_i;
@@ -212,6 +226,8 @@ struct rag_index {
   std::mutex mu;
   Workspace ws[kRing];
   uint64_t ws_tick = 0;
+  ViewSlot views[kRing];          // filter view columns, allocated on first use per stream
+  uint64_t view_tick = 0;
   Workspace* last_ws = nullptr;   // workspace of the most recent search pass
   int last_bq = 0;                // its query count
   // host staging for *_host entry points
@@ -357,8 +373,10 @@ int sample_div() {
 
 template <int D, bool FILTER>
 void launch_seed(rag_index* h, Workspace& w, int groups, hipStream_t st,
-                 const float* q = nullptr, int Bq = 0, const uint32_t* filt_in = nullptr) {
+                 const float* q = nullptr, int Bq = 0, const uint32_t* filt_in = nullptr,
+                 const uint32_t* tags = nullptr) {
   using namespace ragmi;
+  if (!tags) tags = h->tags;
   const int n_tiles = (int)((h->count + 15) / 16);
   if (q) {     // fused: qprep inside the sample launch (also when there is nothing to sample)
     if constexpr (D <= 384) {
@@ -366,7 +384,7 @@ void launch_seed(rag_index* h, Workspace& w, int groups, hipStream_t st,
       const int n_sample = n_tiles == 0 ? 0 : std::min({n_tiles, std::max(256, n_tiles / div_f),
                                                         kMaxSample});
       qprep_sample_kernel<D, FILTER><<<dim3(std::max(1, (n_sample + 7) / 8)), dim3(256), 0, st>>>(
-          q, Bq, filt_in, w.qn, w.qfrag, w.filt, w.eps, store_eps(h), h->corpus, h->tags,
+          q, Bq, filt_in, w.qn, w.qfrag, w.filt, w.eps, store_eps(h), h->corpus, tags,
           (int)h->count, n_tiles, n_sample, w.smax);
       if (n_sample > 0)
         thresh_kernel<kMaxSample><<<dim3(kQ, 1), dim3(256), 0, st>>>(w.smax, n_sample, w.eps,
@@ -382,10 +400,10 @@ void launch_seed(rag_index* h, Workspace& w, int groups, hipStream_t st,
   const int n_sample = std::min({n_tiles, std::max(256, n_tiles / div), kCap});
   if constexpr (D > 384)   // every query group in one pass over each sample tile
     sample_wide_kernel<D, FILTER><<<dim3((n_sample + 7) / 8), dim3(256), 0, st>>>(
-        h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, n_tiles, n_sample, w.smax, groups);
+        h->corpus, tags, w.filt, w.qfrag, (int)h->count, n_tiles, n_sample, w.smax, groups);
   else
     sample_kernel<D, FILTER><<<dim3((n_sample + 7) / 8, groups), dim3(256), 0, st>>>(
-        h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, n_tiles, n_sample, w.smax);
+        h->corpus, tags, w.filt, w.qfrag, (int)h->count, n_tiles, n_sample, w.smax);
   thresh_kernel<kCap><<<dim3(kQ, groups), dim3(256), 0, st>>>(w.smax, n_sample, w.eps, w.seed);
 }
 
@@ -403,12 +421,14 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   // (10M rows: scan 0.76 vs 0.83 of the roofline, same qps, profiles/r03i_headline_prep_ab.jsonl)
   if (D <= 384 && groups == 1 && fused_prep() && h->serial_scans == 0) {
     with_filter(filt, [&](auto f) {
-      launch_seed<D, decltype(f)::value>(h, w, groups, st, a.q, Bq, filt);
+      launch_seed<D, decltype(f)::value>(h, w, groups, st, a.q, Bq, filt, a.tags);
     });
   } else {
     qprep_kernel<D><<<dim3(groups * kQ), dim3(64), 0, st>>>(a.q, Bq, filt, w.qn, w.qfrag, w.filt,
                                                             w.eps, store_eps(h));
-    with_filter(filt, [&](auto f) { launch_seed<D, decltype(f)::value>(h, w, groups, st); });
+    with_filter(filt, [&](auto f) {
+      launch_seed<D, decltype(f)::value>(h, w, groups, st, nullptr, 0, nullptr, a.tags);
+    });
   }
   const int64_t n_tiles = (h->count + 15) / 16;
   // D <= 384: queries in VGPRs, 2 workgroups per CU; wider rows: queries in LDS, 1 per CU,
@@ -476,7 +496,7 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   }
   // go(the arguments scan_kernel and scan_lds_kernel share, then `tail`)
   const auto with_scan_args = [&](auto&& go, auto... tail) {
-    return go(h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, (int)n_tiles, w.seed, w.part_s,
+    return go(h->corpus, a.tags, w.filt, w.qfrag, (int)h->count, (int)n_tiles, w.seed, w.part_s,
               w.part_i, w.heads_s, w.heads_i, w.heads_n, tail...);
   };
   const bool wide = kLdsQ && groups > 1 && !filt;
@@ -554,7 +574,7 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   // second pass over the shard) run inside the same launch
   with_filter(filt, [&](auto f) {
     select_kernel<D, decltype(f)::value><<<dim3(Bq), dim3(256), 0, st>>>(
-        w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, h->tags, w.filt,
+        w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, a.tags, w.filt,
         w.qfrag, (int)h->count, w.qn, a.k, w.eps, w.seed, fb, a.id_offset, a.out_s, a.out_i,
         a.out_packed, h->rows32);
   });
@@ -566,7 +586,7 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   if (R > 0) {
     with_filter(filt, [&](auto f) {
       launch_fixed<kScanBlock>(rescan_kernel<D, decltype(f)::value>, dim3(R), 0, st, w.fb_tier,
-                               w.t2, Bq, h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, w.qn,
+                               w.t2, Bq, h->corpus, a.tags, w.filt, w.qfrag, (int)h->count, w.qn,
                                a.k, w.eps, w.t2_s, w.t2_i, w.t2_tk, a.id_offset, a.out_s, a.out_i,
                                a.out_packed, h->rows32);
     });
@@ -642,7 +662,7 @@ int launch_full_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_t 
     with_filter(a.filt, [&](auto f) {
       constexpr bool F = decltype(f)::value;
       full_score_kernel<D, F><<<dim3(grid), dim3(256), 0, st>>>(
-          h->corpus, h->tags, F ? w.filt + 2 * j : nullptr, w.qn + (int64_t)j * D, n, h->rows32,
+          h->corpus, a.tags, F ? w.filt + 2 * j : nullptr, w.qn + (int64_t)j * D, n, h->rows32,
           k_in, v_in, n_match + j);
     });
     if (hipGetLastError() != hipSuccess ||
@@ -750,7 +770,7 @@ int launch_large_k_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream
   if (n_sample > 0)
     with_filter(filt, [&](auto f) {
       sample_kernel<D, decltype(f)::value><<<dim3((n_sample + 7) / 8, 1), dim3(256), 0, st>>>(
-          h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, n_tiles, n_sample, w.lk_smax);
+          h->corpus, a.tags, w.filt, w.qfrag, (int)h->count, n_tiles, n_sample, w.lk_smax);
     });
   lk_bound_kernel<<<dim3(Bq), dim3(256), 0, st>>>(w.lk_smax, n_sample, k, w.eps, w.lk_thr,
                                                   w.lk_cnt, w.lk_again, w.lk_need);
@@ -760,7 +780,7 @@ int launch_large_k_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream
   for (int r = 0; r < kLkRounds; ++r) {
     with_filter(filt, [&](auto f) {
       lk_collect_kernel<D, decltype(f)::value><<<dim3(cgrid), dim3(256), 0, st>>>(
-          h->corpus, h->tags, w.filt, w.qfrag, (int)h->count, n_tiles, Bq, w.lk_thr, w.lk_cnt,
+          h->corpus, a.tags, w.filt, w.qfrag, (int)h->count, n_tiles, Bq, w.lk_thr, w.lk_cnt,
           w.lk_cand, w.lk_again, w.lk_need, r);
     });
     lk_rescore_kernel<D><<<dim3(kLkCap / 256, Bq), dim3(256), 0, st>>>(
@@ -853,14 +873,24 @@ int upsert_locked(rag_index* h, const float* vecs, const int64_t* rows, const ui
 
 // full: the full exact path for every query (rag_index_search_full); it is also taken for
 // k > RAG_MAX_K_LARGE (unpacked output only: the exchange merge holds at most that many)
-int search_locked(rag_index* h, const float* q, int B, int k, const uint32_t* filt,
-                  int64_t id_offset, float* out_s, int64_t* out_i, int32_t* out_packed,
-                  hipStream_t st, bool full = false) {
+// the argument rules of every search entry point, checked before any HIP call
+int search_args(const float* q, int B, int k, const float* out_s, const int64_t* out_i,
+                const int32_t* out_packed) {
   if (B < 0 || (B > 0 && (!q || (!out_packed && (!out_s || !out_i)))))
     return ragmi::fail(RAG_EINVAL, "bad search args");
   if (k < 1) return ragmi::fail(RAG_ERANGE, "k must be >= 1");
   if (out_packed && k > RAG_MAX_K_LARGE)
     return ragmi::fail(RAG_ERANGE, "packed (exchange) search: k must be <= RAG_MAX_K_LARGE=4096");
+  return RAG_OK;
+}
+
+// tags: the column the passes filter on, the stored tags unless the caller evaluated a filter
+// view of them (search_view_locked)
+int search_locked(rag_index* h, const float* q, int B, int k, const uint32_t* filt,
+                  int64_t id_offset, float* out_s, int64_t* out_i, int32_t* out_packed,
+                  hipStream_t st, bool full = false, const uint32_t* tags = nullptr) {
+  if (const int rc = search_args(q, B, k, out_s, out_i, out_packed)) return rc;
+  if (!tags) tags = h->tags;
   full = full || k > RAG_MAX_K_LARGE;
   RAG_HIP(hipSetDevice(h->device));
   const bool large = k > RAG_MAX_K || full;
@@ -889,6 +919,7 @@ int search_locked(rag_index* h, const float* q, int B, int k, const uint32_t* fi
                      Bq,
                      k,
                      filt ? filt + 2 * b0 : nullptr,
+                     tags,
                      id_offset,
                      out_packed ? nullptr : out_s + (int64_t)b0 * k,
                      out_packed ? nullptr : out_i + (int64_t)b0 * k,
@@ -1197,6 +1228,8 @@ int rag_index_destroy(rag_index_t* h) {
   if (h->tags) (void)hipFree(h->tags);
   if (h->rows32) (void)hipFree(h->rows32);
   if (h->stage) (void)hipFree(h->stage);
+  for (auto& v : h->views)
+    if (v.p) (void)hipFree(v.p);
   delete h;
   return RAG_OK;
 }
@@ -1390,15 +1423,11 @@ int rag_index_export_tags(rag_index_t* h, int64_t row0, int64_t n, uint32_t* out
 
 // ---- row removal: select, move, gather, scatter (rows_kernels.hip) ----
 
-int rag_index_select_rows(rag_index_t* h, uint32_t tag_mask, uint32_t tag_value,
-                          int64_t* out_rows, int64_t cap, int64_t* out_n, void* stream) {
-  ragmi::clear_error();
-  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
-  if (!out_n || cap < 0 || (cap > 0 && !out_rows))
-    return ragmi::fail(RAG_EINVAL, "bad select args (out_n NULL, or cap > 0 without out_rows)");
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  std::lock_guard<std::mutex> lk(h->mu);
-  RAG_HIP(hipSetDevice(h->device));
+namespace {
+
+// the ordered select (count / prefix sum / emit) over tag column `tags` of h->count rows
+int select_locked(rag_index* h, const uint32_t* tags, uint32_t tag_mask, uint32_t tag_value,
+                  int64_t* out_rows, int64_t cap, int64_t* out_n, hipStream_t st) {
   const int64_t count = h->count;
   const int nb = (int)((count + ragmi::kSelChunk - 1) / ragmi::kSelChunk);
   if (nb == 0) {
@@ -1409,13 +1438,149 @@ int rag_index_select_rows(rag_index_t* h, uint32_t tag_mask, uint32_t tag_value,
   RAG_HIP(offsets.alloc((size_t)nb * sizeof(int64_t)));
   int64_t* const off = reinterpret_cast<int64_t*>(offsets.p);
   ragmi::select_count_kernel<<<dim3((unsigned)nb), dim3(ragmi::kSelBlock), 0, st>>>(
-      h->tags, count, tag_mask, tag_value, off);
+      tags, count, tag_mask, tag_value, off);
   ragmi::select_scan_kernel<<<dim3(1), dim3(ragmi::kSelScanBlock), 0, st>>>(off, nb, out_n);
   if (cap > 0)
     ragmi::select_emit_kernel<<<dim3((unsigned)nb), dim3(ragmi::kSelBlock), 0, st>>>(
-        h->tags, count, tag_mask, tag_value, off, out_rows, cap);
+        tags, count, tag_mask, tag_value, off, out_rows, cap);
   RAG_HIP(hipGetLastError());
   return RAG_OK;
+}
+
+// ---- filter views (filter_kernels.hip) ----
+
+// the blob rules of every *_view entry point, checked before any HIP call
+int view_args(const uint32_t* progs, int64_t words, int n_programs) {
+  if (!progs) return ragmi::fail(RAG_EINVAL, "filter view: the program blob is NULL");
+  if (n_programs < 1 || n_programs > RAG_FILTER_MAX_PROGRAMS)
+    return ragmi::fail(RAG_EINVAL, "filter view: n_programs must be in [1, RAG_FILTER_MAX_PROGRAMS=32]");
+  if (words < (int64_t)n_programs * RAG_FILTER_REC_WORDS || words > UINT32_MAX)
+    return ragmi::fail(RAG_EINVAL, "filter view: `words` is smaller than n_programs records of 41 "
+                                   "words (or not below 2^32)");
+  return RAG_OK;
+}
+
+// filter_view_kernel over the handle's cap_rows rows into `view` (>= cap_rows words)
+int launch_filter_view(rag_index* h, const uint32_t* progs, int64_t words, int n_programs,
+                       uint32_t* view, hipStream_t st) {
+  using namespace ragmi;
+  if (h->cap_rows == 0) return RAG_OK;
+  const int64_t chunks = (h->cap_rows + kFvBlock * 4 - 1) / (kFvBlock * 4);
+  const dim3 grid((unsigned)std::min<int64_t>(chunks, (int64_t)kFvWgPerCu * h->n_cu));
+  if (words <= kFvLdsWords)
+    filter_view_kernel<true><<<grid, dim3(kFvBlock), (size_t)words * 4, st>>>(
+        h->tags, h->count, h->cap_rows, progs, (uint32_t)words, n_programs, view);
+  else
+    filter_view_kernel<false><<<grid, dim3(kFvBlock),
+                                (size_t)n_programs * RAG_FILTER_REC_WORDS * 4, st>>>(
+        h->tags, h->count, h->cap_rows, progs, (uint32_t)words, n_programs, view);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// The view column of a call: a buffer kept per stream beside the workspace slots (ViewSlot), of
+// the stored tags' extent, grown when the capacity grew. A stream-ordered allocation per call
+// (as the full pass and the select take their scratch) was built and measured first: with view
+// searches back to back the call then waited ~0.25 ms on the host before its first kernel, at
+// 1M and at 10M rows alike, more than the whole 1M-row search. Kept buffers cost
+// 4 B per row of capacity per stream that ever sent a general filter, and no call has anything
+// to release, on any path. The slot of stream `st`, else an unused one; every slot bound to
+// another stream whose last call may still read its column: the device is drained once and the
+// least recently used slot rebound, as search_locked does for workspaces. hipFree waits for
+// the device, so a column is never freed under a pass that reads it.
+int acquire_view(rag_index* h, hipStream_t st, uint32_t** view) {
+  ViewSlot* lru = nullptr;
+  ViewSlot* sp = pick_slot(h->views, st, lru);
+  if (!sp) {
+    RAG_HIP(hipDeviceSynchronize());
+    sp = lru;
+  }
+  const size_t need = std::max<size_t>((size_t)h->cap_rows * 4, 16);
+  if (sp->bytes < need) {
+    if (sp->p) (void)hipFree(sp->p);
+    sp->p = nullptr;
+    sp->bytes = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&sp->p), need) != hipSuccess) {
+      (void)hipGetLastError();
+      sp->p = nullptr;
+      return ragmi::fail(RAG_ENOMEM, "hipMalloc(filter view) failed");
+    }
+    sp->bytes = need;
+  }
+  sp->used = true;
+  sp->owner = st;
+  sp->tick = ++h->view_tick;
+  *view = sp->p;
+  return RAG_OK;
+}
+
+}  // namespace
+
+int rag_index_select_rows(rag_index_t* h, uint32_t tag_mask, uint32_t tag_value,
+                          int64_t* out_rows, int64_t cap, int64_t* out_n, void* stream) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
+  if (!out_n || cap < 0 || (cap > 0 && !out_rows))
+    return ragmi::fail(RAG_EINVAL, "bad select args (out_n NULL, or cap > 0 without out_rows)");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  return select_locked(h, h->tags, tag_mask, tag_value, out_rows, cap, out_n, st);
+}
+
+int rag_index_filter_view(rag_index_t* h, const uint32_t* progs, int64_t words, int n_programs,
+                          uint32_t* out_view, void* stream) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
+  if (const int rc = view_args(progs, words, n_programs)) return rc;
+  if (!out_view || (reinterpret_cast<uintptr_t>(out_view) & 15))
+    return ragmi::fail(RAG_EINVAL, "filter view: out_view_dev is NULL or not 16-byte aligned");
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  return launch_filter_view(h, progs, words, n_programs, out_view,
+                            static_cast<hipStream_t>(stream));
+}
+
+int rag_index_search_view(rag_index_t* h, const float* q, int B, int k, const uint32_t* progs,
+                          int64_t words, int n_programs, const uint32_t* filters,
+                          int64_t id_offset, int flags, float* out_s, int64_t* out_i,
+                          int32_t* out_packed, void* stream) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
+  if (const int rc = view_args(progs, words, n_programs)) return rc;
+  if (flags & ~RAG_SEARCH_FULL) return ragmi::fail(RAG_EINVAL, "view search: unknown flags");
+  if (const int rc = search_args(q, B, k, out_s, out_i, out_packed)) return rc;
+  if (out_packed && (flags & RAG_SEARCH_FULL))
+    return ragmi::fail(RAG_EINVAL, "view search: the full exact pass has no packed form");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (out_packed && (id_offset < 0 || id_offset + h->count > INT32_MAX))
+    return ragmi::fail(RAG_ERANGE, "packed ids are int32: global rows must stay below 2^31");
+  if (B == 0) return RAG_OK;
+  RAG_HIP(hipSetDevice(h->device));
+  // view and search under this one hold of the lock: a delete moves rows (and their tags)
+  // under the same lock, so the view cannot disagree with the rows the passes read
+  uint32_t* v = nullptr;
+  if (const int rc = acquire_view(h, st, &v)) return rc;
+  if (const int rc = launch_filter_view(h, progs, words, n_programs, v, st)) return rc;
+  return search_locked(h, q, B, k, filters, id_offset, out_s, out_i, out_packed, st,
+                       (flags & RAG_SEARCH_FULL) != 0, v);
+}
+
+int rag_index_select_rows_view(rag_index_t* h, const uint32_t* progs, int64_t words,
+                               int64_t* out_rows, int64_t cap, int64_t* out_n, void* stream) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
+  if (const int rc = view_args(progs, words, 1)) return rc;
+  if (!out_n || cap < 0 || (cap > 0 && !out_rows))
+    return ragmi::fail(RAG_EINVAL, "bad select args (out_n NULL, or cap > 0 without out_rows)");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  uint32_t* v = nullptr;
+  if (const int rc = acquire_view(h, st, &v)) return rc;
+  if (const int rc = launch_filter_view(h, progs, words, 1, v, st)) return rc;
+  return select_locked(h, v, 1u, 1u, out_rows, cap, out_n, st);
 }
 
 int rag_index_move_rows(rag_index_t* h, const int64_t* src_rows, const int64_t* dst_rows,
@@ -1632,9 +1797,12 @@ static int set_ensure(SetSlot& sl, char** buf, size_t* have, size_t bytes) {
   return RAG_OK;
 }
 
+// progs (NULL: the plain search): the filter programs of a view search, `words` words for
+// n_programs programs, on the merge device like the filters
 static int shardset_search_locked(rag_shardset* set, const float* q, int B, int k, const uint32_t* filt,
                            bool full, float* out_s, int64_t* out_i, uint8_t* out_empty,
-                           hipStream_t st) {
+                           hipStream_t st, const uint32_t* progs = nullptr, int64_t words = 0,
+                           int n_programs = 0) {
   const int n = set->n;
   const bool packed = !full && k <= RAG_MAX_K_LARGE;
   // all slots busy: the least recently used one, after its `done` event (below)
@@ -1650,10 +1818,12 @@ static int shardset_search_locked(rag_shardset* set, const float* q, int B, int 
                                                              : ids_off + (size_t)n * bk * 8);
   if (rc) return rc;
   const size_t qb = up256((size_t)B * set->dim * 4), fb = up256((size_t)B * 8);
+  const size_t pb = progs ? up256((size_t)words * 4) : 0;   // a remote shard's copy of the blob
   for (int s = 0; s < n; ++s)
     if (set->shard[s]->device != set->dev0) {
       RAG_HIP(hipSetDevice(set->shard[s]->device));
-      rc = set_ensure(sl, &sl.remote[s], &sl.remote_bytes[s], qb + fb + up256(bk * 4) + bk * 8);
+      rc = set_ensure(sl, &sl.remote[s], &sl.remote_bytes[s],
+                      qb + fb + up256(bk * 4) + up256(bk * 8) + pb);
       if (rc) return rc;
     }
   RAG_HIP(hipSetDevice(set->dev0));
@@ -1683,6 +1853,12 @@ static int shardset_search_locked(rag_shardset* set, const float* q, int B, int 
         fs = reinterpret_cast<const uint32_t*>(r + qb);
       }
     }
+    const uint32_t* ps = progs;
+    if (remote && progs) {
+      char* const rp = r + qb + fb + up256(bk * 4) + up256(bk * 8);
+      RAG_HIP(hipMemcpyPeerAsync(rp, h->device, progs, set->dev0, (size_t)words * 4, ss));
+      ps = reinterpret_cast<const uint32_t*>(rp);
+    }
     int32_t* w_pk = remote ? reinterpret_cast<int32_t*>(r + qb + fb) : pk;
     float* w_os = remote ? reinterpret_cast<float*>(r + qb + fb) : os;
     int64_t* w_oi = remote ? reinterpret_cast<int64_t*>(r + qb + fb + up256(bk * 4)) : oi;
@@ -1690,6 +1866,10 @@ static int shardset_search_locked(rag_shardset* set, const float* q, int B, int 
       // nothing stored here yet (fewer rows than shards): an all -1 list
       if (packed) RAG_HIP(hipMemsetAsync(w_pk, 0xFF, bk * 8, ss));
       else RAG_HIP(hipMemsetAsync(w_oi, 0xFF, bk * 8, ss));
+    } else if (progs) {
+      rc = rag_index_search_view(h, qs, B, k, ps, words, n_programs, fs, 0,
+                                 full ? RAG_SEARCH_FULL : 0, w_os, w_oi, packed ? w_pk : nullptr,
+                                 ss);
     } else if (packed) {
       rc = rag_index_search_packed(h, qs, B, k, fs, 0, w_pk, ss);
     } else {
@@ -1822,6 +2002,34 @@ int rag_shardset_search(rag_shardset_t* set, const float* q, int B, int k, const
   if (rc) {
     // a search that failed half way: let what it already started on the shard streams finish,
     // so nothing of it still writes into the slot when the next search takes it
+    for (int s = 0; s < set->n; ++s) {
+      (void)hipSetDevice(set->dev[s]);
+      (void)hipStreamSynchronize(set->stream[s]);
+    }
+  }
+  return rc;
+}
+
+int rag_shardset_search_view(rag_shardset_t* set, const float* q, int B, int k,
+                             const uint32_t* progs, int64_t words, int n_programs,
+                             const uint32_t* filters, int flags, float* out_s, int64_t* out_i,
+                             uint8_t* out_empty, void* stream) {
+  ragmi::clear_error();
+  if (!set) return ragmi::fail(RAG_EINVAL, "shard set is NULL");
+  if (const int rc = view_args(progs, words, n_programs)) return rc;
+  if (k < 1) return ragmi::fail(RAG_EINVAL, "shard set search: k must be >= 1");
+  if (B < 0 || (B > 0 && (!q || !out_s || !out_i)) || (flags & ~RAG_SHARDSET_FULL))
+    return ragmi::fail(RAG_EINVAL, "bad shard set search args");
+  if (B == 0) return RAG_OK;
+  if ((int64_t)B * k > INT32_MAX)
+    return ragmi::fail(RAG_ERANGE, "shard set search: B * k too large");
+  DeviceGuard guard;
+  std::lock_guard<std::mutex> lk(set->mu);
+  const int rc = shardset_search_locked(set, q, B, k, filters, (flags & RAG_SHARDSET_FULL) != 0,
+                                        out_s, out_i, out_empty, static_cast<hipStream_t>(stream),
+                                        progs, words, n_programs);
+  if (rc) {
+    // as rag_shardset_search: what a failed search started on the shard streams finishes first
     for (int s = 0; s < set->n; ++s) {
       (void)hipSetDevice(set->dev[s]);
       (void)hipStreamSynchronize(set->stream[s]);

@@ -137,6 +137,16 @@ INDEX_API = {
     "rag_shardset_destroy": (ctypes.c_int, [c_vp]),
     "rag_shardset_search": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp,
                                            ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rag_index_filter_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int, c_vp,
+                                             c_vp]),
+    "rag_index_search_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp,
+                                             ctypes.c_int64, ctypes.c_int, c_vp, ctypes.c_int64,
+                                             ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rag_index_select_rows_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp,
+                                                  ctypes.c_int64, c_vp, c_vp]),
+    "rag_shardset_search_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp,
+                                                ctypes.c_int64, ctypes.c_int, c_vp, ctypes.c_int,
+                                                c_vp, c_vp, c_vp, c_vp]),
     "rag_bench_scan": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(ctypes.c_double)]),
     "rag_index_set_scan_order": (ctypes.c_int, [c_vp, ctypes.c_int]),

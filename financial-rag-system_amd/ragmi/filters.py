@@ -1,0 +1,280 @@
+"""Filter programs: Qdrant's filter algebra over the two tag fields, compiled for the GPU.
+
+`PayloadTags.compile` (ragmi.qdrant) knows one filter shape, Filter(must=[FieldCondition(key,
+match=MatchValue)]), and turns it into one (mask, value) pair. Everything else the tag can
+answer — `should`, `must_not`, `min_should`, MatchAny, MatchExcept, "is empty", nested filters —
+is compiled here into a PROGRAM: at most MAX_ATOMS atoms and a 256-bit truth table over them.
+filter_view_kernel (csrc/filter_kernels.hip) evaluates up to MAX_PROGRAMS programs against every
+row's tag in one streaming launch and writes a derived tag column, bit s = "the row passes
+program s"; the search then runs unchanged over that column with the ordinary per-query filter
+(1 << s, 1 << s) (the blob layout is include/ragmi.h's "Filter programs").
+
+Semantics (Qdrant's published filter rules; parity with a Qdrant server is unpinned, as for
+search, MMR and groups). The tag holds one 16-bit code per field, 0 = absent; "present" means
+code != 0. A point whose value is a list, a dict or None has code 0 (PayloadTags.code), so it
+counts as absent: IsEmpty is true for it and no match condition is.
+
+  Filter(must, should, must_not, min_should) matches iff
+    every `must` condition matches, and
+    `should` is empty / None or at least one `should` condition matches, and
+    no `must_not` condition matches, and
+    `min_should` is None or at least min_count of its conditions match.
+  Filter() matches every point.
+
+  FieldCondition(key, match=MatchValue(v))            present and equal to v
+  FieldCondition(key, match=MatchAny(any=[...]))      present and in the list ([] matches nothing)
+  FieldCondition(key, match=MatchExcept(except_=[]))  present and not in the list
+  IsEmptyCondition(is_empty=PayloadField(key))        code == 0
+  a nested Filter, to any depth
+
+A value that was never ingested is in no set. Refused with UnsupportedFilter, which names the
+cause: `range`, keys outside the collection's payload_tag_fields, any other condition or match
+class (HasId, IsNull, geo, text), and a filter that needs more than MAX_ATOMS distinct atoms.
+
+Atoms:
+  ("maskeq", mask, value)        (tag & mask) == value — the legacy filter form
+  ("inset", f, bitmap, nbits)    code_f(tag) < nbits and bit code_f of `bitmap` is set, where
+                                 code_f = (tag >> 16 f) & 0xFFFF and nbits = len(codebook_f) + 1
+                                 at compile time: a code at or past it is not a member
+A row passes iff bit idx of the table is set, idx = sum_i atom_i(tag) << i.
+
+Host-only, numpy-only. eval_view_np restates the kernel for the tests; nothing in the product
+calls it.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import qdrant_models as models
+
+MAX_ATOMS = 8          # RAG_FILTER_MAX_ATOMS
+MAX_PROGRAMS = 32      # RAG_FILTER_MAX_PROGRAMS
+REC_WORDS = 41         # RAG_FILTER_REC_WORDS: atom count, 8 table words, 8 atoms of 4 words
+ATOM_MASKEQ = 0        # RAG_FILTER_ATOM_MASKEQ
+ATOM_INSET = 1         # RAG_FILTER_ATOM_INSET
+
+
+class UnsupportedFilter(NotImplementedError):
+    pass
+
+
+@dataclass(frozen=True)
+class FilterProgram:
+    """atoms: a tuple of atom tuples (module docstring); table: the truth table as an int, bit
+    idx set = assignment idx passes. Hashable: equal programs share a view bit."""
+    atoms: tuple
+    table: int
+
+    @staticmethod
+    def maskeq(mask: int, value: int) -> "FilterProgram":
+        """The one-atom program of a legacy (mask, value) filter."""
+        return FilterProgram((("maskeq", int(mask), int(value)),), 0b10)
+
+    def passes(self, tag: int) -> bool:
+        idx = 0
+        for i, a in enumerate(self.atoms):
+            idx |= int(_atom(a, tag)) << i
+        return bool((self.table >> idx) & 1)
+
+
+def _atom(a, tag: int) -> bool:
+    if a[0] == "maskeq":
+        return (tag & a[1]) == a[2]
+    code = (tag >> (16 * a[1])) & 0xFFFF
+    return code < a[3] and bool((a[2] >> code) & 1)
+
+
+# ------------------------------------------------------------------ compile
+def _as_list(x) -> list:
+    if x is None:
+        return []
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
+class _Compiler:
+    """Walks a Filter into an expression over atom indices: True / False, ("atom", i),
+    ("not", e), ("and", [e]), ("or", [e]), ("atleast", n, [e])."""
+
+    def __init__(self, tags):
+        self.tags = tags
+        self.atoms: list = []
+
+    def atom(self, a):
+        if a not in self.atoms:
+            self.atoms.append(a)
+        return ("atom", self.atoms.index(a))
+
+    def field(self, key) -> int:
+        if key not in self.tags.fields:
+            raise UnsupportedFilter(
+                f"payload key {key!r} is not an indexed keyword field {self.tags.fields}; "
+                "create the collection with payload_tag_fields")
+        return self.tags.fields.index(key)
+
+    def codes(self, f: int, values) -> int:
+        """Bitmap of the known codes of `values` (a never-ingested value is in no set)."""
+        bm = 0
+        for v in values:
+            c = self.tags.code(f, v, create=False)
+            if c:
+                bm |= 1 << c
+        return bm
+
+    def inset(self, f: int, bm: int):
+        return self.atom(("inset", f, bm, len(self.tags.codes[f]) + 1)) if bm else False
+
+    def condition(self, cond):
+        if isinstance(cond, models.Filter):
+            return self.filter(cond)
+        if isinstance(cond, models.IsEmptyCondition):
+            f = self.field(getattr(cond.is_empty, "key", cond.is_empty))
+            return self.atom(("maskeq", 0xFFFF << (16 * f), 0))
+        if not isinstance(cond, models.FieldCondition):
+            raise UnsupportedFilter(
+                f"condition {type(cond).__name__} is not supported (FieldCondition with "
+                "MatchValue / MatchAny / MatchExcept, IsEmptyCondition and nested Filters are)")
+        if cond.range is not None:
+            raise UnsupportedFilter(f"`range` on {cond.key!r}: the tag holds keyword codes, not "
+                                    "numbers")
+        f = self.field(cond.key)
+        m = cond.match
+        fmask = 0xFFFF << (16 * f)
+        if isinstance(m, models.MatchValue):
+            c = self.tags.code(f, m.value, create=False)
+            return self.atom(("maskeq", fmask, c << (16 * f))) if c else False
+        if isinstance(m, models.MatchAny):
+            return self.inset(f, self.codes(f, _as_list(m.any)))
+        if isinstance(m, models.MatchExcept):
+            present = ("not", self.atom(("maskeq", fmask, 0)))
+            listed = self.inset(f, self.codes(f, _as_list(m.except_)))
+            return ("and", [present, ("not", listed)])
+        raise UnsupportedFilter(f"match {type(m).__name__} on {cond.key!r} is not supported "
+                                "(MatchValue, MatchAny and MatchExcept are)")
+
+    def filter(self, flt):
+        parts = [self.condition(c) for c in _as_list(flt.must)]
+        should = [self.condition(c) for c in _as_list(flt.should)]
+        if should:
+            parts.append(("or", should))
+        parts += [("not", self.condition(c)) for c in _as_list(flt.must_not)]
+        ms = flt.min_should
+        if ms is not None:
+            if not hasattr(ms, "conditions") or not hasattr(ms, "min_count"):
+                raise UnsupportedFilter("min_should must be a MinShould(conditions, min_count)")
+            parts.append(("atleast", int(ms.min_count),
+                          [self.condition(c) for c in _as_list(ms.conditions)]))
+        return ("and", parts)
+
+
+def _ev(e, idx: int) -> bool:
+    if e is True or e is False:
+        return e
+    op = e[0]
+    if op == "atom":
+        return bool((idx >> e[1]) & 1)
+    if op == "not":
+        return not _ev(e[1], idx)
+    if op == "and":
+        return all(_ev(x, idx) for x in e[1])
+    if op == "or":
+        return any(_ev(x, idx) for x in e[1])
+    return sum(_ev(x, idx) for x in e[2]) >= e[1]        # atleast
+
+
+def compile_program(tags, flt):
+    """A Filter over `tags` (a PayloadTags: .fields, .codes, .code) -> FilterProgram, or
+    (0, 0) when every point matches (also flt None), or None when nothing can."""
+    if flt is None:
+        return (0, 0)
+    if not isinstance(flt, models.Filter):
+        raise UnsupportedFilter(f"expected a Filter, got {type(flt).__name__}")
+    c = _Compiler(tags)
+    expr = c.filter(flt)
+    m = len(c.atoms)
+    if m > MAX_ATOMS:
+        raise UnsupportedFilter(f"the filter needs {m} distinct atoms (conditions on the tag); "
+                                f"a filter program holds at most {MAX_ATOMS}")
+    table = 0
+    for idx in range(1 << m):
+        if _ev(expr, idx):
+            table |= 1 << idx
+    if table == 0:
+        return None
+    if table == (1 << (1 << m)) - 1:
+        return (0, 0)
+    return FilterProgram(tuple(c.atoms), table)
+
+
+# ------------------------------------------------------------------ device blob
+def pack_view(programs) -> np.ndarray:
+    """The device blob of U <= MAX_PROGRAMS programs (uint32; include/ragmi.h "Filter
+    programs"): U records of REC_WORDS words, then the bitmap pool."""
+    programs = list(programs)
+    if not 1 <= len(programs) <= MAX_PROGRAMS:
+        raise ValueError(f"a view holds 1 to {MAX_PROGRAMS} programs")
+    rec = np.zeros((len(programs), REC_WORDS), np.uint32)
+    pool: list = []
+    where: dict = {}
+    base = len(programs) * REC_WORDS
+    for s, p in enumerate(programs):
+        if len(p.atoms) > MAX_ATOMS:
+            raise ValueError(f"a program holds at most {MAX_ATOMS} atoms")
+        rec[s, 0] = len(p.atoms)
+        for w in range(8):
+            rec[s, 1 + w] = (p.table >> (32 * w)) & 0xFFFFFFFF
+        for i, a in enumerate(p.atoms):
+            d = rec[s, 9 + 4 * i:13 + 4 * i]
+            if a[0] == "maskeq":
+                d[:] = (ATOM_MASKEQ, a[1] & 0xFFFFFFFF, a[2] & 0xFFFFFFFF, 0)
+            else:
+                _, f, bm, nbits = a
+                key = (bm, nbits)
+                if key not in where:       # equal bitmaps are stored once
+                    where[key] = base + len(pool)
+                    pool += [(bm >> (32 * w)) & 0xFFFFFFFF for w in range((nbits + 31) // 32)]
+                d[:] = (ATOM_INSET, f, where[key], nbits)
+    return np.concatenate([rec.reshape(-1), np.asarray(pool, np.uint32)]).astype(np.uint32)
+
+
+def view_programs(blob) -> int:
+    """How many programs a well-formed blob (pack_view's) holds: the records end where the
+    bitmap pool begins, at the smallest INSET offset, or at the blob's end without one."""
+    blob = np.asarray(blob, np.uint32).reshape(-1)
+    end, n = len(blob), 0
+    while (n + 1) * REC_WORDS <= end:
+        r = blob[n * REC_WORDS:(n + 1) * REC_WORDS]
+        for i in range(min(int(r[0]), MAX_ATOMS)):
+            if r[9 + 4 * i] == ATOM_INSET:
+                end = min(end, int(r[11 + 4 * i]))
+        n += 1
+    return n
+
+
+def eval_view_np(blob, tags, n_programs: int | None = None) -> np.ndarray:
+    """filter_view_kernel restated in numpy: view[r] = sum_s pass_s(tags[r]) << s. Follows the
+    kernel's guards: atom counts clamped to MAX_ATOMS, a bitmap word outside the blob reads as
+    "not a member"."""
+    blob = np.asarray(blob, np.uint32).reshape(-1)
+    t = np.asarray(tags, np.uint32).reshape(-1)
+    U = view_programs(blob) if n_programs is None else int(n_programs)
+    words = len(blob)
+    out = np.zeros(t.shape, np.uint32)
+    for s in range(U):
+        r = blob[s * REC_WORDS:(s + 1) * REC_WORDS]
+        idx = np.zeros(t.shape, np.uint32)
+        for i in range(min(int(r[0]), MAX_ATOMS)):
+            kind, p0, p1, p2 = (int(x) for x in r[9 + 4 * i:13 + 4 * i])
+            if kind == ATOM_INSET:
+                code = (t >> np.uint32(16 * (p0 & 1))) & np.uint32(0xFFFF)
+                w = p1 + (code >> np.uint32(5)).astype(np.int64)
+                ok = (code < p2) & (w < words)
+                bits = np.where(ok, blob[np.where(ok, w, 0)], 0).astype(np.uint32)
+                a = (bits >> (code & np.uint32(31))) & np.uint32(1)
+            else:
+                a = ((t & np.uint32(p0)) == np.uint32(p1)).astype(np.uint32)
+            idx |= a << np.uint32(i)
+        tw = r[1 + (idx >> np.uint32(5)).astype(np.int64)]
+        out |= ((tw >> (idx & np.uint32(31))) & np.uint32(1)) << np.uint32(s)
+    return out

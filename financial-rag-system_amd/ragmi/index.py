@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .filters import MAX_PROGRAMS, REC_WORDS, view_programs
 
 MAX_K = 32          # RAG_MAX_K in include/ragmi.h: the scan's certified top-k path
 MAX_K_LARGE = 4096  # RAG_MAX_K_LARGE: k in (32, 4096] takes the exact large-k pass; larger k
@@ -26,6 +27,7 @@ MMR_MAX_CANDIDATES = 1024   # RAG_MMR_MAX_CANDIDATES: the longest list rag_index
 GROUPS_MAX_CANDIDATES = 4096   # RAG_GROUPS_MAX_CANDIDATES: the longest list rag_group_select walks
 GROUPS_MAX = 1024              # RAG_GROUPS_MAX: groups per query
 GROUPS_MAX_CELLS = 4096        # RAG_GROUPS_MAX_CELLS: groups x hits per group
+SEARCH_FULL = 1     # RAG_SEARCH_FULL (rag_index_search_view)
 STORAGE = {"fp16": 0, "fp32": 1}   # RAG_STORE_FP16 / RAG_STORE_FP32
 CREATE_DIAGNOSTIC = 0x100          # RAG_CREATE_DIAGNOSTIC: honour the RAGMI_* A/B knobs
 
@@ -41,6 +43,26 @@ def _as_dev(x, dtype, device) -> torch.Tensor:
         t = torch.from_numpy(np.ascontiguousarray(np.asarray(x))).to(dtype=dtype)
         t = t.to(device=device, non_blocking=False)
     return t.contiguous()
+
+
+def view_blob(programs, n_programs, device):
+    """A filter-program blob (ragmi.filters.pack_view; a uint32 host array, or an int32 cuda
+    tensor already on `device`) as the *_view calls take it: (int32 cuda tensor, words, U).
+    `n_programs` None: read off the blob (filters.view_programs; host arrays only)."""
+    if isinstance(programs, torch.Tensor):
+        if n_programs is None:
+            raise ValueError("a device blob needs n_programs")
+        t = programs.to(device=device, dtype=torch.int32).contiguous().reshape(-1)
+    else:
+        a = np.ascontiguousarray(np.asarray(programs, dtype=np.uint32).reshape(-1))
+        if n_programs is None:
+            n_programs = view_programs(a)
+        t = torch.from_numpy(a.view(np.int32)).to(device)
+    U = int(n_programs)
+    if not 1 <= U <= MAX_PROGRAMS or t.numel() < U * REC_WORDS:
+        raise ValueError(f"a view blob holds 1 to {MAX_PROGRAMS} program records of "
+                         f"{REC_WORDS} words")
+    return t, t.numel(), U
 
 
 def per_query(x, B: int, dtype, what: str) -> np.ndarray:
@@ -173,11 +195,20 @@ class FlatIndex:
                 raise ValueError("filters must be [B, 2] (tag_mask, tag_value)")
         return q, B, f
 
-    def search_packed(self, queries, k: int, filters=None, id_offset: int = 0) -> torch.Tensor:
+    def search_packed(self, queries, k: int, filters=None, id_offset: int = 0,
+                      programs=None, n_programs: int | None = None) -> torch.Tensor:
         """Top-k in the multi-GPU exchange form: int32 [B, k, 2] = (fp32 score bits, global
-        row; -1 = none), enqueued on the current stream (rag_index_search_packed)."""
+        row; -1 = none), enqueued on the current stream (rag_index_search_packed).
+        `programs`: as in search."""
         q, B, f = self._search_args(queries, k, filters, k_max=MAX_K_LARGE)
         out = torch.empty((B, k, 2), dtype=torch.int32, device=self.device)
+        if programs is not None:
+            p, words, U = view_blob(programs, n_programs, self.device)
+            check(self._L.rag_index_search_view(
+                self._h, q.data_ptr(), B, int(k), p.data_ptr(), words, U,
+                f.data_ptr() if f is not None else None, int(id_offset), 0, None, None,
+                out.data_ptr(), _stream_ptr(self.device)))
+            return out
         check(self._L.rag_index_search_packed(self._h, q.data_ptr(), B, int(k),
                                               f.data_ptr() if f is not None else None,
                                               int(id_offset), out.data_ptr(),
@@ -185,20 +216,32 @@ class FlatIndex:
         return out
 
     def search(self, queries, k: int, filters=None, id_offset: int = 0,
-               out: tuple[torch.Tensor, torch.Tensor] | None = None, full: bool = False):
+               out: tuple[torch.Tensor, torch.Tensor] | None = None, full: bool = False,
+               programs=None, n_programs: int | None = None):
         """Top-k of each query row. Returns (scores fp32 [B,k], ids int64 [B,k]) as cuda
         tensors, enqueued on the current stream (ids -1 where fewer than k rows match).
         `filters`: None, or per-query (tag_mask, tag_value) pairs [B, 2] (uint32).
         Any k >= 1: k <= 32 on the scan, k <= 4096 on the large-k pass, beyond on the full
         exact pass (every row scored exactly, then sorted); full=True forces the full pass
         (rag_index_search_full) — the same result, the path for queries a large-k pass left
-        unanswered."""
+        unanswered.
+        `programs`: a filter-program blob (ragmi.filters.pack_view). The search then runs over
+        the blob's filter view of the tags (rag_index_search_view) and `filters` are (mask,
+        value) pairs over the VIEW's bits: (1 << s, 1 << s) asks for program s."""
         q, B, f = self._search_args(queries, k, filters)
         if out is None:
             out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
             out_i = torch.empty((B, k), dtype=torch.int64, device=self.device)
         else:
             out_s, out_i = out
+        if programs is not None:
+            p, words, U = view_blob(programs, n_programs, self.device)
+            check(self._L.rag_index_search_view(
+                self._h, q.data_ptr(), B, int(k), p.data_ptr(), words, U,
+                f.data_ptr() if f is not None else None, int(id_offset),
+                SEARCH_FULL if full else 0, out_s.data_ptr(), out_i.data_ptr(), None,
+                _stream_ptr(self.device)))
+            return out_s, out_i
         fn = self._L.rag_index_search_full if full else self._L.rag_index_search
         check(fn(self._h, q.data_ptr(), B, int(k),
                  f.data_ptr() if f is not None else None,
@@ -305,6 +348,40 @@ class FlatIndex:
                                             int(tag_value) & 0xFFFFFFFF,
                                             out.data_ptr() if cap else None, cap, n.data_ptr(),
                                             _stream_ptr(self.device)))
+        total = int(n.item())
+        return out[:min(total, cap)], total
+
+    def filter_view(self, programs, n_programs: int | None = None,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+        """The filter view of the stored tags (rag_index_filter_view): an int32 cuda tensor
+        [capacity] holding the uint32 words, bit s of word r = row r passes program s of the
+        blob, 0 for rows at or past the count. `out`: a contiguous int32 tensor of at least
+        `capacity` elements to write into. Enqueued on the current stream."""
+        p, words, U = view_blob(programs, n_programs, self.device)
+        cap = self.capacity
+        if out is None:
+            out = torch.empty((cap,), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.device != self.device or out.numel() < cap \
+                or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int32 tensor of >= capacity elements on "
+                             "the index's device")
+        check(self._L.rag_index_filter_view(self._h, p.data_ptr(), words, U, out.data_ptr(),
+                                            _stream_ptr(self.device)))
+        return out[:cap]
+
+    def select_rows_view(self, programs, cap: int | None = None):
+        """select_rows of the rows passing ONE filter program (the blob's first record;
+        rag_index_select_rows_view): (rows int64 cuda tensor, total). Synchronises the current
+        stream (the total is read back)."""
+        p, words, _ = view_blob(programs, 1, self.device)
+        cap = self.count if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("cap must be >= 0")
+        out = torch.empty((cap,), dtype=torch.int64, device=self.device)
+        n = torch.empty((1,), dtype=torch.int64, device=self.device)
+        check(self._L.rag_index_select_rows_view(self._h, p.data_ptr(), words,
+                                                 out.data_ptr() if cap else None, cap,
+                                                 n.data_ptr(), _stream_ptr(self.device)))
         total = int(n.item())
         return out[:min(total, cap)], total
 

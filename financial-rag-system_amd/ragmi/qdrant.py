@@ -33,6 +33,7 @@ import torch
 
 from . import groups
 from . import qdrant_models as models
+from .filters import MAX_PROGRAMS, FilterProgram, UnsupportedFilter, compile_program, pack_view
 from .index import GROUPS_MAX, GROUPS_MAX_CELLS, MAX_K, MMR_MAX_CANDIDATES, FlatIndex
 from .shardset import ShardSet, parse_devices
 
@@ -53,10 +54,6 @@ def _norm_id(pid):
     if isinstance(pid, str):
         return str(uuid.UUID(pid))
     raise ValueError(f"unsupported point id type {type(pid)!r}")
-
-
-class UnsupportedFilter(NotImplementedError):
-    pass
 
 
 class PayloadTags:
@@ -290,7 +287,33 @@ class Collection:
                                    search=self.search_points)
 
     def compile_filter(self, flt):
-        return self.tags.compile(flt)
+        """A Filter as the searches take it: the (mask, value) pair of PayloadTags.compile for
+        every filter it accepts (today's path, untouched), else a FilterProgram
+        (ragmi.filters.compile_program: should, must_not, min_should, MatchAny, MatchExcept,
+        is-empty, nested filters); None when nothing can match. A filter neither accepts is
+        refused with the general compiler's message, which names the cause. A filter with
+        `min_should` goes to the general compiler at once: PayloadTags.compile never looked
+        at that clause."""
+        if getattr(flt, "min_should", None) is not None:
+            return compile_program(self.tags, flt)
+        try:
+            return self.tags.compile(flt)
+        except UnsupportedFilter:
+            return compile_program(self.tags, flt)
+
+    def _legacy_only(self, flt, what: str):
+        """PayloadTags.compile for a route that takes no general filter yet: its refusal says
+        that the route is the reason when the filter algebra would have accepted the filter."""
+        try:
+            if getattr(flt, "min_should", None) is not None:
+                raise UnsupportedFilter("min_should is not a `must` condition")
+            return self.tags.compile(flt)
+        except UnsupportedFilter as e:
+            compile_program(self.tags, flt)        # refused by both: the general message
+            raise UnsupportedFilter(
+                f"{what} takes only Filter(must=[FieldCondition(key, match=MatchValue)]); "
+                f"general filters (should, must_not, MatchAny, ...) are out of scope here: {e}"
+            ) from e
 
     # ---------------------------------------------------------------- writes
     def upsert(self, ids: list, vectors, payloads: list) -> int:
@@ -338,7 +361,8 @@ class Collection:
         and version. Returns the operation id. The device work has finished on return."""
         kind, what = parse_selector(points_selector)
         with self.lock:
-            flt = self.tags.compile(what) if kind == "filter" else None   # may refuse the filter
+            # may refuse the filter
+            flt = self._legacy_only(what, "Collection.delete") if kind == "filter" else None
             self.op += 1
             if kind == "ids":
                 found = {self.id_to_row[pid] for pid in what if pid in self.id_to_row}
@@ -373,11 +397,13 @@ class Collection:
     def count_matching(self, flt) -> int:
         """Points a Filter matches, counted on the device (select_rows with cap = 0)."""
         with self.lock:
-            c = self.tags.compile(flt)
+            c = self.compile_filter(flt)
             if c is None or not self.row_ids:
                 return 0
             if c == (0, 0):
                 return len(self.row_ids)
+            if isinstance(c, FilterProgram):
+                return self.index.select_rows_view(pack_view([c]), cap=0)[1]
             return self.index.select_rows(c[0], c[1], cap=0)[1]
 
     def search_points(self, queries, limit: int, filters: list, with_vectors=False):
@@ -403,13 +429,62 @@ class Collection:
             out = [[] for _ in range(B)]
             if not live or self.index.count == 0:
                 return out
-            q, use = self._live_queries(queries, filters, live)
-            s, ids = self._exact_lists(q, k, use)
+            s, ids = self._lists(queries, filters, live, k)
             s = s.cpu().numpy()
             ids = ids.cpu().numpy()
             for j, i in enumerate(live):
                 out[i] = [(int(r), float(sc)) for r, sc in zip(ids[j], s[j]) if r >= 0]
             return out
+
+    def _lists(self, queries, filters: list, live: list, k: int):
+        """The exact top-k lists of the `live` requests. Every live filter a (mask, value)
+        pair: the path of every release so far, unchanged. Otherwise the view path
+        (_view_lists)."""
+        if not any(isinstance(filters[i], FilterProgram) for i in live):
+            q, use = self._live_queries(queries, filters, live)
+            return self._exact_lists(q, k, use)
+        return self._view_lists(queries, filters, live, k)
+
+    def _view_lists(self, queries, filters: list, live: list, k: int):
+        """_lists with general filters among the live ones: the batch's distinct programs
+        share view bits (a (mask, value) pair rides as its one-atom MASKEQ program; (0, 0)
+        needs no bit, over any view it passes every row), every query gets the filter
+        (1 << slot, 1 << slot), and one view search answers the batch. More than MAX_PROGRAMS
+        distinct programs: the queries are dealt into calls of at most that many, each query
+        into the first call that knows its program or has a free bit, and the results are
+        scattered back."""
+        q = queries if isinstance(queries, torch.Tensor) else np.asarray(queries, np.float32)
+        q = q[live] if len(live) != len(filters) else q
+        calls: list = []                       # (slots: {program: bit}, members, their filters)
+        for j, i in enumerate(live):
+            f = filters[i]
+            prog = (f if isinstance(f, FilterProgram) else
+                    None if tuple(f) == (0, 0) else FilterProgram.maskeq(*f))
+            for slots, members, fl in calls:
+                if prog is None or prog in slots or len(slots) < MAX_PROGRAMS:
+                    break
+            else:
+                slots, members, fl = {}, [], []
+                calls.append((slots, members, fl))
+            bit = 0 if prog is None else 1 << slots.setdefault(prog, len(slots))
+            members.append(j)
+            fl.append((bit, bit))
+        s = ids = None
+        for slots, members, fl in calls:
+            # every call holds a program: a call is opened for a query that brings one, except
+            # the first, and a batch without any program never comes here
+            blob = pack_view(list(slots))
+            use = np.asarray(fl, dtype=np.uint32).reshape(-1, 2)
+            if len(calls) == 1:
+                return self._exact_lists(q, k, use, programs=blob)
+            s1, i1 = self._exact_lists(q[members], k, use, programs=blob)
+            if s is None:
+                s = torch.empty((len(live), k), dtype=s1.dtype, device=s1.device)
+                ids = torch.empty((len(live), k), dtype=i1.dtype, device=i1.device)
+            sel = torch.as_tensor(members, device=s1.device)
+            s[sel] = s1
+            ids[sel] = i1
+        return s, ids
 
     @staticmethod
     def _live_queries(queries, filters: list, live: list):
@@ -420,19 +495,22 @@ class Collection:
         fl = np.asarray([filters[i] for i in live], dtype=np.uint32).reshape(-1, 2)
         return q, (fl if fl.any() else None)
 
-    def _exact_lists(self, q, k: int, use):
+    def _exact_lists(self, q, k: int, use, programs=None):
         """The exact top-k lists (scores, rows) of queries `q`, as the index's tensors, with
         every query a large-k pass left unanswered re-answered on the full exact pass. What
-        search reports and what the MMR path re-selects from. Called under the lock."""
+        search reports and what the MMR path re-selects from. Called under the lock.
+        `programs`: a filter-program blob; `use` then indexes the bits of its view, and the
+        re-run takes the same blob."""
+        view = {} if programs is None else {"programs": programs}
         if isinstance(self.index, ShardSet):
             # a shard that left a query unanswered hands the merge an all -1 list, which
             # the merged top-k does not show: the set reads its per-shard flags and
             # re-answers those queries itself (ShardSet.search, rescue)
             before = self.index.rescued
-            s, ids = self.index.search(q, k, filters=use, rescue=True)
+            s, ids = self.index.search(q, k, filters=use, rescue=True, **view)
             self.rescued += self.index.rescued - before
             return s, ids
-        s, ids = self.index.search(q, k, filters=use)
+        s, ids = self.index.search(q, k, filters=use, **view)
         short = (ids < 0).any(dim=1)
         if bool(short.any()):
             # a -1 is padding (fewer matching points than k) unless the pass left the
@@ -444,7 +522,7 @@ class Collection:
             if n_un > self._unanswered:
                 redo = torch.nonzero(short).reshape(-1).tolist()
                 s2, i2 = self.index.search(q[redo], k, filters=use[redo] if use is not None
-                                           else None, full=True)
+                                           else None, full=True, **view)
                 s[redo] = s2
                 ids[redo] = i2
                 self.rescued += len(redo)
@@ -469,8 +547,7 @@ class Collection:
             lim = [int(limits[i]) for i in live]
             C = int(ncand.max())
             k = min(max(lim), C)
-            q, use = self._live_queries(queries, filters, live)
-            s, ids = self._exact_lists(q, C, use)
+            s, ids = self._lists(queries, filters, live, C)
             s, ids = self.index.mmr(s, ids, k, np.asarray([diversity[i] for i in live],
                                                           np.float32), ncand)
             s = s.cpu().numpy()
@@ -509,6 +586,12 @@ class Collection:
             count = self.index.count
             codes = self.tags.codes[f]
             live = [i for i, fl in enumerate(filters) if fl is not None]
+            if any(isinstance(filters[i], FilterProgram) for i in live):
+                raise UnsupportedFilter(
+                    "query_points_groups takes only Filter(must=[FieldCondition(key, "
+                    "match=MatchValue)]); a grouped search under a general filter (should, "
+                    "must_not, MatchAny, ...) is out of scope: its exactness ladder composes "
+                    "(mask, value) pairs")
             if limit < 1 or group_size < 1 or not live or count == 0 or not codes:
                 return out
             # neither clamp can change a result: there are no more groups than codes, no

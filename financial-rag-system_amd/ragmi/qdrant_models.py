@@ -64,10 +64,35 @@ class MatchAny:
 
 
 @dataclass
+class MatchExcept:
+    """The field is present and none of these values (Qdrant's `except`, a Python keyword:
+    the field is spelled `except_` as in qdrant_client)."""
+    except_: list
+
+
+@dataclass
 class FieldCondition:
     key: str
     match: Any = None
     range: Any = None
+
+
+@dataclass
+class PayloadField:
+    key: str
+
+
+@dataclass
+class IsEmptyCondition:
+    """The field is absent (or holds no scalar keyword value; ragmi.filters)."""
+    is_empty: PayloadField
+
+
+@dataclass
+class MinShould:
+    """Filter.min_should: at least `min_count` of `conditions` match."""
+    conditions: list
+    min_count: int
 
 
 @dataclass

@@ -115,11 +115,18 @@ class _Empty:
     points: list = []
 
 
+def _match(value):
+    """A string: the reference's MatchValue of its upper case; a list or tuple of strings (a
+    cross-company question, "10-K or 10-Q"): MatchAny of theirs."""
+    if isinstance(value, (list, tuple)):
+        return models.MatchAny(any=[v.upper() for v in value])
+    return models.MatchValue(value=value.upper())
+
+
 def _filter(ticker, document_type=None):
-    must = [models.FieldCondition(key="ticker", match=models.MatchValue(value=ticker.upper()))]
+    must = [models.FieldCondition(key="ticker", match=_match(ticker))]
     if document_type:
-        must.append(models.FieldCondition(key="document_type",
-                                          match=models.MatchValue(value=document_type.upper())))
+        must.append(models.FieldCondition(key="document_type", match=_match(document_type)))
     return models.Filter(must=must)
 
 

@@ -318,9 +318,24 @@ class ShardSet:
         merged = torch.sort(torch.cat(parts)).values
         return (merged if cap is None else merged[:int(cap)]), total
 
+    @_keeps_device
+    def select_rows_view(self, programs, cap: int | None = None):
+        """FlatIndex.select_rows_view over the set, merged as select_rows merges."""
+        parts, total = [], 0
+        for s, shard in enumerate(self.shards):
+            rows, n = shard.select_rows_view(programs, cap)
+            total += n
+            if rows.numel():
+                parts.append((rows * self.n + s).to(self.device))
+        if not parts:
+            return torch.empty((0,), dtype=torch.int64, device=self.device), total
+        merged = torch.sort(torch.cat(parts)).values
+        return (merged if cap is None else merged[:int(cap)]), total
+
     # ---------------------------------------------------------------- search
     @_keeps_device
-    def search(self, queries, k: int, filters=None, full: bool = False, rescue: bool = False):
+    def search(self, queries, k: int, filters=None, full: bool = False, rescue: bool = False,
+               programs=None, n_programs: int | None = None):
         """Top-k of each query over all shards: (scores fp32 [B, k], ids int64 [B, k], global
         rows, -1 where fewer than k rows match) on the merge device's current stream —
         FlatIndex.search's result on the same rows, bit for bit. full=True: every shard
@@ -328,15 +343,26 @@ class ShardSet:
         shards returned nothing per query; where such a shard's unanswered() rose, its
         large-k pass left the query unanswered and the merged top-k lacks that shard's rows,
         so those queries are re-run with full=True (counted once each in `rescued`).
-        Synchronises when rescue is set."""
+        Synchronises when rescue is set. `programs`: as FlatIndex.search — every shard
+        searches over the blob's filter view of its tags (rag_shardset_search_view), and the
+        rescue re-runs with the same blob."""
+        from .index import view_blob
         q, B, f = self.shards[0]._search_args(queries, k, filters)
         out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
         out_i = torch.empty((B, k), dtype=torch.int64, device=self.device)
         empty = torch.empty((self.n, B), dtype=torch.uint8, device=self.device)
-        check(self._L.rag_shardset_search(
-            self._h, q.data_ptr(), B, int(k), f.data_ptr() if f is not None else None,
-            SHARDSET_FULL if full else 0, out_s.data_ptr(), out_i.data_ptr(), empty.data_ptr(),
-            torch.cuda.current_stream(self.device).cuda_stream))
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        if programs is not None:
+            programs, words, n_programs = view_blob(programs, n_programs, self.device)
+            check(self._L.rag_shardset_search_view(
+                self._h, q.data_ptr(), B, int(k), programs.data_ptr(), words, n_programs,
+                f.data_ptr() if f is not None else None, SHARDSET_FULL if full else 0,
+                out_s.data_ptr(), out_i.data_ptr(), empty.data_ptr(), st))
+        else:
+            check(self._L.rag_shardset_search(
+                self._h, q.data_ptr(), B, int(k), f.data_ptr() if f is not None else None,
+                SHARDSET_FULL if full else 0, out_s.data_ptr(), out_i.data_ptr(),
+                empty.data_ptr(), st))
         if rescue and not full and B:
             e = empty.cpu().numpy().astype(bool)
             redo = np.zeros(B, bool)
@@ -347,7 +373,8 @@ class ShardSet:
                 self._unanswered[s] = n_un
             if redo.any():
                 sel = torch.as_tensor(np.nonzero(redo)[0], device=self.device)
-                s2, i2 = self.search(q[sel], k, f[sel] if f is not None else None, full=True)
+                s2, i2 = self.search(q[sel], k, f[sel] if f is not None else None, full=True,
+                                     programs=programs, n_programs=n_programs)
                 out_s[sel] = s2
                 out_i[sel] = i2
                 self.rescued += int(redo.sum())

@@ -342,6 +342,67 @@ int rag_shardset_search(rag_shardset_t* set, const float* queries_dev, int B, in
                         const uint32_t* filters_dev, int flags, float* out_scores_dev,
                         int64_t* out_ids_dev, uint8_t* out_empty_dev, void* stream);
 
+/* Filter programs (the filter algebra: should, must_not, min_should, MatchAny, MatchExcept,
+ * is-empty, nested filters; ragmi.filters compiles a Qdrant Filter into one). A program has at
+ * most RAG_FILTER_MAX_ATOMS atoms and a 256-bit truth table over them: a row passes iff bit
+ * idx of the table is set, idx = sum over atoms i of atom_i(tag) << i. Atom kinds:
+ *   RAG_FILTER_ATOM_MASKEQ (p0 = mask, p1 = value):  (tag & mask) == value
+ *   RAG_FILTER_ATOM_INSET  (p0 = field f, p1 = bitmap word offset, p2 = bitmap length in bits):
+ *       with code = (tag >> 16 f) & 0xFFFF: code < p2 and bit code of the bitmap is set
+ *       (bit b of a bitmap is bit b % 32 of its word b / 32).
+ * The device blob for U programs (uint32 words, `words` of them):
+ *   words [s * 41, (s + 1) * 41), s < U: program s's record —
+ *       [0]       atom count (read clamped to RAG_FILTER_MAX_ATOMS)
+ *       [1..8]    the truth table, bit idx = bit idx % 32 of word 1 + idx / 32
+ *       [9 + 4 i .. 12 + 4 i], i < 8: atom i = (kind, p0, p1, p2); unused atoms are zero
+ *   words [41 U, words): the bitmap pool; an INSET atom's p1 is a word offset from the blob's
+ *       start.
+ * The blob is never trusted: a bitmap word is read only when its index is < words (a code whose
+ * word lies outside is "not a member"), so a malformed blob gives wrong bits, never a read
+ * outside the blob.
+ *
+ * rag_index_filter_view: out_view_dev[r] (uint32 [capacity], 16-byte aligned, device) = sum
+ * over s < n_programs of pass_s(tag[r]) << s for r < count, 0 for count <= r < capacity; nothing
+ * past out_view_dev[capacity - 1] is written. One streaming launch: 4 B read and 4 B written per
+ * row.
+ * rag_index_search_view: rag_index_search over that view instead of the stored tags, under one
+ * hold of the handle's lock: filter_view_kernel runs once on `stream` ahead of the first pass
+ * into a view column the handle keeps per stream (4 B per row of capacity, allocated on a
+ * stream's first view call, freed with the handle), and every pass of the call reads that
+ * view. filters_dev [B][2] are ordinary
+ * (mask, value) pairs over the VIEW's bits: (1 << s, 1 << s) asks for program s, (0, 0) for
+ * every row; NULL = no query filters. flags: RAG_SEARCH_FULL forces the full exact pass.
+ * out_packed_dev non-NULL: the packed form of rag_index_search_packed (k <= RAG_MAX_K_LARGE,
+ * global rows below 2^31) and the two other outputs are ignored; NULL: out_scores_dev and
+ * out_ids_dev as rag_index_search writes them.
+ * rag_index_select_rows_view: rag_index_select_rows of the rows passing ONE program (the blob's
+ * first record).
+ * rag_shardset_search_view: rag_shardset_search with the view search on every shard; the blob
+ * travels to a shard on another device as the filters do.
+ * Argument errors (NULL blob, n_programs outside [1, RAG_FILTER_MAX_PROGRAMS], words < 41 *
+ * n_programs, the k / packed rules of the plain calls) are refused before any HIP call. All four
+ * are asynchronous on `stream`. */
+#define RAG_FILTER_MAX_ATOMS 8
+#define RAG_FILTER_MAX_PROGRAMS 32
+#define RAG_FILTER_REC_WORDS 41
+#define RAG_FILTER_ATOM_MASKEQ 0
+#define RAG_FILTER_ATOM_INSET 1
+#define RAG_SEARCH_FULL 1
+int rag_index_filter_view(rag_index_t* index, const uint32_t* progs_dev, int64_t words,
+                          int n_programs, uint32_t* out_view_dev, void* stream);
+int rag_index_search_view(rag_index_t* index, const float* queries_dev, int B, int k,
+                          const uint32_t* progs_dev, int64_t words, int n_programs,
+                          const uint32_t* filters_dev, int64_t id_offset, int flags,
+                          float* out_scores_dev, int64_t* out_ids_dev, int32_t* out_packed_dev,
+                          void* stream);
+int rag_index_select_rows_view(rag_index_t* index, const uint32_t* progs_dev, int64_t words,
+                               int64_t* out_rows_dev, int64_t cap, int64_t* out_n_dev,
+                               void* stream);
+int rag_shardset_search_view(rag_shardset_t* set, const float* queries_dev, int B, int k,
+                             const uint32_t* progs_dev, int64_t words, int n_programs,
+                             const uint32_t* filters_dev, int flags, float* out_scores_dev,
+                             int64_t* out_ids_dev, uint8_t* out_empty_dev, void* stream);
+
 /* Exactness bookkeeping (tests, bench): tier1 / tier2 = number of queries, since the index
  * was created, whose top-k was certified by the list re-scoring fallback / needed the second
  * pass over the shard (all other queries passed the error-bound check directly).

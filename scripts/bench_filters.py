@@ -1,0 +1,135 @@
+"""What a general filter costs next to the legacy (mask, value) filter it generalises.
+
+ROWS (default 1M) x 384 fp16 rows on a FlatIndex, the `--config filtered` corpus shape: 16
+ticker codes in the low 16 tag bits (row r: ticker r % 16), 3 document types in the high 16
+(row r: (r // 16) % 3), Gaussian rows, B = 32 queries (corpus rows plus noise), k = 15. In one
+process, alternating batch by batch after WARMUP (20) batches of each, ITERS (100) batches of
+each timed by a HIP event pair around the call:
+  a  legacy     32 distinct per-query (mask, value) filters on rag_index_search: query j < 16
+                ticker j, query j >= 16 ticker j - 16 and type 10-K — the path every release
+                so far has had
+  b  view       the same 32 filters as 32 distinct one-atom MASKEQ programs through
+                rag_index_search_view: filter_view_kernel, then the same passes over the view
+  c  any_not    per query MatchAny of 4 tickers + must_not on one document type: 32 distinct
+                2-atom programs
+  d  shared     (c) with all 32 queries sharing query 0's program (one view bit)
+  v  view_only  filter_view_kernel alone over (b)'s blob (rag_index_filter_view)
+One JSON line with the medians and ranges, to stdout and appended to --out (default
+profiles/filters_timing.jsonl). --kinds picks a subset; `--kinds a --pkg DIR` times the legacy
+path of ANOTHER checkout's package (the parent commit's, built in place), interleaved process
+by process with this one's, to show that the legacy path did not move.
+
+filter_view_kernel's own time comes from a separate run under a kernel trace, e.g.
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o filters -- \\
+      python scripts/bench_filters.py --iters 20 --kinds bcd --out /dev/null
+(DIR/**/filters_kernel_stats.csv: the filter_view_kernel rows)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+D, B, K, TICKERS, TYPES = 384, 32, 15, 16, 3
+CHUNK = 1 << 18
+
+
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def spread(t):
+    return [round(float(np.median(t)), 4), round(min(t), 4), round(max(t), 4)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--kinds", default="abcdv")
+    ap.add_argument("--pkg", default=os.path.join(ROOT, "financial-rag-system_amd"))
+    ap.add_argument("--label", default="this")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filters_timing.jsonl"))
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.pkg))
+    from ragmi.index import FlatIndex
+    dev = torch.device("cuda", 0)
+    idx = FlatIndex(D, args.rows, dev, storage="fp16")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1000)
+    q = None
+    for r0 in range(0, args.rows, CHUNK):
+        n = min(CHUNK, args.rows - r0)
+        rows = torch.arange(r0, r0 + n, device=dev)
+        x = torch.randn((n, D), generator=g, device=dev)
+        if q is None:
+            q = x[:B] + 0.05 * torch.randn((B, D), generator=g, device=dev)
+        tags = (rows % TICKERS + 1) | (((rows // TICKERS) % TYPES + 1) << 16)
+        idx.upsert(x, rows, tags.to(torch.int32), new_count=r0 + n)
+    torch.cuda.synchronize()
+    pairs = [(0xFFFF, 1 + j) if j < TICKERS else (0xFFFFFFFF, (1 + j - TICKERS) | (1 << 16))
+             for j in range(B)]
+    legacy = torch.from_numpy(np.array(pairs, np.uint32).view(np.int32)).to(dev)
+    runs = {}
+    if "a" in args.kinds:
+        runs["legacy"] = lambda: idx.search(q, K, legacy)
+    if set(args.kinds) & set("bcdv"):
+        from ragmi.filters import FilterProgram, pack_view
+        bit = lambda s: [1 << s, 1 << s]
+        own = torch.from_numpy(np.array([bit(j) for j in range(B)], np.uint32).view(np.int32)).to(dev)
+        one = torch.from_numpy(np.array([bit(0)] * B, np.uint32).view(np.int32)).to(dev)
+        as_dev = lambda blob: torch.from_numpy(blob.view(np.int32)).to(dev)
+        blob_b = as_dev(pack_view([FilterProgram.maskeq(m, v) for m, v in pairs]))
+
+        def any_not(j):       # ticker in {j, .., j + 3} (mod 16) and type != j % 3
+            bm = sum(1 << (1 + (j + i) % TICKERS) for i in range(4))
+            return FilterProgram((("inset", 0, bm, TICKERS + 1),
+                                  ("maskeq", 0xFFFF0000, (1 + j % TYPES) << 16)), 0b0010)
+
+        blob_c = as_dev(pack_view([any_not(j) for j in range(B)]))
+        blob_d = as_dev(pack_view([any_not(0)]))
+        if "b" in args.kinds:
+            runs["view"] = lambda: idx.search(q, K, own, programs=blob_b, n_programs=B)
+        if "c" in args.kinds:
+            runs["any_not"] = lambda: idx.search(q, K, own, programs=blob_c, n_programs=B)
+        if "d" in args.kinds:
+            runs["shared"] = lambda: idx.search(q, K, one, programs=blob_d, n_programs=1)
+        if "v" in args.kinds:
+            out = torch.empty((idx.capacity,), dtype=torch.int32, device=dev)
+            runs["view_only"] = lambda: idx.filter_view(blob_b, n_programs=B, out=out)
+    for _ in range(args.warmup):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in runs}
+    for _ in range(args.iters):
+        for name, fn in runs.items():
+            times[name].append(event_ms(fn))
+    rec = {"bench": "filters", "label": args.label, "rows": args.rows, "dim": D, "storage": "fp16",
+           "tickers": TICKERS, "types": TYPES, "B": B, "k": K, "warmup": args.warmup,
+           "iters": args.iters}
+    rec.update({f"{name}_ms_median_min_max": spread(t) for name, t in times.items()})
+    if "view" in times and "legacy" in times:
+        rec["view_minus_legacy_ms"] = round(float(np.median(times["view"]) -
+                                                  np.median(times["legacy"])), 4)
+    rec["device"] = torch.cuda.get_device_name(0)
+    line = json.dumps(rec)
+    print(line)
+    if args.out and args.out != os.devnull:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    idx.close()
+
+
+if __name__ == "__main__":
+    main()
