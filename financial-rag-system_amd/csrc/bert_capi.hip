@@ -15,7 +15,14 @@
 #include <vector>
 
 #include "../../include/ragmi_bert.h"
-#include "bert_kernels.hip"
+// the device layer, one header per stage of the forward, in dependency order
+#include "bert_device.hpp"
+#include "ln_kernels.hip"
+#include "gemm_kernels.hip"
+#include "gemm_ws_kernels.hip"
+#include "ffn_kernels.hip"
+#include "attn_kernels.hip"
+#include "head_kernels.hip"
 #include "common_host.hpp"
 
 namespace {
@@ -39,7 +46,7 @@ struct Layer {
   _Float16 *wqkv_l = nullptr, *wo_l = nullptr, *w1_l = nullptr, *w2_l = nullptr;  // fp16x3
   float *bqkv = nullptr, *bo = nullptr, *g1 = nullptr, *be1 = nullptr, *bi1 = nullptr,
         *bi2 = nullptr, *g2 = nullptr, *be2 = nullptr;
-  // deferred LayerNorm (fp16x3, hidden 384; DlArgs in bert_kernels.hip): the consumers of a
+  // deferred LayerNorm (fp16x3, hidden 384; DlArgs in gemm_ws_kernels.hip): the consumers of a
   // pending LN with its gamma folded into the weights — QKV (the previous layer's output LN;
   // layers >= 1) and FFN1 (this layer's attention-output LN) — and per output column c1 (the
   // folded planes' row sums) and c2 (bias + W beta)

@@ -6,7 +6,7 @@ Drop-ins for the two sentence-transformers objects the reference builds in its l
       (main.py:144-149 /embed, 211-213 embed_query; main2.py:170-171 embed_query_batch)
   get_reranker() -> CrossEncoder("cross-encoder/ms-marco-MiniLM-L-6-v2")  main.py:86-90
       .predict([[query, text], ...]) -> float32 [n]   (main.py:241-247 rerank_documents)
-The transformer forward runs in libragmi.so (csrc/bert_kernels.hip); tokenisation is host-side
+The transformer forward runs in libragmi.so (csrc/bert_capi.hip and the encoder headers it includes); tokenisation is host-side
 WordPiece (`tokenizers`) from the checkpoint's own vocab.txt. Models load from LOCAL
 directories in the HF layout (config.json + model.safetensors + vocab.txt): there is no hub
 access, and no CPU forward to fall back to.

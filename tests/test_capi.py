@@ -137,9 +137,10 @@ def test_ring_kernels_launch_through_launch_fixed():
         text = open(os.path.join(csrc, f)).read()
         for k in ring:
             assert re.search(rf"\b{k}<[^;]*?>\s*<<<", text) is None, f"{f}: {k} launched by hand"
-    kern = open(os.path.join(csrc, "bert_kernels.hip")).read()
-    assert "__launch_bounds__(kPipeBlock<CFG>, 1) void gemm_pipe_kernel" in kern
-    assert "__launch_bounds__(kWsBlock<CFG>, 1) void gemm_ws_kernel" in kern
+    pipe = open(os.path.join(csrc, "gemm_kernels.hip")).read()
+    ws = open(os.path.join(csrc, "gemm_ws_kernels.hip")).read()
+    assert "__launch_bounds__(kPipeBlock<CFG>, 1) void gemm_pipe_kernel" in pipe
+    assert "__launch_bounds__(kWsBlock<CFG>, 1) void gemm_ws_kernel" in ws
     scan = open(os.path.join(csrc, "scan_kernels.hip")).read()
     certify = open(os.path.join(csrc, "certify_kernels.hip")).read()
     for b, k, text in (("kScanBlock, 2", "scan_kernel", scan),

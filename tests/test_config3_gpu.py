@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 B, K, TOPK = 32, 15, 5
 # fp16x3 bounds tighter than north_star's 1e-3: measured 2.7e-5 / 3.8e-7 once hi and lo of
-# every split come from one fp32 value (bert_kernels.hip split16; 3.3e-4 before), so a
+# every split come from one fp32 value (bert_device.hpp split16; 3.3e-4 before), so a
 # regression to fp16-level rounding anywhere in the forward fails here
 TOL = {"fp16x3": dict(ce=1e-4, bge=5e-6), "fp16": dict(ce=2e-2, bge=2e-3)}
 

@@ -1,4 +1,4 @@
-"""GPU parity of the deferred LayerNorm (fp16x3, hidden 384): csrc/bert_kernels.hip DlArgs /
+"""GPU parity of the deferred LayerNorm (fp16x3, hidden 384): csrc/gemm_ws_kernels.hip DlArgs /
 ws_dl_epilogue, C entries rag_bert_gemm_dl and rag_encoder_set_defer_ln (ragmi_bert.h).
 
 The token rows' residual stream stays un-normalised between sublayers (z as fp16 hi + lo

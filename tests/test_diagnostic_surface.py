@@ -141,6 +141,6 @@ def test_diagnostic_instances_are_gated_in_the_sources():
     bert = _src("bert_capi.hip")
     assert _inside_diag(bert, bert.index("integral_constant<int, 106>"))
     # round 6: the fused FFN (measured slower) is diagnostic-build only, kernel and launch
-    kern = _src("bert_kernels.hip")
+    kern = _src("ffn_kernels.hip")
     for src, probe in ((kern, "void ffn_fused_kernel("), (bert, "launch_ffn_fused(w->xh")):
         assert _inside_diag(src, src.index(probe)), probe

@@ -1,4 +1,4 @@
-"""The fused deferred-LayerNorm FFN (round 6, VERDICT r5 item 1: bert_kernels.hip
+"""The fused deferred-LayerNorm FFN (round 6, VERDICT r5 item 1: ffn_kernels.hip
 ffn_fused_kernel, rag_encoder_set_ffn_fused): FFN1 + GELU + FFN2 + residual + LayerNorm
 statistics in one launch per layer, the 1536-wide intermediate kept on the CU.
 

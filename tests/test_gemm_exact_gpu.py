@@ -6,7 +6,7 @@ bias k/256) so every product and every partial sum is exactly representable in f
 result does not depend on the MFMA accumulation order, and each output element — its fp32
 value, its fp16 rounding and the fp16 lo plane fp16(v - fp16(v)) — is known exactly. A lane
 or fragment stored to the wrong place (e.g. a v_permlane16_swap pairing that misroutes some
-lanes of the 16-B fp16 stores, bert_kernels.hip store_f16_pair) shows up as a mismatch
+lanes of the 16-B fp16 stores, gemm_kernels.hip store_f16_pair) shows up as a mismatch
 regardless of any numerical tolerance.
 """
 import numpy as np

@@ -1,4 +1,4 @@
-"""GPU tests of the encoder GEMM kernels (csrc/bert_kernels.hip: gemm_kernel = TILE,
+"""GPU tests of the encoder GEMM kernels (csrc/gemm_kernels.hip, gemm_ws_kernels.hip: gemm_kernel = TILE,
 gemm_pipe_kernel<PipeSmall> = SMALL, gemm_ws_kernel = WS) through the C ABI diagnostic entry rag_bert_gemm, against a float64
 torch reference of the same nn.Linear (modeling_bert.py BertSelfAttention.query/key/value,
 BertSelfOutput.dense, BertIntermediate.dense + erf-GELU, BertOutput.dense).
