@@ -1690,6 +1690,34 @@ int rag_group_select(const float* cand_s, const int64_t* cand_r, const uint32_t*
   return RAG_OK;
 }
 
+// ---- fusion queries: reciprocal rank fusion of candidate lists (reselect_kernels.hip) ----
+
+int rag_fuse_rrf(const int64_t* cand_r, const int32_t* ncand, int B, int L, int C, int k,
+                 int rrf_k, float* out_s, int64_t* out_r, int32_t* out_count, void* stream) {
+  ragmi::clear_error();
+  static_assert(ragmi::kRrfMaxL == RAG_FUSION_MAX_LISTS &&
+                    ragmi::kRrfMaxE == RAG_FUSION_MAX_ENTRIES &&
+                    (ragmi::kRrfMaxE & (ragmi::kRrfMaxE - 1)) == 0 &&
+                    ragmi::kRrfMaxE % ragmi::kRrfBlock == 0,
+                "rrf_fuse_kernel's LDS arrays and its sort");
+  if (L < 1 || L > RAG_FUSION_MAX_LISTS)
+    return ragmi::fail(RAG_ERANGE, "fuse_rrf: L must be in [1, RAG_FUSION_MAX_LISTS=16]");
+  if (C < 1) return ragmi::fail(RAG_ERANGE, "fuse_rrf: C must be >= 1");
+  if ((int64_t)L * C > RAG_FUSION_MAX_ENTRIES)
+    return ragmi::fail(RAG_ERANGE, "fuse_rrf: L * C must be <= RAG_FUSION_MAX_ENTRIES=4096");
+  if (k < 1) return ragmi::fail(RAG_EINVAL, "fuse_rrf: k must be >= 1");
+  if (rrf_k < 1) return ragmi::fail(RAG_EINVAL, "fuse_rrf: rrf_k must be >= 1");
+  if (B < 0) return ragmi::fail(RAG_EINVAL, "fuse_rrf: B must be >= 0");
+  if (B > 0 && (!cand_r || !out_s || !out_r))
+    return ragmi::fail(RAG_EINVAL, "fuse_rrf: a NULL candidate or output pointer");
+  if (B == 0) return RAG_OK;
+  ragmi::rrf_fuse_kernel<<<dim3((unsigned)B), dim3(ragmi::kRrfBlock), 0,
+                           static_cast<hipStream_t>(stream)>>>(cand_r, ncand, L, C, k, rrf_k,
+                                                               out_s, out_r, out_count);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
 int rag_merge_topk(const float* in_s, const int64_t* in_i, int n_lists, int B, int k,
                    float* out_s, int64_t* out_i, void* stream) {
   ragmi::clear_error();

@@ -1,7 +1,8 @@
 // reselect_kernels.hip — re-selection from a query's exact candidate list (included by
 // index_capi.hip after certify_kernels.hip): mmr_kernel picks k diverse hits (rag_index_mmr),
-// group_select_kernel deals the list into groups by payload key (rag_group_select). Both take
-// one workgroup per query and read candidate lists, never the scan's state.
+// group_select_kernel deals the list into groups by payload key (rag_group_select),
+// rrf_fuse_kernel fuses a request's L lists by reciprocal rank (rag_fuse_rrf). All take one
+// workgroup per query and read candidate lists, never the scan's state.
 namespace ragmi {
 
 // ----------------------------------------------------------------------------------------
@@ -306,6 +307,130 @@ __global__ __launch_bounds__(kGrpBlock) void group_select_kernel(
     out_count[b * 2] = ng;
     out_count[b * 2 + 1] = n;
   }
+}
+
+// ----------------------------------------------------------------------------------------
+// reciprocal rank fusion (rag_fuse_rrf). One workgroup per request fuses its L
+// candidate lists of C rows each; it reads only its input arrays (no index). L * C <= kRrfMaxE.
+//   n[l]     = min(ncand[b][l] clamped to [0, C], leading entries of list l with row >= 0)
+//   entry e  = l * C + p is live iff p < n[l]; its contribution is 1.0 / (double)(rrf_k + p)
+//   fused(r) = (float) of the fp64 sum, from 0.0, of the contributions of the live entries
+//              holding r, in ascending e (= list ascending, position ascending)
+//   output   = the distinct rows by (fused descending, row ascending), the first k of them
+// The live entries sit in LDS as (row as uint64, e); a dead entry's row is ~0, above every
+// live one (rows are >= 0). A bitonic sort over N = the power of two >= L * C orders them by
+// (row, e), so the entries of a row are one run in summation order. The lane at a run's head
+// walks the run and adds in fp64; the results wait in registers past a barrier (the walks read
+// what the results overwrite), then the head's slot becomes (row, ~bits of the fused fp32) and
+// every other slot dead. The fused values are positive and finite, so ~bits ascending is the
+// value descending; a second bitonic sort by (~bits, row) leaves the result at the front.
+// The order is total over distinct rows, so the output is a pure function of the inputs:
+// integer LDS atomics only (min for n[l], add for the count of heads). Every output element
+// is written exactly once, in loops of kRrfBlock (C and k may both exceed the block).
+// ----------------------------------------------------------------------------------------
+constexpr int kRrfBlock = 512;
+constexpr int kRrfMaxL = 16;       // RAG_FUSION_MAX_LISTS
+constexpr int kRrfMaxE = 4096;     // RAG_FUSION_MAX_ENTRIES
+constexpr int kRrfPer = kRrfMaxE / kRrfBlock;   // slots per thread at the limit
+
+// N slots of (k64, k32), ascending by (k64, k32) if RowMajor else by (k32, k64). N is a power
+// of two >= 2; every thread of the block calls it. Ends on a barrier.
+template <bool RowMajor>
+__device__ __forceinline__ void rrf_bitonic(uint64_t* k64, uint32_t* k32, int N, int tid) {
+  for (int size = 2; size <= N; size <<= 1) {
+    for (int j = size >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (N >> 1); t += kRrfBlock) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const int hi = lo | j;
+        const uint64_t a64 = k64[lo], b64 = k64[hi];
+        const uint32_t a32 = k32[lo], b32 = k32[hi];
+        const bool gt = RowMajor ? (a64 > b64 || (a64 == b64 && a32 > b32))
+                                 : (a32 > b32 || (a32 == b32 && a64 > b64));
+        if (gt == ((lo & size) == 0)) {
+          k64[lo] = b64;
+          k64[hi] = a64;
+          k32[lo] = b32;
+          k32[hi] = a32;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__global__ __launch_bounds__(kRrfBlock) void rrf_fuse_kernel(
+    const int64_t* __restrict__ cand_r, const int32_t* __restrict__ ncand, int L, int C, int k,
+    int rrf_k, float* __restrict__ out_s, int64_t* __restrict__ out_r,
+    int32_t* __restrict__ out_count) {
+  __shared__ uint64_t s_row[kRrfMaxE];
+  __shared__ uint32_t s_aux[kRrfMaxE];   // e, then ~bits of the fused value
+  __shared__ int s_n[kRrfMaxL];
+  __shared__ int s_m;
+  constexpr uint64_t kDead = ~0ull;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int E = L * C;               // <= kRrfMaxE
+  int N = 2;
+  while (N < E) N <<= 1;             // <= kRrfMaxE
+  cand_r += b * E;
+
+  if (tid < L) s_n[tid] = ncand ? min(C, max(0, ncand[b * L + tid])) : C;
+  if (tid == 0) s_m = 0;
+  __syncthreads();
+  for (int e = tid; e < E; e += kRrfBlock) {
+    const int l = e / C, p = e - l * C;
+    if (cand_r[e] < 0) atomicMin(&s_n[l], p);   // a list ends at its first negative row
+  }
+  __syncthreads();
+  for (int e = tid; e < N; e += kRrfBlock) {
+    uint64_t r = kDead;
+    if (e < E) {
+      const int l = e / C, p = e - l * C;
+      if (p < s_n[l]) r = (uint64_t)cand_r[e];
+    }
+    s_row[e] = r;
+    s_aux[e] = (uint32_t)e;
+  }
+  __syncthreads();
+  rrf_bitonic<true>(s_row, s_aux, N, tid);
+
+  uint32_t fused[kRrfPer];           // ~bits for a run's head, ~0 for every other slot
+  int heads = 0;
+#pragma unroll
+  for (int u = 0; u < kRrfPer; ++u) {
+    const int i = tid + u * kRrfBlock;
+    fused[u] = ~0u;
+    if (i >= N) continue;
+    const uint64_t r = s_row[i];
+    if (r == kDead || (i > 0 && s_row[i - 1] == r)) continue;
+    double sum = 0.0;
+    for (int j = i; j < N && s_row[j] == r; ++j) {
+      const int e = (int)s_aux[j];
+      const int p = e - (e / C) * C;
+      sum += 1.0 / (double)((int64_t)rrf_k + p);
+    }
+    fused[u] = ~__float_as_uint((float)sum);
+    ++heads;
+  }
+  if (heads) atomicAdd(&s_m, heads);
+  __syncthreads();                   // every walk has read its run
+#pragma unroll
+  for (int u = 0; u < kRrfPer; ++u) {
+    const int i = tid + u * kRrfBlock;
+    if (i >= N) continue;
+    if (fused[u] == ~0u) s_row[i] = kDead;
+    s_aux[i] = fused[u];
+  }
+  __syncthreads();
+  rrf_bitonic<false>(s_row, s_aux, N, tid);
+
+  const int m = s_m;                 // distinct rows, <= E <= N
+  for (int t = tid; t < k; t += kRrfBlock) {
+    const bool live = t < m;
+    out_s[b * k + t] = live ? __uint_as_float(~s_aux[t]) : kNegInf;
+    out_r[b * k + t] = live ? (int64_t)s_row[t] : -1;
+  }
+  if (out_count && tid == 0) out_count[b] = m;
 }
 
 }  // namespace ragmi

@@ -125,6 +125,8 @@ INDEX_API = {
     "rag_group_select": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                         c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rag_fuse_rrf": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
     "rag_merge_topk": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       c_vp, c_vp, c_vp]),
     "rag_merge_topk_packed": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

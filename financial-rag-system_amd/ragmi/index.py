@@ -27,6 +27,8 @@ MMR_MAX_CANDIDATES = 1024   # RAG_MMR_MAX_CANDIDATES: the longest list rag_index
 GROUPS_MAX_CANDIDATES = 4096   # RAG_GROUPS_MAX_CANDIDATES: the longest list rag_group_select walks
 GROUPS_MAX = 1024              # RAG_GROUPS_MAX: groups per query
 GROUPS_MAX_CELLS = 4096        # RAG_GROUPS_MAX_CELLS: groups x hits per group
+FUSION_MAX_LISTS = 16          # RAG_FUSION_MAX_LISTS: lists per request rag_fuse_rrf fuses
+FUSION_MAX_ENTRIES = 4096      # RAG_FUSION_MAX_ENTRIES: lists x entries per list
 SEARCH_FULL = 1     # RAG_SEARCH_FULL (rag_index_search_view)
 STORAGE = {"fp16": 0, "fp32": 1}   # RAG_STORE_FP16 / RAG_STORE_FP32
 CREATE_DIAGNOSTIC = 0x100          # RAG_CREATE_DIAGNOSTIC: honour the RAGMI_* A/B knobs
@@ -687,6 +689,47 @@ def group_select_tags(cand_scores: torch.Tensor, cand_rows: torch.Tensor,
             out_r.data_ptr(), pos.data_ptr() if pos is not None else None, count.data_ptr(),
             _stream_ptr(dev)))
     return GroupSelection(keys, fill, out_s, out_r, count, pos)
+
+
+def fuse_rrf(cand_rows: torch.Tensor, k: int, rrf_k: int = 2, ncand=None,
+             with_count: bool = False):
+    """rag_fuse_rrf over candidate lists on one device (int64 [B, L, C], -1 = none): per request
+    the distinct rows of its L lists ordered by (fused reciprocal-rank score desc, row asc), the
+    first k of them — include/ragmi.h. `ncand`: None, or int32 values [B, L] (a host array or a
+    tensor on the lists' device). Returns (scores fp32 [B, k], rows int64 [B, k]) with -inf / -1
+    padding, and the distinct-row counts int32 [B] when `with_count`. Index-free; enqueued on
+    the current stream."""
+    if not isinstance(cand_rows, torch.Tensor) or cand_rows.dim() != 3:
+        raise ValueError("cand_rows must be a [B, L, C] tensor")
+    if cand_rows.dtype != torch.int64:
+        raise ValueError("cand_rows must be int64 rows")
+    dev = cand_rows.device
+    r = cand_rows.contiguous()
+    B, L, C = r.shape
+    k, rrf_k = int(k), int(rrf_k)
+    if not 1 <= L <= FUSION_MAX_LISTS:
+        raise ValueError(f"L must be in [1, {FUSION_MAX_LISTS}] lists")
+    if C < 1 or L * C > FUSION_MAX_ENTRIES:
+        raise ValueError(f"C must be >= 1 and L * C <= {FUSION_MAX_ENTRIES} entries")
+    if k < 1 or rrf_k < 1:
+        raise ValueError("k and rrf_k must be >= 1")
+    n = None
+    if ncand is not None:
+        if isinstance(ncand, torch.Tensor):
+            n = ncand.to(device=dev, dtype=torch.int32).contiguous()
+        else:
+            n = torch.from_numpy(np.ascontiguousarray(np.asarray(ncand, dtype=np.int32))).to(dev)
+        if n.shape != (B, L):
+            raise ValueError("ncand must be [B, L]")
+    out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out_r = torch.empty((B, k), dtype=torch.int64, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev) if with_count else None
+    with torch.cuda.device(dev):      # index-free: the launch goes to the current device
+        check(_lib.load().rag_fuse_rrf(
+            r.data_ptr(), n.data_ptr() if n is not None else None, B, L, C, k, rrf_k,
+            out_s.data_ptr(), out_r.data_ptr(),
+            count.data_ptr() if count is not None else None, _stream_ptr(dev)))
+    return (out_s, out_r, count) if with_count else (out_s, out_r)
 
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int):

@@ -34,7 +34,8 @@ import torch
 from . import groups
 from . import qdrant_models as models
 from .filters import MAX_PROGRAMS, FilterProgram, UnsupportedFilter, compile_program, pack_view
-from .index import GROUPS_MAX, GROUPS_MAX_CELLS, MAX_K, MMR_MAX_CANDIDATES, FlatIndex
+from .index import (FUSION_MAX_ENTRIES, FUSION_MAX_LISTS, GROUPS_MAX, GROUPS_MAX_CELLS, MAX_K,
+                    MMR_MAX_CANDIDATES, FlatIndex, fuse_rrf)
 from .shardset import ShardSet, parse_devices
 
 DEFAULT_TAG_FIELDS = ("ticker", "document_type")
@@ -564,6 +565,70 @@ class Collection:
             return [[self.point(r, s, True, with_vectors) for r, s in h]
                     for h in self.search_mmr(queries, limits, filters, diversity, candidates)]
 
+    def search_fusion(self, requests: list):
+        """Fusion queries. `requests`: per request (rrf_k, [(vector, Filter or
+        None, limit), ...], limit), as fusion_params returns them. Every prefetch of every
+        request rides one batched search at C = the largest prefetch limit (clamped to the
+        collection's count); the lists are arranged [B, Lmax, C] on the device, each cut to
+        its own limit by ncand, and fused by rag_fuse_rrf in one launch per distinct rrf_k. A
+        prefetch whose filter can match nothing, or whose limit is < 1, is an empty list and
+        is not searched. Returns per request [(row, fused score)], best first."""
+        with self.lock:
+            out = [[] for _ in requests]
+            count = self.index.count
+            # every filter is compiled, so that a refusal does not depend on the limits
+            compiled = [[self.compile_filter(f) for _, f, _ in pres] for _, pres, _ in requests]
+            qs, filters, where = [], [], []          # the searched prefetches, flattened
+            for b, (_, pres, limit) in enumerate(requests):
+                if limit < 1 or count == 0:
+                    continue
+                for l, (vec, _, plim) in enumerate(pres):
+                    if compiled[b][l] is not None and plim >= 1:
+                        qs.append(vec)
+                        filters.append(compiled[b][l])
+                        where.append((b, l, min(plim, count)))
+            if not qs:
+                return out
+            live = sorted({b for b, _, _ in where})
+            slot = {b: j for j, b in enumerate(live)}
+            Lmax = max(len(requests[b][1]) for b in live)
+            C = max(n for _, _, n in where)
+            if Lmax * C > FUSION_MAX_ENTRIES:
+                raise ValueError(f"fusion: {Lmax} prefetches of up to {C} hits are {Lmax * C} "
+                                 f"entries; at most {FUSION_MAX_ENTRIES} (prefetches x the "
+                                 "largest prefetch limit) are fused")
+            _, ids = self._lists(_stack_queries(qs, self.dim), filters, list(range(len(qs))), C)
+            dev = ids.device
+            rows = torch.full((len(live), Lmax, C), -1, dtype=torch.int64, device=dev)
+            at = np.asarray([(slot[b], l) for b, l, _ in where], dtype=np.int64)
+            rows[torch.from_numpy(at[:, 0]).to(dev), torch.from_numpy(at[:, 1]).to(dev)] = ids
+            ncand = np.zeros((len(live), Lmax), dtype=np.int32)
+            ncand[at[:, 0], at[:, 1]] = [n for _, _, n in where]
+            lim = [int(requests[b][2]) for b in live]
+            k = min(max(lim), Lmax * C)
+            by_k: dict[int, list] = {}
+            for j, b in enumerate(live):
+                by_k.setdefault(requests[b][0], []).append(j)
+            for rrf_k, members in by_k.items():
+                if len(members) == len(live):
+                    s, r = fuse_rrf(rows, k, rrf_k, ncand)
+                else:
+                    sel = torch.as_tensor(members, device=dev)
+                    s, r = fuse_rrf(rows[sel], k, rrf_k, ncand[members])
+                s = s.cpu().numpy()
+                r = r.cpu().numpy()
+                for m, j in enumerate(members):
+                    out[live[j]] = [(int(x), float(sc)) for x, sc in zip(r[m], s[m])
+                                    if x >= 0][:lim[j]]
+            return out
+
+    def search_points_fusion(self, requests: list, with_vectors=False):
+        """search_fusion with every hit resolved to its ScoredPoint (score = the fused score)
+        under the same hold of the lock (see search_points)."""
+        with self.lock:
+            return [[self.point(r, s, True, with_vectors) for r, s in h]
+                    for h in self.search_fusion(requests)]
+
     def search_groups(self, queries, group_by: str, limit: int, group_size: int, filters: list,
                       with_vectors=False, candidates: int | None = None,
                       widen: int | None = None):
@@ -652,6 +717,86 @@ def mmr_params(mmr: models.Mmr, limit) -> tuple[float, int]:
         raise ValueError(f"MMR re-selects from at most {MMR_MAX_CANDIDATES} candidates "
                          f"(candidates_limit, or a limit above it): got {int(cand)}")
     return div, int(cand)
+
+
+RRF_K = 2                    # FusionQuery(Fusion.RRF), Rrf(k=None)
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+def is_fusion(query) -> bool:
+    """Whether a query argument asks for fusion of prefetched lists."""
+    return isinstance(query, (models.FusionQuery, models.RrfQuery))
+
+
+def fusion_params(query, prefetch, limit, query_filter=None):
+    """(rrf_k, [(vector, Filter or None, limit), ...]) of a fusion request — query a FusionQuery
+    or RrfQuery, prefetch a Prefetch or a list of them — or ValueError naming what is wrong or
+    not built: DBSF, nested prefetches, a prefetch without a plain nearest query, a nearest /
+    MMR query over prefetched candidates, a top-level filter."""
+    if not is_fusion(query):
+        raise ValueError("prefetch is only built for fusion: query must be FusionQuery(Fusion.RRF) "
+                         "or RrfQuery(Rrf(k)); re-scoring prefetched candidates with a nearest "
+                         "query is not built")
+    if isinstance(query, models.FusionQuery):
+        fusion = getattr(query.fusion, "value", query.fusion)
+        if fusion == models.Fusion.DBSF.value:
+            raise ValueError("Fusion.DBSF (distribution-based score fusion) is not built; "
+                             "use Fusion.RRF")
+        if fusion != models.Fusion.RRF.value:
+            raise ValueError(f"unknown fusion {query.fusion!r}: Fusion.RRF is the one built")
+        rrf_k = RRF_K
+    else:
+        rrf_k = getattr(query.rrf, "k", None)
+        if rrf_k is None:
+            rrf_k = RRF_K
+        elif not _is_int(rrf_k) or rrf_k < 1:
+            raise ValueError(f"Rrf.k must be an int >= 1, got {rrf_k!r}")
+    if query_filter is not None:
+        raise ValueError("a fusion query takes no top-level query_filter: the filter belongs on "
+                         "each Prefetch(filter=...)")
+    if not _is_int(limit):
+        raise ValueError("a fusion query needs an int limit")
+    if isinstance(prefetch, models.Prefetch):
+        prefetch = [prefetch]
+    if prefetch is None or len(prefetch) == 0:
+        raise ValueError("a fusion query needs prefetches to fuse: prefetch=[Prefetch(...), ...]")
+    if len(prefetch) > FUSION_MAX_LISTS:
+        raise ValueError(f"a fusion query fuses at most {FUSION_MAX_LISTS} prefetches, "
+                         f"got {len(prefetch)}")
+    out = []
+    for n, p in enumerate(prefetch):
+        if not isinstance(p, models.Prefetch):
+            raise ValueError(f"prefetch[{n}] is not a Prefetch")
+        if p.prefetch is not None:
+            raise ValueError(f"prefetch[{n}]: a nested Prefetch.prefetch is not built")
+        vec, mmr = nearest_of(p.query)
+        if vec is None or is_fusion(vec):
+            raise ValueError(f"prefetch[{n}] needs a query: a vector or a NearestQuery")
+        if mmr is not None:
+            raise ValueError(f"prefetch[{n}]: an MMR query (NearestQuery.mmr) inside a prefetch "
+                             "is not built")
+        if not _is_int(p.limit):
+            raise ValueError(f"prefetch[{n}] needs an int limit")
+        out.append((vec, p.filter, int(p.limit)))
+    return int(rrf_k), out
+
+
+def _stack_queries(qs: list, dim: int):
+    """Query vectors (lists, arrays, tensors) as one [n, dim] batch: a tensor when any of them
+    is one, else a float32 array."""
+    if any(isinstance(x, torch.Tensor) for x in qs):
+        dev = next(x.device for x in qs if isinstance(x, torch.Tensor))
+        Q = torch.stack([(x if isinstance(x, torch.Tensor) else
+                          torch.as_tensor(np.asarray(x, np.float32))).to(dev).reshape(-1)
+                         for x in qs])
+    else:
+        Q = np.stack([np.asarray(x, np.float32).reshape(-1) for x in qs])
+    if Q.shape[1] != dim:
+        raise ValueError(f"every query must be one {dim}-dim vector")
+    return Q
 
 
 def _payloads(points: list, with_payload) -> list:
@@ -793,8 +938,13 @@ class QdrantClient:
 
     def query_points(self, collection_name: str, query=None, limit: int = 10,
                      query_filter: models.Filter | None = None, with_payload=True,
-                     with_vectors=False, **kwargs) -> models.QueryResponse:
+                     with_vectors=False, prefetch=None, **kwargs) -> models.QueryResponse:
         col = self._col(collection_name)
+        if prefetch is not None or is_fusion(query):
+            # a fusion request never rides the coalescer: its prefetches are their own batch
+            rrf_k, pres = fusion_params(query, prefetch, limit, query_filter)
+            pts = col.search_points_fusion([(rrf_k, pres, int(limit))], with_vectors)[0]
+            return models.QueryResponse(points=_payloads(pts, with_payload))
         query, mmr = nearest_of(query)
         flt = col.compile_filter(query_filter)
         if mmr is not None:
@@ -823,10 +973,28 @@ class QdrantClient:
         MMR requests in it (QueryRequest.query = NearestQuery(..., mmr=Mmr(...))): one search
         at the batch's largest candidate count and one MMR launch, the plain requests riding
         at diversity 0 with their own limit as candidate count — unless a plain limit exceeds
-        RAG_MMR_MAX_CANDIDATES, in which case the plain requests are searched on their own."""
+        RAG_MMR_MAX_CANDIDATES, in which case the plain requests are searched on their own.
+        Fusion requests (QueryRequest.prefetch with a FusionQuery / RrfQuery) are answered
+        together by one search_points_fusion call, the remaining requests as a batch of their
+        own, and the results are scattered back in request order."""
         col = self._col(collection_name)
         if not requests:
             return []
+        fus = [i for i, r in enumerate(requests)
+               if getattr(r, "prefetch", None) is not None or is_fusion(r.query)]
+        if fus:
+            par = [fusion_params(requests[i].query, requests[i].prefetch, requests[i].limit,
+                                 requests[i].filter) for i in fus]
+            out: list = [None] * len(requests)
+            hits = col.search_points_fusion(
+                [(rrf_k, pres, int(requests[i].limit)) for i, (rrf_k, pres) in zip(fus, par)])
+            for i, h in zip(fus, hits):
+                out[i] = models.QueryResponse(points=_payloads(h, requests[i].with_payload))
+            rest = [i for i in range(len(requests)) if out[i] is None]
+            for i, resp in zip(rest, self.query_batch_points(
+                    collection_name, [requests[i] for i in rest], **kwargs)):
+                out[i] = resp
+            return out
         unwrapped = [nearest_of(r.query) for r in requests]
         qs = [v for v, _ in unwrapped]
         Q = torch.stack([x if isinstance(x, torch.Tensor) else
@@ -870,6 +1038,9 @@ class QdrantClient:
             raise ValueError("query_points_groups needs group_by, a payload field")
         if kwargs.get("with_lookup") is not None:
             raise NotImplementedError("with_lookup (a join on another collection) is not supported")
+        if is_fusion(query) or kwargs.get("prefetch") is not None:
+            raise ValueError("a grouped query over prefetched candidates (prefetch, FusionQuery, "
+                             "RrfQuery) is not built")
         query, mmr = nearest_of(query)
         if mmr is not None:
             raise ValueError("a grouped query cannot be an MMR query (NearestQuery.mmr)")

@@ -199,11 +199,47 @@ class NearestQuery:
     mmr: Optional[Mmr] = None
 
 
+class Fusion(str, enum.Enum):
+    RRF = "rrf"
+    DBSF = "dbsf"
+
+
+@dataclass
+class FusionQuery:
+    """query_points(prefetch=[Prefetch(...), ...], query=FusionQuery(fusion=Fusion.RRF)): the
+    prefetched lists fused by reciprocal rank, with the default constant 2."""
+    fusion: Fusion
+
+
+@dataclass
+class Rrf:
+    """Reciprocal rank fusion parameters: a hit at 0-based position p of a prefetched list
+    contributes 1 / (k + p). None takes the default, 2."""
+    k: Optional[int] = None
+
+
+@dataclass
+class RrfQuery:
+    """FusionQuery(Fusion.RRF) with its constant spelled out: RrfQuery(rrf=Rrf(k=60))."""
+    rrf: Rrf
+
+
+@dataclass
+class Prefetch:
+    """One candidate list of a fusion query: the `limit` nearest points to `query` (a vector,
+    or a NearestQuery without mmr) under `filter`. A nested `prefetch` is refused."""
+    query: Any = None
+    filter: Optional[Filter] = None
+    limit: int = 10
+    prefetch: Any = None
+
+
 @dataclass
 class QueryRequest:
     """Batched query entry for query_batch_points (one per request of a micro-batch); `query`
-    is a vector or a NearestQuery."""
+    is a vector or a NearestQuery, or with `prefetch` a FusionQuery / RrfQuery."""
     query: Any
     filter: Optional[Filter] = None
     limit: int = 10
     with_payload: Any = True
+    prefetch: Any = None

@@ -139,13 +139,40 @@ def _query(vector, diversity, candidates):
                                mmr=models.Mmr(diversity=diversity, candidates_limit=candidates))
 
 
+FUSION_PREFETCH = 50         # a rewrite's list is max(limit, this) hits long
+
+
+def _fusion(vector, rewrites, flt, limit, rrf_k, diversity, candidates):
+    """(query, prefetch) of a multi-query retrieval: the original vector and each rewrite become
+    one Prefetch under the request's filter, fused by reciprocal rank (rrf_k None: the default
+    constant)."""
+    if diversity is not None or candidates is not None:
+        raise ValueError("rewrites (fusion) cannot be combined with diversity / candidates (MMR)")
+    query = (models.FusionQuery(fusion=models.Fusion.RRF) if rrf_k is None else
+             models.RrfQuery(rrf=models.Rrf(k=rrf_k)))
+    return query, [models.Prefetch(query=v, filter=flt, limit=max(limit, FUSION_PREFETCH))
+                   for v in [vector, *rewrites]]
+
+
 def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEVE_LIMIT, *,
-                         diversity=None, candidates=None):
+                         diversity=None, candidates=None, rewrites=None, rrf_k=None):
     """diversity / candidates (keyword-only, not in the reference): MMR re-selection of the
     `limit` hits from the `candidates` nearest (Mmr's defaults where one is None), so
-    near-duplicate chunks do not fill the list; both None is the reference's call."""
+    near-duplicate chunks do not fill the list; both None is the reference's call.
+    rewrites (keyword-only): extra query vectors for the same question; the lists of the
+    original and of each rewrite, max(limit, 50) hits under the same filter, are fused by
+    reciprocal rank (constant rrf_k, None = 2) and cut to `limit`. None is today's call; with
+    diversity / candidates it is a ValueError."""
     if _testing():
         return type("obj", (object,), {"points": []})
+    if rewrites is not None:
+        query, prefetch = _fusion(query_vector, rewrites, _filter(ticker, document_type), limit,
+                                  rrf_k, diversity, candidates)
+        try:
+            return get_qdrant().query_points(collection_name=COLLECTION_NAME, query=query,
+                                             prefetch=prefetch, limit=limit)
+        except Exception:
+            return type("obj", (object,), {"points": []})
     # the reference's swallow-to-empty (main.py:232-239) unchanged: query_points answers any
     # limit exactly (large limits on the full exact pass), so an exception here is a real
     # failure, as it is for the reference's Qdrant call
@@ -159,12 +186,21 @@ def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEV
 
 
 def retrieve_batch(query_vectors, tickers, document_types=None, limit=RETRIEVE_LIMIT, *,
-                   diversity=None, candidates=None):
+                   diversity=None, candidates=None, rewrites=None, rrf_k=None):
     """One GPU scan for a whole micro-batch (main2.py:281-295 + 228), per-request filters;
-    diversity / candidates as in retrieve_from_qdrant, for every request of the batch."""
+    diversity / candidates as in retrieve_from_qdrant, for every request of the batch.
+    rewrites: per request a list of extra query vectors (as in retrieve_from_qdrant); every
+    prefetch of the batch rides one scan and one fusion launch."""
     if _testing():
         return [type("obj", (object,), {"points": []}) for _ in tickers]
     document_types = document_types or [None] * len(tickers)
+    if rewrites is not None:
+        reqs = []
+        for v, t, d, rw in zip(query_vectors, tickers, document_types, rewrites):
+            query, prefetch = _fusion(v, rw or [], _filter(t, d), limit, rrf_k, diversity,
+                                      candidates)
+            reqs.append(models.QueryRequest(query=query, prefetch=prefetch, limit=limit))
+        return get_qdrant().query_batch_points(COLLECTION_NAME, reqs)
     reqs = [models.QueryRequest(query=_query(v, diversity, candidates), limit=limit,
                                 filter=_filter(t, d))
             for v, t, d in zip(query_vectors, tickers, document_types)]

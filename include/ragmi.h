@@ -286,6 +286,42 @@ int rag_group_select(const float* cand_scores_dev, const int64_t* cand_rows_dev,
                      float* out_scores_dev, int64_t* out_rows_dev, int32_t* out_pos_dev,
                      int32_t* out_count_dev, void* stream);
 
+/* Fusion queries (Qdrant's query_points(prefetch = [Prefetch(...), ...], query =
+ * FusionQuery(Fusion.RRF))): the L candidate lists of a request fused by reciprocal rank.
+ * Index-free like rag_group_select: it reads only its input arrays (cand_rows_dev int64
+ * [B][L][C], -1 = none; ncand_dev int32 [B][L] or NULL = C everywhere), runs on the calling
+ * thread's current device and is asynchronous on `stream`.
+ *
+ * Entries. For request b and list l the entries are the first n_{b,l} positions, n_{b,l} =
+ * min(ncand_dev[b][l] clamped to [0, C], the number of leading entries with row >= 0): a negative
+ * row ends its list. Rows are opaque int64 ids, compared and copied, never dereferenced; they may
+ * exceed 2^31 (global ids).
+ *
+ * Fused score. An entry at 0-based position p contributes c(p) = 1.0 / (double)(rrf_k + p), one
+ * correctly rounded fp64 division. For a distinct row r, fused(r) = (float)(sum of c(p)) over
+ * every entry holding r: the contributions are added in fp64 in (list ascending, position
+ * ascending) order from 0.0, and the sum is rounded once to fp32. A row that appears twice in
+ * one list (a search never produces that, a caller may) contributes twice.
+ *
+ * Result. The distinct rows ordered by (fused fp32 value descending, row ascending); the first k
+ * go to out_scores_dev fp32 [B][k] and out_rows_dev int64 [B][k], -inf / -1 past the last
+ * distinct row; out_count_dev int32 [B] (may be NULL) is the number of distinct rows, which may
+ * exceed k. Every output element is written by the launch, and the result is a pure function of
+ * the inputs (no floating-point atomics). So L = 1 returns the list unchanged with scores
+ * (float)(1.0 / (rrf_k + p)), and the first k' outputs of a run at k are the run at k'.
+ *
+ * Limits, refused on the host before any HIP call: 1 <= L <= RAG_FUSION_MAX_LISTS, C >= 1,
+ * L * C <= RAG_FUSION_MAX_ENTRIES (RAG_ERANGE); k >= 1, rrf_k >= 1, B >= 0, non-NULL
+ * cand_rows_dev / out_scores_dev / out_rows_dev (RAG_EINVAL); B = 0 launches nothing. The
+ * arithmetic is this project's definition, modelled on Qdrant's published RRF (reciprocal of
+ * position plus a constant, default 2); the reference never fuses, and parity with a Qdrant
+ * server's own fusion is unpinned. */
+#define RAG_FUSION_MAX_LISTS 16
+#define RAG_FUSION_MAX_ENTRIES 4096 /* L * C */
+int rag_fuse_rrf(const int64_t* cand_rows_dev, const int32_t* ncand_dev, int B, int L, int C,
+                 int k, int rrf_k, float* out_scores_dev, int64_t* out_rows_dev,
+                 int32_t* out_count_dev, void* stream);
+
 /* Merge n_lists per-shard result lists (each [B][k] sorted by (score desc, id asc), device;
  * laid out [n_lists][B][k]; padding: id -1) into the global top-k [B][k] (device) by (score
  * desc, id asc), padding -inf / -1 past the valid entries. Any k >= 1 (k > RAG_MAX_K_LARGE:
