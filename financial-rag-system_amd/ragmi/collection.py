@@ -1,0 +1,469 @@
+"""Collection — one COSINE collection: an index in HBM (FlatIndex, or a ShardSet over several
+devices) plus the host-side id / payload / version maps, and every search route over them.
+
+A row number means a point only while the collection's lock is held (a delete moves rows):
+every route resolves its hits to ScoredPoints under the same hold of the lock as the search
+that produced them (`_points`). All index work goes on the caller's current stream.
+"""
+from __future__ import annotations
+
+import threading
+import uuid
+from typing import Any
+
+import numpy as np
+import torch
+
+from . import groups
+from . import qdrant_models as models
+from .coalesce import Coalescer
+from .filters import (DEFAULT_TAG_FIELDS, MAX_PROGRAMS, FilterProgram, PayloadTags,
+                      UnsupportedFilter, compile_filter, compile_legacy_only, pack_view)
+from .index import (FUSION_MAX_ENTRIES, GROUPS_MAX, GROUPS_MAX_CELLS, FlatIndex, fuse_rrf,
+                    hits_of, host_or_tensor)
+from .shardset import ShardSet, parse_devices
+
+
+def _norm_id(pid):
+    """Qdrant point ids are unsigned ints or UUIDs; 32-hex md5 digests (ingest.py:151-154)
+    are accepted as UUIDs and reported back in canonical dashed form."""
+    if isinstance(pid, bool):
+        raise ValueError("point id must be int or UUID string")
+    if isinstance(pid, (int, np.integer)):
+        if pid < 0:
+            raise ValueError("integer point ids must be unsigned")
+        return int(pid)
+    if isinstance(pid, uuid.UUID):
+        return str(pid)
+    if isinstance(pid, str):
+        return str(uuid.UUID(pid))
+    raise ValueError(f"unsupported point id type {type(pid)!r}")
+
+
+def parse_selector(points_selector):
+    """The `points_selector` of QdrantClient.delete -> ("ids", [normalised ids]) or
+    ("filter", Filter): a plain list of ids, a PointIdsList, a FilterSelector or a bare
+    Filter."""
+    sel = points_selector
+    if isinstance(sel, models.FilterSelector):
+        if sel.filter is None:
+            raise ValueError("FilterSelector needs a filter")
+        return "filter", sel.filter
+    if isinstance(sel, models.Filter):
+        return "filter", sel
+    if isinstance(sel, models.PointIdsList):
+        sel = sel.points
+    if isinstance(sel, (str, bytes, dict)) or not hasattr(sel, "__iter__"):
+        raise ValueError("points_selector must be a list of ids, a PointIdsList, a "
+                         "FilterSelector or a Filter")
+    return "ids", [_norm_id(pid) for pid in sel]
+
+
+def stack_queries(qs: list, dim: int, one: bool = False, host: bool = False):
+    """The query stacker: query vectors given as lists, arrays or tensors, as one [n, dim]
+    batch: a tensor when any of them is one, else a float32 array. one=True: `qs` is the one
+    vector of a single request. host=True (the coalescer route, whose leader stacks its riders'
+    queries on the host): tensors are brought to host numpy first."""
+    if host:
+        qs = [x.detach().float().cpu().numpy() if isinstance(x, torch.Tensor) else x for x in qs]
+    if len(qs) == 1:
+        Q = host_or_tensor(qs[0]).reshape(1, -1)
+    elif any(isinstance(x, torch.Tensor) for x in qs):
+        dev = next(x.device for x in qs if isinstance(x, torch.Tensor))
+        Q = torch.stack([(x if isinstance(x, torch.Tensor) else
+                          torch.as_tensor(np.asarray(x, np.float32))).to(dev).reshape(-1)
+                         for x in qs])
+    else:
+        Q = np.stack([np.asarray(x, np.float32).reshape(-1) for x in qs])
+    if Q.shape[1] != dim:
+        raise ValueError(f"{'query' if one else 'every query'} must be one {dim}-dim vector")
+    return Q
+
+
+class Collection:
+    """One COSINE collection: FlatIndex in HBM + host-side id/payload maps. With `devices`
+    (one device index per shard, ragmi.shardset.parse_devices) the rows are striped over a
+    ShardSet instead; rows, ids, payloads and tags stay global and host-side either way.
+    `index`: an object to use as the index (the protocol of DESIGN.md "Where the front end
+    lives"); no FlatIndex / ShardSet is created then."""
+
+    def __init__(self, name: str, dim: int, device, tag_fields=DEFAULT_TAG_FIELDS,
+                 capacity: int = 1024, storage: str = "fp32", devices=None, *, index=None):
+        self.name = name
+        self.dim = dim
+        self.tags = PayloadTags(tag_fields)
+        devices = parse_devices(devices)
+        self.index = (index if index is not None else
+                      ShardSet(dim=dim, devices=devices, capacity=capacity, storage=storage)
+                      if devices is not None else
+                      FlatIndex(dim=dim, capacity=capacity, device=device, storage=storage))
+        self.id_to_row: dict[Any, int] = {}
+        self.row_ids: list[Any] = []
+        self.payloads: list[dict | None] = []
+        self.versions: list[int] = []
+        self.op = 0
+        self.group_stats = {}    # routes grouped searches took (ragmi.groups.search_groups)
+        self.lock = threading.RLock()
+        # 32 queries per scan pass at D = 384, 4 groups of 32 at D = 1024 (ragmi.h)
+        self.coalescer = Coalescer(self, 0.0, 32 if dim <= 384 else 128,
+                                   search=self.search_points)
+
+    @property
+    def rescued(self) -> int:
+        """Queries re-answered on the full exact pass (the index's counter; stats). Setting it
+        sets the index's counter."""
+        return self.index.rescued
+
+    @rescued.setter
+    def rescued(self, n: int) -> None:
+        self.index.rescued = n
+
+    def compile_filter(self, flt):
+        """ragmi.filters.compile_filter over this collection's tags."""
+        return compile_filter(self.tags, flt)
+
+    # ---------------------------------------------------------------- writes
+    def upsert(self, ids: list, vectors, payloads: list) -> int:
+        with self.lock:
+            self.op += 1
+            vec = host_or_tensor(vectors)
+            if vec.ndim != 2 or vec.shape[1] != self.dim:
+                raise ValueError(f"vectors must be [n, {self.dim}]")
+            # last write wins for duplicate ids inside one batch (Qdrant semantics)
+            last: dict[Any, int] = {}
+            for i, pid in enumerate(ids):
+                last[_norm_id(pid)] = i
+            rows, sel, tags = [], [], []
+            new_count = len(self.row_ids)
+            for pid, i in last.items():
+                r = self.id_to_row.get(pid)
+                if r is None:
+                    r = new_count
+                    new_count += 1
+                    self.id_to_row[pid] = r
+                    self.row_ids.append(pid)
+                    self.payloads.append(None)
+                    self.versions.append(0)
+                p = payloads[i] if payloads is not None else None
+                self.payloads[r] = dict(p) if p is not None else None
+                self.versions[r] = self.op
+                rows.append(r)
+                sel.append(i)
+                tags.append(self.tags.tag(p))
+            if new_count > self.index.capacity:
+                self.index.reserve(max(new_count, 2 * self.index.capacity))
+            if rows:
+                sel_t = vec[sel] if isinstance(vec, torch.Tensor) else vec[np.asarray(sel)]
+                self.index.upsert(sel_t, np.asarray(rows, dtype=np.int64),
+                                  np.asarray(tags, dtype=np.uint32), new_count=new_count)
+            return self.op
+
+    def delete(self, points_selector) -> int:
+        """Remove the selected points (parse_selector). Unknown ids are ignored, duplicates
+        collapse, a filter on a never-ingested value selects nothing; a filter is resolved on
+        the device (select_rows over the tags), never by walking the payloads. The rows are
+        removed from the index by the removal rule (ragmi.index.plan_removal) and the same
+        (src, dst) moves are applied to the host maps: a moved point keeps its id, payload
+        and version. Returns the operation id. The device work has finished on return."""
+        kind, what = parse_selector(points_selector)
+        with self.lock:
+            # may refuse the filter
+            flt = (compile_legacy_only(self.tags, what, "Collection.delete")
+                   if kind == "filter" else None)
+            self.op += 1
+            if kind == "ids":
+                found = {self.id_to_row[pid] for pid in what if pid in self.id_to_row}
+                rows = np.fromiter(found, dtype=np.int64, count=len(found))
+            else:
+                rows = self._matching(flt)[0]
+            if rows.size:
+                src, dst, n1 = self.index.remove_rows(rows)
+                self._apply_removal(rows, src, dst, n1)
+                torch.cuda.current_stream(self.index.device).synchronize()
+            return self.op
+
+    def _apply_removal(self, rows, src, dst, n1: int) -> None:
+        """The host side of a removal: forget the deleted rows' ids, give every moved row's
+        id, payload and version its new slot, truncate to the new count."""
+        for r in rows.tolist():
+            del self.id_to_row[self.row_ids[r]]
+        for s, d in zip(src.tolist(), dst.tolist()):
+            pid = self.row_ids[s]
+            self.row_ids[d] = pid
+            self.payloads[d] = self.payloads[s]
+            self.versions[d] = self.versions[s]
+            self.id_to_row[pid] = d
+        del self.row_ids[n1:], self.payloads[n1:], self.versions[n1:]
+
+    # ---------------------------------------------------------------- reads
+    def _matching(self, c, cap: int | None = None):
+        """The rows a compiled filter selects, resolved on the device: (rows, total) — the
+        first `cap` rows (default: all) as a host int64 array, None for cap = 0 (a pure count),
+        and the count of every match. The one triage of a filter for row selection: nothing
+        matches, every row matches, select_rows of a (mask, value) pair, select_rows_view of a
+        FilterProgram. Called under the lock."""
+        n = len(self.row_ids)
+        if c is None or not n:
+            return np.empty(0, np.int64), 0
+        if c == (0, 0):
+            return np.arange(n if cap is None else min(cap, n), dtype=np.int64), n
+        if isinstance(c, FilterProgram):
+            rows, total = self.index.select_rows_view(pack_view([c]), cap=cap)
+        else:
+            rows, total = self.index.select_rows(c[0], c[1], cap=cap)
+        return (rows.cpu().numpy() if cap != 0 else None), total
+
+    def count_matching(self, flt) -> int:
+        """Points a Filter matches, counted on the device (select_rows with cap = 0)."""
+        with self.lock:
+            return self._matching(self.compile_filter(flt), cap=0)[1]
+
+    def _points(self, hits: list, with_vectors=False) -> list:
+        """Per request its hits [(row, score)] resolved to ScoredPoints (payload attached). A
+        delete moves rows, so a row number means a point only while the lock is held: called
+        under the same hold of the lock as the search that produced the hits."""
+        return [[self.point(r, s, True, with_vectors) for r, s in h] for h in hits]
+
+    def search_points(self, queries, limit: int, filters: list, with_vectors=False):
+        """search with every hit resolved to its ScoredPoint under the same hold of the lock
+        (_points). What query_points, query_batch_points and the coalescer's leaders call."""
+        with self.lock:
+            return self._points(self.search(queries, limit, filters), with_vectors)
+
+    def search(self, queries, limit: int, filters: list):
+        """queries [B, dim]; filters: per query compiled filter ((mask, value) or None)."""
+        with self.lock:
+            B = len(filters)
+            if limit < 1:
+                return [[] for _ in range(B)]
+            # Qdrant answers any limit with at most the collection's points (main.py:215,
+            # 232-237): k <= 32 on the scan, <= 4096 on the large-k pass, beyond that on the
+            # full exact pass (rag_index_search)
+            k = min(limit, max(1, self.index.count))
+            live = [i for i, f in enumerate(filters) if f is not None]
+            out = [[] for _ in range(B)]
+            if not live or self.index.count == 0:
+                return out
+            for i, h in zip(live, hits_of(*self._lists(queries, filters, live, k))):
+                out[i] = h
+            return out
+
+    @staticmethod
+    def _live(queries, filters: list, live: list):
+        """The one slice of the live requests: their queries ([n, dim], a tensor staying a
+        tensor) and their compiled filters."""
+        q = host_or_tensor(queries)
+        return (q[live] if len(live) != len(filters) else q), [filters[i] for i in live]
+
+    @staticmethod
+    def _pairs(fl: list):
+        """(mask, value) filters as the index takes them: [n, 2] uint32, or None when no
+        request filters."""
+        use = np.asarray(fl, dtype=np.uint32).reshape(-1, 2)
+        return use if use.any() else None
+
+    def _lists(self, queries, filters: list, live: list, k: int):
+        """The exact top-k lists of the `live` requests. Every live filter a (mask, value)
+        pair: the path of every release so far, unchanged. Otherwise the view path
+        (_view_lists)."""
+        q, fl = self._live(queries, filters, live)
+        if not any(isinstance(f, FilterProgram) for f in fl):
+            return self._exact_lists(q, k, self._pairs(fl))
+        return self._view_lists(q, fl, k)
+
+    def _view_lists(self, q, fl: list, k: int):
+        """_lists with general filters among the live ones: the batch's distinct programs
+        share view bits (a (mask, value) pair rides as its one-atom MASKEQ program; (0, 0)
+        needs no bit, over any view it passes every row), every query gets the filter
+        (1 << slot, 1 << slot), and one view search answers the batch. More than MAX_PROGRAMS
+        distinct programs: the queries are dealt into calls of at most that many, each query
+        into the first call that knows its program or has a free bit, and the results are
+        scattered back."""
+        calls: list = []                       # (slots: {program: bit}, members, their filters)
+        for j, f in enumerate(fl):
+            prog = (f if isinstance(f, FilterProgram) else
+                    None if tuple(f) == (0, 0) else FilterProgram.maskeq(*f))
+            for slots, members, bits in calls:
+                if prog is None or prog in slots or len(slots) < MAX_PROGRAMS:
+                    break
+            else:
+                slots, members, bits = {}, [], []
+                calls.append((slots, members, bits))
+            bit = 0 if prog is None else 1 << slots.setdefault(prog, len(slots))
+            members.append(j)
+            bits.append((bit, bit))
+        s = ids = None
+        for slots, members, bits in calls:
+            # every call holds a program: a call is opened for a query that brings one, except
+            # the first, and a batch without any program never comes here
+            blob = pack_view(list(slots))
+            use = np.asarray(bits, dtype=np.uint32).reshape(-1, 2)
+            if len(calls) == 1:
+                return self._exact_lists(q, k, use, programs=blob)
+            s1, i1 = self._exact_lists(q[members], k, use, programs=blob)
+            if s is None:
+                s = torch.empty((len(fl), k), dtype=s1.dtype, device=s1.device)
+                ids = torch.empty((len(fl), k), dtype=i1.dtype, device=i1.device)
+            sel = torch.as_tensor(members, device=s1.device)
+            s[sel] = s1
+            ids[sel] = i1
+        return s, ids
+
+    def _exact_lists(self, q, k: int, use, programs=None):
+        """The exact top-k lists (scores, rows) of queries `q`, as the index's tensors, with
+        every query a large-k pass left unanswered re-answered on the full exact pass (the
+        index's search, rescue). What search reports and what the MMR path re-selects from.
+        Called under the lock. `programs`: a filter-program blob; `use` then indexes the bits
+        of its view."""
+        view = {} if programs is None else {"programs": programs}
+        return self.index.search(q, k, filters=use, rescue=True, **view)
+
+    def search_mmr(self, queries, limits, filters: list, diversity, candidates):
+        """search with MMR re-selection, per request b: limits[b] hits chosen at diversity[b]
+        from its candidates[b] nearest points (clamped to the collection's count) — one
+        search at C = the largest of them, one MMR launch with per-query candidate counts.
+        A request at diversity 0 with candidates = its limit is the plain search. Returns
+        per request [(row, score)] in selection order."""
+        with self.lock:
+            B = len(filters)
+            out = [[] for _ in range(B)]
+            count = self.index.count
+            live = [i for i, f in enumerate(filters) if f is not None and limits[i] >= 1]
+            if not live or count == 0:
+                return out
+            ncand = np.minimum(np.asarray([candidates[i] for i in live], np.int64), count)
+            ncand = np.maximum(ncand, 1).astype(np.int32)
+            lim = [int(limits[i]) for i in live]
+            C = int(ncand.max())
+            k = min(max(lim), C)
+            s, ids = self._lists(queries, filters, live, C)
+            s, ids = self.index.mmr(s, ids, k, np.asarray([diversity[i] for i in live],
+                                                          np.float32), ncand)
+            for i, n, h in zip(live, lim, hits_of(s, ids)):
+                out[i] = h[:n]
+            return out
+
+    def search_points_mmr(self, queries, limits, filters: list, diversity, candidates,
+                          with_vectors=False):
+        """search_mmr with every hit resolved to its ScoredPoint under the same hold of the
+        lock (_points)."""
+        with self.lock:
+            return self._points(self.search_mmr(queries, limits, filters, diversity, candidates),
+                                with_vectors)
+
+    def search_fusion(self, requests: list):
+        """Fusion queries. `requests`: per request (rrf_k, [(vector, Filter or
+        None, limit), ...], limit), as fusion_params returns them. Every prefetch of every
+        request rides one batched search at C = the largest prefetch limit (clamped to the
+        collection's count); the lists are arranged [B, Lmax, C] on the device, each cut to
+        its own limit by ncand, and fused by rag_fuse_rrf in one launch per distinct rrf_k. A
+        prefetch whose filter can match nothing, or whose limit is < 1, is an empty list and
+        is not searched. Returns per request [(row, fused score)], best first."""
+        with self.lock:
+            out = [[] for _ in requests]
+            count = self.index.count
+            # every filter is compiled, so that a refusal does not depend on the limits
+            compiled = [[self.compile_filter(f) for _, f, _ in pres] for _, pres, _ in requests]
+            qs, filters, where = [], [], []          # the searched prefetches, flattened
+            for b, (_, pres, limit) in enumerate(requests):
+                if limit < 1 or count == 0:
+                    continue
+                for l, (vec, _, plim) in enumerate(pres):
+                    if compiled[b][l] is not None and plim >= 1:
+                        qs.append(vec)
+                        filters.append(compiled[b][l])
+                        where.append((b, l, min(plim, count)))
+            if not qs:
+                return out
+            live = sorted({b for b, _, _ in where})
+            slot = {b: j for j, b in enumerate(live)}
+            Lmax = max(len(requests[b][1]) for b in live)
+            C = max(n for _, _, n in where)
+            if Lmax * C > FUSION_MAX_ENTRIES:
+                raise ValueError(f"fusion: {Lmax} prefetches of up to {C} hits are {Lmax * C} "
+                                 f"entries; at most {FUSION_MAX_ENTRIES} (prefetches x the "
+                                 "largest prefetch limit) are fused")
+            _, ids = self._lists(stack_queries(qs, self.dim), filters, list(range(len(qs))), C)
+            dev = ids.device
+            rows = torch.full((len(live), Lmax, C), -1, dtype=torch.int64, device=dev)
+            at = np.asarray([(slot[b], l) for b, l, _ in where], dtype=np.int64)
+            rows[torch.from_numpy(at[:, 0]).to(dev), torch.from_numpy(at[:, 1]).to(dev)] = ids
+            ncand = np.zeros((len(live), Lmax), dtype=np.int32)
+            ncand[at[:, 0], at[:, 1]] = [n for _, _, n in where]
+            lim = [int(requests[b][2]) for b in live]
+            k = min(max(lim), Lmax * C)
+            by_k: dict[int, list] = {}
+            for j, b in enumerate(live):
+                by_k.setdefault(requests[b][0], []).append(j)
+            for rrf_k, members in by_k.items():
+                if len(members) == len(live):
+                    s, r = fuse_rrf(rows, k, rrf_k, ncand)
+                else:
+                    sel = torch.as_tensor(members, device=dev)
+                    s, r = fuse_rrf(rows[sel], k, rrf_k, ncand[members])
+                for j, h in zip(members, hits_of(s, r)):
+                    out[live[j]] = h[:lim[j]]
+            return out
+
+    def search_points_fusion(self, requests: list, with_vectors=False):
+        """search_fusion with every hit resolved to its ScoredPoint (score = the fused score)
+        under the same hold of the lock (_points)."""
+        with self.lock:
+            return self._points(self.search_fusion(requests), with_vectors)
+
+    def search_groups(self, queries, group_by: str, limit: int, group_size: int, filters: list,
+                      with_vectors=False, candidates: int | None = None,
+                      widen: int | None = None):
+        """Grouped search (ragmi.groups.search_groups): per request the `limit`
+        best groups of points sharing a value of tag field `group_by`, each with its
+        `group_size` best hits — exact, whatever `candidates` / `widen` (policy) say. Returns
+        per request a list of PointGroup (id = the payload value) whose hits are resolved to
+        ScoredPoints under the same hold of the lock (_points). The route counters accumulate
+        in `group_stats`."""
+        if group_by not in self.tags.fields:
+            raise UnsupportedFilter(
+                f"group_by {group_by!r} is not an indexed keyword field {self.tags.fields}; "
+                "create the collection with payload_tag_fields")
+        f = self.tags.fields.index(group_by)
+        shift = 16 * f
+        key_mask = 0xFFFF << shift
+        with self.lock:
+            B = len(filters)
+            out = [[] for _ in range(B)]
+            count = self.index.count
+            codes = self.tags.codes[f]
+            live = [i for i, fl in enumerate(filters) if fl is not None]
+            if any(isinstance(filters[i], FilterProgram) for i in live):
+                raise UnsupportedFilter(
+                    "query_points_groups takes only Filter(must=[FieldCondition(key, "
+                    "match=MatchValue)]); a grouped search under a general filter (should, "
+                    "must_not, MatchAny, ...) is out of scope: its exactness ladder composes "
+                    "(mask, value) pairs")
+            if limit < 1 or group_size < 1 or not live or count == 0 or not codes:
+                return out
+            # neither clamp can change a result: there are no more groups than codes, no
+            # more hits than points
+            G, S = min(int(limit), len(codes)), min(int(group_size), count)
+            if G > GROUPS_MAX or G * S > GROUPS_MAX_CELLS:
+                raise ValueError(f"grouped search: at most {GROUPS_MAX} groups and "
+                                 f"{GROUPS_MAX_CELLS} hits in all (limit x group_size)")
+            every = [c << shift for c in codes.values()]
+            q, fl = self._live(queries, filters, live)
+            possible = [[v & key_mask] if m & key_mask else every for m, v in fl]
+            res = groups.search_groups(self.index, q, self._pairs(fl), key_mask, possible, G, S,
+                                       candidates, widen, search=self._exact_lists,
+                                       stats=self.group_stats)
+            for i, found in zip(live, res):
+                points = self._points([hits for _, hits in found], with_vectors)
+                out[i] = [models.PointGroup(hits=pts, id=self.tags.value_of(f, key >> shift))
+                          for (key, _), pts in zip(found, points)]
+            return out
+
+    def point(self, row: int, score: float, with_payload=True, with_vectors=False):
+        payload = self.payloads[row] if with_payload else None
+        vec = None
+        if with_vectors:
+            vec = (self.index.export_rows32(row, 1)[0] if self.index.storage == "fp32" else
+                   self.index.export_rows(row, 1)[0].view(np.float16).astype(np.float32)).tolist()
+        return models.ScoredPoint(id=self.row_ids[row], version=self.versions[row],
+                                  score=score, payload=payload, vector=vec)

@@ -1,6 +1,6 @@
 """Filter programs: Qdrant's filter algebra over the two tag fields, compiled for the GPU.
 
-`PayloadTags.compile` (ragmi.qdrant) knows one filter shape, Filter(must=[FieldCondition(key,
+`PayloadTags.compile` (below) knows one filter shape, Filter(must=[FieldCondition(key,
 match=MatchValue)]), and turns it into one (mask, value) pair. Everything else the tag can
 answer — `should`, `must_not`, `min_should`, MatchAny, MatchExcept, "is empty", nested filters —
 is compiled here into a PROGRAM: at most MAX_ATOMS atoms and a 256-bit truth table over them.
@@ -43,7 +43,9 @@ calls it.
 """
 from __future__ import annotations
 
+import itertools
 from dataclasses import dataclass
+from typing import Any
 
 import numpy as np
 
@@ -58,6 +60,81 @@ ATOM_INSET = 1         # RAG_FILTER_ATOM_INSET
 
 class UnsupportedFilter(NotImplementedError):
     pass
+
+
+DEFAULT_TAG_FIELDS = ("ticker", "document_type")
+
+
+class PayloadTags:
+    """Dictionary-codes up to two keyword payload fields into a per-row uint32 tag
+    (16 bits per field, code 0 = field absent) and compiles Qdrant `must` filters on those
+    fields into (mask, value) so the GPU scan filters with (tag & mask) == value.
+    Host-only logic (no device code)."""
+
+    def __init__(self, fields=DEFAULT_TAG_FIELDS):
+        if len(fields) > 2:
+            raise ValueError("at most two indexed keyword payload fields (16 bits each)")
+        self.fields = tuple(fields)
+        self.codes: list[dict[Any, int]] = [dict() for _ in self.fields]
+
+    def code(self, f: int, value, create: bool) -> int | None:
+        if isinstance(value, (list, dict)) or value is None:
+            return None
+        table = self.codes[f]
+        c = table.get(value)
+        if c is None and create:
+            if len(table) >= 0xFFFF:
+                raise OverflowError(f"more than 65535 distinct values for {self.fields[f]}")
+            c = len(table) + 1          # 0 = field absent
+            table[value] = c
+        return c
+
+    def value_of(self, f: int, code: int):
+        """The payload value behind code `code` of field f, the reverse of `code`: codes are
+        handed out in insertion order (1, 2, ...) and a dict keeps that order, so no second
+        table is kept."""
+        table = self.codes[f]
+        if not 1 <= code <= len(table):
+            raise KeyError(f"no value with code {code} for {self.fields[f]}")
+        return next(itertools.islice(table, code - 1, None))
+
+    def tag(self, payload: dict | None) -> int:
+        tag = 0
+        if payload:
+            for f, key in enumerate(self.fields):
+                if key in payload:
+                    c = self.code(f, payload[key], create=True)
+                    if c:
+                        tag |= c << (16 * f)
+        return tag
+
+    def compile(self, flt: models.Filter | None):
+        """Filter(must=[FieldCondition(key, MatchValue(v))...]) -> (mask, value); None when
+        nothing can match (a value never ingested); (0, 0) for no filter."""
+        if flt is None:
+            return (0, 0)
+        if flt.should or flt.must_not:
+            raise UnsupportedFilter("only `must` conditions are supported (main.py:218-236)")
+        mask = value = 0
+        for cond in flt.must or []:
+            if not isinstance(cond, models.FieldCondition) or cond.range is not None:
+                raise UnsupportedFilter("only FieldCondition(key, match=MatchValue) is supported")
+            if cond.key not in self.fields:
+                raise UnsupportedFilter(
+                    f"payload key {cond.key!r} is not an indexed keyword field "
+                    f"{self.fields}; create the collection with payload_tag_fields")
+            if not isinstance(cond.match, models.MatchValue):
+                raise UnsupportedFilter("only MatchValue matches are supported")
+            f = self.fields.index(cond.key)
+            c = self.code(f, cond.match.value, create=False)
+            if c is None:
+                return None
+            m = 0xFFFF << (16 * f)
+            if mask & m and (value & m) != (c << (16 * f)):
+                return None             # two different values for one field
+            mask |= m
+            value |= c << (16 * f)
+        return (mask, value)
 
 
 @dataclass(frozen=True)
@@ -205,6 +282,37 @@ def compile_program(tags, flt):
     if table == (1 << (1 << m)) - 1:
         return (0, 0)
     return FilterProgram(tuple(c.atoms), table)
+
+
+# ------------------------------------------------------------------ the two front ends
+def compile_filter(tags, flt):
+    """A Filter as the searches take it: the (mask, value) pair of PayloadTags.compile for
+    every filter it accepts (the legacy path, untouched), else a FilterProgram
+    (compile_program: should, must_not, min_should, MatchAny, MatchExcept, is-empty, nested
+    filters); None when nothing can match. A filter neither accepts is refused with the general
+    compiler's message, which names the cause. A filter with `min_should` goes to the general
+    compiler at once: PayloadTags.compile never looked at that clause."""
+    if getattr(flt, "min_should", None) is not None:
+        return compile_program(tags, flt)
+    try:
+        return tags.compile(flt)
+    except UnsupportedFilter:
+        return compile_program(tags, flt)
+
+
+def compile_legacy_only(tags, flt, what: str):
+    """PayloadTags.compile for a route (`what`) that takes no general filter yet: its refusal
+    says that the route is the reason when the filter algebra would have accepted the filter."""
+    try:
+        if getattr(flt, "min_should", None) is not None:
+            raise UnsupportedFilter("min_should is not a `must` condition")
+        return tags.compile(flt)
+    except UnsupportedFilter as e:
+        compile_program(tags, flt)        # refused by both: the general message
+        raise UnsupportedFilter(
+            f"{what} takes only Filter(must=[FieldCondition(key, match=MatchValue)]); "
+            f"general filters (should, must_not, MatchAny, ...) are out of scope here: {e}"
+        ) from e
 
 
 # ------------------------------------------------------------------ device blob

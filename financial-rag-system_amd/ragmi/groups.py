@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .index import MAX_K_LARGE, QUERY_TILE
+from .index import MAX_K_LARGE, QUERY_TILE, hits_of
 
 
 def default_candidates(G: int, S: int) -> int:
@@ -108,10 +108,7 @@ def search_groups(index, queries, filters, key_mask: int, keys_possible, G: int,
         f = fl[which].copy()
         f[:, 0] |= np.uint32(key_mask)
         f[:, 1] |= np.asarray([k for _, k in pairs], np.uint32)
-        s, r = search(_take(queries, which), k_key, f)
-        s, r = _np(s), _np(r)
-        return [[(int(row), float(sc)) for sc, row in zip(s[j], r[j]) if row >= 0]
-                for j in range(len(pairs))]
+        return hits_of(*search(_take(queries, which), k_key, f))
 
     select(list(range(B)), C1)                                            # 1
     wide = [b for b in range(B)

@@ -47,6 +47,20 @@ def _as_dev(x, dtype, device) -> torch.Tensor:
     return t.contiguous()
 
 
+def host_or_tensor(x):
+    """Vectors as the index calls take them: a tensor stays a tensor (used in place), anything
+    else becomes a float32 host array."""
+    return x if isinstance(x, torch.Tensor) else np.asarray(x, np.float32)
+
+
+def hits_of(scores, rows) -> list:
+    """Exact lists [B, k] (tensors or arrays) -> per query [(row, score)] without the -1
+    padding. Reads device lists back."""
+    s = scores.cpu().numpy() if isinstance(scores, torch.Tensor) else np.asarray(scores)
+    r = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    return [[(int(x), float(sc)) for x, sc in zip(rj, sj) if x >= 0] for rj, sj in zip(r, s)]
+
+
 def view_blob(programs, n_programs, device):
     """A filter-program blob (ragmi.filters.pack_view; a uint32 host array, or an int32 cuda
     tensor already on `device`) as the *_view calls take it: (int32 cuda tensor, words, U).
@@ -99,7 +113,52 @@ def plan_removal(count: int, rows):
     return src, dst, n1
 
 
-class FlatIndex:
+def rescue_unanswered(index, s, ids, again) -> None:
+    """The rescue rule of FlatIndex.search(rescue=True), over the lists (s, ids) a search just
+    returned: a list with a -1 is padding (fewer matching points than k) unless the pass left
+    the query unanswered (tier 3: more than 16384 rows tied within the error band of its k-th
+    best on the large-k pass), which shows as `index.unanswered()` risen past the watermark
+    `index._unanswered`. Only then are the short queries re-run, `again(rows)` answering them
+    on the full exact pass, written over their lists and counted in `index.rescued`: an
+    unanswered query must never read as "no documents". Host logic over any index."""
+    if bool((ids < 0).any()):
+        n_un = index.unanswered()
+        if n_un > index._unanswered:
+            redo = torch.nonzero((ids < 0).any(dim=1)).reshape(-1).tolist()
+            s[redo], ids[redo] = again(redo)
+            index.rescued += len(redo)
+        index._unanswered = n_un
+
+
+class ListOps:
+    """What FlatIndex and ShardSet compose alike from their own search, mmr and gather_tags."""
+
+    def search_mmr(self, queries, k: int, diversity, candidates, filters=None):
+        """search(k=C) followed by mmr, C = the largest of `candidates` (a scalar or one value
+        per query: how many nearest candidates each query re-selects from), all on the device
+        and the current stream. Returns (scores [B, k], rows [B, k]) as mmr does."""
+        q, B, f = self._search_args(queries, k, filters)
+        nc = per_query(candidates, B, np.int32, "candidates")
+        if B and int(nc.min()) < 1:
+            raise ValueError("candidates must be >= 1")
+        C = int(nc.max()) if B else 1
+        if C > MMR_MAX_CANDIDATES:
+            raise ValueError(f"at most {MMR_MAX_CANDIDATES} MMR candidates per query")
+        s, r = self.search(q, C, f)
+        return self.mmr(s, r, k, diversity, None if B and (nc == C).all() else nc)
+
+    def group_select(self, cand_scores, cand_rows, key_mask: int, G: int, S: int, ncand=None,
+                     with_pos: bool = False) -> "GroupSelection":
+        """The grouped walk over exact candidate lists (search(k=C)'s result; rows of this
+        index): gather_tags of the rows, then rag_group_select, both on the current stream.
+        The selection reads only the lists, so a ShardSet's result is the one-index result
+        bit for bit. See group_select_tags for the result."""
+        r = _as_dev(cand_rows, torch.int64, self.device)
+        return group_select_tags(_as_dev(cand_scores, torch.float32, self.device), r,
+                                 self.gather_tags(r), key_mask, G, S, ncand, with_pos)
+
+
+class FlatIndex(ListOps):
     """In-HBM flat index with exact (score desc, row asc) top-k search. storage "fp16": the
     fp16 rows only (what the scan streams); "fp32": the normalised fp32 rows too, which the
     exact scores read (Qdrant's default Float32 vectors; rag_index_create_ex).
@@ -122,6 +181,8 @@ class FlatIndex:
         check(self._L.rag_index_create_ex(self.dim, int(capacity), self.device.index, flags,
                                           ctypes.byref(h)))
         self._h = h
+        self._unanswered = 0     # unanswered() as last read (search, rescue)
+        self.rescued = 0         # queries re-answered on the full exact pass (stats)
 
     # ---------------------------------------------------------------- lifetime
     def close(self) -> None:
@@ -197,29 +258,43 @@ class FlatIndex:
                 raise ValueError("filters must be [B, 2] (tag_mask, tag_value)")
         return q, B, f
 
+    def _launch(self, q, f, k: int, id_offset: int, view, full=False, lists=None, packed=None):
+        """The one search launch behind search and search_packed, on the current stream: into
+        `lists` (scores, ids) or into `packed`; over the filter view of `view` (view_blob's
+        triple) when there is one, else over the stored tags."""
+        fp = f.data_ptr() if f is not None else None
+        sp = lists[0].data_ptr() if lists is not None else None
+        ip = lists[1].data_ptr() if lists is not None else None
+        st = _stream_ptr(self.device)
+        if view is not None:
+            p, words, U = view
+            check(self._L.rag_index_search_view(
+                self._h, q.data_ptr(), q.shape[0], int(k), p.data_ptr(), words, U, fp,
+                int(id_offset), SEARCH_FULL if full else 0, sp, ip,
+                packed.data_ptr() if packed is not None else None, st))
+        elif packed is not None:
+            check(self._L.rag_index_search_packed(self._h, q.data_ptr(), q.shape[0], int(k), fp,
+                                                  int(id_offset), packed.data_ptr(), st))
+        else:
+            fn = self._L.rag_index_search_full if full else self._L.rag_index_search
+            check(fn(self._h, q.data_ptr(), q.shape[0], int(k), fp, int(id_offset), sp, ip, st))
+        # staging tensors (q, f) go back to torch's stream-ordered caching allocator: any
+        # reuse is enqueued on this same stream after our kernels, so no sync is needed.
+
     def search_packed(self, queries, k: int, filters=None, id_offset: int = 0,
                       programs=None, n_programs: int | None = None) -> torch.Tensor:
         """Top-k in the multi-GPU exchange form: int32 [B, k, 2] = (fp32 score bits, global
         row; -1 = none), enqueued on the current stream (rag_index_search_packed).
         `programs`: as in search."""
         q, B, f = self._search_args(queries, k, filters, k_max=MAX_K_LARGE)
+        view = None if programs is None else view_blob(programs, n_programs, self.device)
         out = torch.empty((B, k, 2), dtype=torch.int32, device=self.device)
-        if programs is not None:
-            p, words, U = view_blob(programs, n_programs, self.device)
-            check(self._L.rag_index_search_view(
-                self._h, q.data_ptr(), B, int(k), p.data_ptr(), words, U,
-                f.data_ptr() if f is not None else None, int(id_offset), 0, None, None,
-                out.data_ptr(), _stream_ptr(self.device)))
-            return out
-        check(self._L.rag_index_search_packed(self._h, q.data_ptr(), B, int(k),
-                                              f.data_ptr() if f is not None else None,
-                                              int(id_offset), out.data_ptr(),
-                                              _stream_ptr(self.device)))
+        self._launch(q, f, k, id_offset, view, packed=out)
         return out
 
     def search(self, queries, k: int, filters=None, id_offset: int = 0,
                out: tuple[torch.Tensor, torch.Tensor] | None = None, full: bool = False,
-               programs=None, n_programs: int | None = None):
+               programs=None, n_programs: int | None = None, rescue: bool = False):
         """Top-k of each query row. Returns (scores fp32 [B,k], ids int64 [B,k]) as cuda
         tensors, enqueued on the current stream (ids -1 where fewer than k rows match).
         `filters`: None, or per-query (tag_mask, tag_value) pairs [B, 2] (uint32).
@@ -229,29 +304,22 @@ class FlatIndex:
         unanswered.
         `programs`: a filter-program blob (ragmi.filters.pack_view). The search then runs over
         the blob's filter view of the tags (rag_index_search_view) and `filters` are (mask,
-        value) pairs over the VIEW's bits: (1 << s, 1 << s) asks for program s."""
+        value) pairs over the VIEW's bits: (1 << s, 1 << s) asks for program s.
+        rescue=True (Collection.search): queries the pass left unanswered are re-run with
+        full=True under the same filters and programs (rescue_unanswered; counted in
+        `rescued`). Reads the lists back, so it synchronises; without it nothing is read."""
         q, B, f = self._search_args(queries, k, filters)
+        view = None if programs is None else view_blob(programs, n_programs, self.device)
         if out is None:
-            out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
-            out_i = torch.empty((B, k), dtype=torch.int64, device=self.device)
-        else:
-            out_s, out_i = out
-        if programs is not None:
-            p, words, U = view_blob(programs, n_programs, self.device)
-            check(self._L.rag_index_search_view(
-                self._h, q.data_ptr(), B, int(k), p.data_ptr(), words, U,
-                f.data_ptr() if f is not None else None, int(id_offset),
-                SEARCH_FULL if full else 0, out_s.data_ptr(), out_i.data_ptr(), None,
-                _stream_ptr(self.device)))
-            return out_s, out_i
-        fn = self._L.rag_index_search_full if full else self._L.rag_index_search
-        check(fn(self._h, q.data_ptr(), B, int(k),
-                 f.data_ptr() if f is not None else None,
-                 int(id_offset), out_s.data_ptr(), out_i.data_ptr(),
-                 _stream_ptr(self.device)))
-        # staging tensors (q, f) go back to torch's stream-ordered caching allocator: any
-        # reuse is enqueued on this same stream after our kernels, so no sync is needed.
-        return out_s, out_i
+            out = (torch.empty((B, k), dtype=torch.float32, device=self.device),
+                   torch.empty((B, k), dtype=torch.int64, device=self.device))
+        self._launch(q, f, k, id_offset, view, full, lists=out)
+        if rescue and not full:
+            p, U = (None, None) if view is None else (view[0], view[2])
+            rescue_unanswered(self, *out, lambda redo: self.search(
+                q[redo], k, None if f is None else f[redo], id_offset, full=True, programs=p,
+                n_programs=U))
+        return out
 
     # ---------------------------------------------------------------- MMR
     def mmr(self, cand_scores, cand_rows, k: int, diversity, ncand=None,
@@ -291,20 +359,6 @@ class FlatIndex:
                                     _stream_ptr(self.device)))
         return (out_s, out_i, pos) if with_pos else (out_s, out_i)
 
-    def search_mmr(self, queries, k: int, diversity, candidates, filters=None):
-        """search(k=C) followed by mmr, C = the largest of `candidates` (a scalar or one value
-        per query: how many nearest candidates each query re-selects from), all on the device
-        and the current stream. Returns (scores [B, k], rows [B, k]) as mmr does."""
-        q, B, f = self._search_args(queries, k, filters)
-        nc = per_query(candidates, B, np.int32, "candidates")
-        if B and int(nc.min()) < 1:
-            raise ValueError("candidates must be >= 1")
-        C = int(nc.max()) if B else 1
-        if C > MMR_MAX_CANDIDATES:
-            raise ValueError(f"at most {MMR_MAX_CANDIDATES} MMR candidates per query")
-        s, r = self.search(q, C, f)
-        return self.mmr(s, r, k, diversity, None if B and (nc == C).all() else nc)
-
     # ---------------------------------------------------------------- grouped search
     def gather_tags(self, rows) -> torch.Tensor:
         """The tags of `rows` (int64, any shape; rag_index_gather_tags): an int32 tensor of the
@@ -317,15 +371,6 @@ class FlatIndex:
                                                 _stream_ptr(self.device)))
         return out
 
-    def group_select(self, cand_scores, cand_rows, key_mask: int, G: int, S: int, ncand=None,
-                     with_pos: bool = False) -> "GroupSelection":
-        """The grouped walk over exact candidate lists (search(k=C)'s result; rows of this
-        index): gather_tags of the rows, then rag_group_select, both on the current stream.
-        See group_select_tags for the result."""
-        r = _as_dev(cand_rows, torch.int64, self.device)
-        return group_select_tags(_as_dev(cand_scores, torch.float32, self.device), r,
-                                 self.gather_tags(r), key_mask, G, S, ncand, with_pos)
-
     # ---------------------------------------------------------------- row removal
     def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None,
                     out: torch.Tensor | None = None):
@@ -336,20 +381,29 @@ class FlatIndex:
         Synchronises the current stream (the total is read back)."""
         if cap is None:
             cap = self.count if out is None else min(self.count, out.numel())
+        return self._selected(cap, out, lambda rows, cap, n, st: self._L.rag_index_select_rows(
+            self._h, int(tag_mask) & 0xFFFFFFFF, int(tag_value) & 0xFFFFFFFF, rows, cap, n, st))
+
+    def _out(self, out, n: int, dtype, what: str) -> torch.Tensor:
+        """A caller's `out=` buffer checked, or a fresh one: `n` elements of `dtype` here."""
+        if out is None:
+            return torch.empty((n,), dtype=dtype, device=self.device)
+        if out.dtype != dtype or out.device != self.device or out.numel() < n \
+                or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {str(dtype)[6:]} tensor of >= {what} "
+                             "elements on the index's device")
+        return out
+
+    def _selected(self, cap, out, launch):
+        """The tail of both selects: `launch(rows, cap, total, stream)` writes at most `cap`
+        rows and the count of every match; (out[:min(total, cap)], total)."""
         cap = int(cap)
         if cap < 0:
             raise ValueError("cap must be >= 0")
-        if out is None:
-            out = torch.empty((cap,), dtype=torch.int64, device=self.device)
-        elif out.dtype != torch.int64 or out.device != self.device or out.numel() < cap \
-                or not out.is_contiguous():
-            raise ValueError("out must be a contiguous int64 tensor of >= cap elements on the "
-                             "index's device")
+        out = self._out(out, cap, torch.int64, "cap")
         n = torch.empty((1,), dtype=torch.int64, device=self.device)
-        check(self._L.rag_index_select_rows(self._h, int(tag_mask) & 0xFFFFFFFF,
-                                            int(tag_value) & 0xFFFFFFFF,
-                                            out.data_ptr() if cap else None, cap, n.data_ptr(),
-                                            _stream_ptr(self.device)))
+        check(launch(out.data_ptr() if cap else None, cap, n.data_ptr(),
+                     _stream_ptr(self.device)))
         total = int(n.item())
         return out[:min(total, cap)], total
 
@@ -361,12 +415,7 @@ class FlatIndex:
         `capacity` elements to write into. Enqueued on the current stream."""
         p, words, U = view_blob(programs, n_programs, self.device)
         cap = self.capacity
-        if out is None:
-            out = torch.empty((cap,), dtype=torch.int32, device=self.device)
-        elif out.dtype != torch.int32 or out.device != self.device or out.numel() < cap \
-                or not out.is_contiguous():
-            raise ValueError("out must be a contiguous int32 tensor of >= capacity elements on "
-                             "the index's device")
+        out = self._out(out, cap, torch.int32, "capacity")
         check(self._L.rag_index_filter_view(self._h, p.data_ptr(), words, U, out.data_ptr(),
                                             _stream_ptr(self.device)))
         return out[:cap]
@@ -376,16 +425,9 @@ class FlatIndex:
         rag_index_select_rows_view): (rows int64 cuda tensor, total). Synchronises the current
         stream (the total is read back)."""
         p, words, _ = view_blob(programs, 1, self.device)
-        cap = self.count if cap is None else int(cap)
-        if cap < 0:
-            raise ValueError("cap must be >= 0")
-        out = torch.empty((cap,), dtype=torch.int64, device=self.device)
-        n = torch.empty((1,), dtype=torch.int64, device=self.device)
-        check(self._L.rag_index_select_rows_view(self._h, p.data_ptr(), words,
-                                                 out.data_ptr() if cap else None, cap,
-                                                 n.data_ptr(), _stream_ptr(self.device)))
-        total = int(n.item())
-        return out[:min(total, cap)], total
+        return self._selected(self.count if cap is None else cap, None,
+                              lambda rows, cap, n, st: self._L.rag_index_select_rows_view(
+                                  self._h, p.data_ptr(), words, rows, cap, n, st))
 
     def move_rows(self, src, dst, new_count: int) -> None:
         """Copy every stored form of row src[i] into slot dst[i], bit for bit, then set the
@@ -443,15 +485,39 @@ class FlatIndex:
         return src, dst, n1
 
     # ---------------------------------------------------------------- introspection
-    def export_rows(self, row0: int = 0, n: int | None = None) -> np.ndarray:
-        """Stored fp16 rows (uint16 bits) [n, dim], row-major."""
+    def _export(self, fn, ptr, row0: int, n, tail: tuple, dtype) -> np.ndarray:
         if n is None:
             n = self.count - row0
-        out = np.empty((n, self.dim), dtype=np.uint16)
+        out = np.empty((n,) + tail, dtype=dtype)
         torch.cuda.current_stream(self.device).synchronize()
-        check(self._L.rag_index_export_rows(self._h, int(row0), int(n),
-                                            out.ctypes.data_as(_lib.c_u16p)))
+        check(fn(self._h, int(row0), int(n), out.ctypes.data_as(ptr)))
         return out
+
+    def export_rows(self, row0: int = 0, n: int | None = None) -> np.ndarray:
+        """Stored fp16 rows (uint16 bits) [n, dim], row-major."""
+        return self._export(self._L.rag_index_export_rows, _lib.c_u16p, row0, n, (self.dim,),
+                            np.uint16)
+
+    def export_rows32(self, row0: int = 0, n: int | None = None) -> np.ndarray:
+        """fp32 storage: the stored normalised fp32 rows [n, dim]."""
+        return self._export(self._L.rag_index_export_rows32, _lib.c_f32p, row0, n, (self.dim,),
+                            np.float32)
+
+    def export_tags(self, row0: int = 0, n: int | None = None) -> np.ndarray:
+        return self._export(self._L.rag_index_export_tags, _lib.c_u32p, row0, n, (), np.uint32)
+
+    def _import(self, fn, ptr, a: np.ndarray, row0: int, tags, new_count) -> None:
+        n = a.shape[0]
+        t = None
+        if tags is not None:
+            t = np.ascontiguousarray(tags, dtype=np.uint32)
+            if t.shape != (n,):
+                raise ValueError("tags must be [n]")
+        if new_count is None:
+            new_count = max(self.count, row0 + n)
+        torch.cuda.current_stream(self.device).synchronize()
+        check(fn(self._h, int(row0), int(n), a.ctypes.data_as(ptr),
+                 t.ctypes.data_as(_lib.c_u32p) if t is not None else None, int(new_count)))
 
     def import_rows(self, rows_f16, row0: int = 0, tags=None,
                     new_count: int | None = None) -> None:
@@ -462,28 +528,7 @@ class FlatIndex:
             a = a.view(np.uint16)
         if a.dtype != np.uint16 or a.ndim != 2 or a.shape[1] != self.dim:
             raise ValueError(f"rows must be float16/uint16 [n, {self.dim}]")
-        n = a.shape[0]
-        t = None
-        if tags is not None:
-            t = np.ascontiguousarray(tags, dtype=np.uint32)
-            if t.shape != (n,):
-                raise ValueError("tags must be [n]")
-        if new_count is None:
-            new_count = max(self.count, row0 + n)
-        torch.cuda.current_stream(self.device).synchronize()
-        check(self._L.rag_index_import_rows(
-            self._h, int(row0), int(n), a.ctypes.data_as(_lib.c_u16p),
-            t.ctypes.data_as(_lib.c_u32p) if t is not None else None, int(new_count)))
-
-    def export_rows32(self, row0: int = 0, n: int | None = None) -> np.ndarray:
-        """fp32 storage: the stored normalised fp32 rows [n, dim]."""
-        if n is None:
-            n = self.count - row0
-        out = np.empty((n, self.dim), dtype=np.float32)
-        torch.cuda.current_stream(self.device).synchronize()
-        check(self._L.rag_index_export_rows32(self._h, int(row0), int(n),
-                                              out.ctypes.data_as(_lib.c_f32p)))
-        return out
+        self._import(self._L.rag_index_import_rows, _lib.c_u16p, a, row0, tags, new_count)
 
     def import_rows32(self, rows_f32, row0: int = 0, tags=None,
                       new_count: int | None = None) -> None:
@@ -492,27 +537,7 @@ class FlatIndex:
         a = np.ascontiguousarray(rows_f32, dtype=np.float32)
         if a.ndim != 2 or a.shape[1] != self.dim:
             raise ValueError(f"rows must be float32 [n, {self.dim}]")
-        n = a.shape[0]
-        t = None
-        if tags is not None:
-            t = np.ascontiguousarray(tags, dtype=np.uint32)
-            if t.shape != (n,):
-                raise ValueError("tags must be [n]")
-        if new_count is None:
-            new_count = max(self.count, row0 + n)
-        torch.cuda.current_stream(self.device).synchronize()
-        check(self._L.rag_index_import_rows32(
-            self._h, int(row0), int(n), a.ctypes.data_as(_lib.c_f32p),
-            t.ctypes.data_as(_lib.c_u32p) if t is not None else None, int(new_count)))
-
-    def export_tags(self, row0: int = 0, n: int | None = None) -> np.ndarray:
-        if n is None:
-            n = self.count - row0
-        out = np.empty((n,), dtype=np.uint32)
-        torch.cuda.current_stream(self.device).synchronize()
-        check(self._L.rag_index_export_tags(self._h, int(row0), int(n),
-                                            out.ctypes.data_as(_lib.c_u32p)))
-        return out
+        self._import(self._L.rag_index_import_rows32, _lib.c_f32p, a, row0, tags, new_count)
 
     def set_scan_order(self, serial: bool) -> None:
         """serial=True: each pass's scan waits for the previous pass's scan on any stream
@@ -541,7 +566,7 @@ class FlatIndex:
         k <= 32 passes whose second pass was skipped (RAGMI_RESCAN_WG=0, diagnostic handles
         only), and 32 < k <= 4096 passes where more than 16384 rows tie within the MFMA error
         band of a query's k-th best score after the last collection round (possible in
-        production, e.g. thousands of identical boilerplate chunks). Collection.search re-runs
+        production, e.g. thousands of identical boilerplate chunks). search(rescue=True) re-runs
         such queries on the full exact pass (search(full=True)). rag_index_unanswered;
         synchronises the device."""
         n = ctypes.c_int64()

@@ -17,234 +17,27 @@ construction and `save()` / `close()` write them back (ragmi.store shard format)
 keyed by row; the keyword payload fields used by the reference's `must` filter (`ticker`,
 `document_type`, main.py:218-230) are dictionary-coded into a per-row uint32 tag in HBM
 (16 bits per field) so filtering runs inside the scan kernel.
+
+This module holds the client and the parsing of request arguments; the collection engine is
+ragmi.collection, the coalescer ragmi.coalesce, the tag codebook and the filter compilers
+ragmi.filters. Their public names are re-exported here.
 """
 from __future__ import annotations
 
-import itertools
 import os
 import shutil
 import threading
-import time
-import uuid
-from typing import Any, Iterable
+from typing import Iterable
 
 import numpy as np
-import torch
 
-from . import groups
 from . import qdrant_models as models
-from .filters import MAX_PROGRAMS, FilterProgram, UnsupportedFilter, compile_program, pack_view
-from .index import (FUSION_MAX_ENTRIES, FUSION_MAX_LISTS, GROUPS_MAX, GROUPS_MAX_CELLS, MAX_K,
-                    MMR_MAX_CANDIDATES, FlatIndex, fuse_rrf)
-from .shardset import ShardSet, parse_devices
-
-DEFAULT_TAG_FIELDS = ("ticker", "document_type")
-
-
-def _norm_id(pid):
-    """Qdrant point ids are unsigned ints or UUIDs; 32-hex md5 digests (ingest.py:151-154)
-    are accepted as UUIDs and reported back in canonical dashed form."""
-    if isinstance(pid, bool):
-        raise ValueError("point id must be int or UUID string")
-    if isinstance(pid, (int, np.integer)):
-        if pid < 0:
-            raise ValueError("integer point ids must be unsigned")
-        return int(pid)
-    if isinstance(pid, uuid.UUID):
-        return str(pid)
-    if isinstance(pid, str):
-        return str(uuid.UUID(pid))
-    raise ValueError(f"unsupported point id type {type(pid)!r}")
-
-
-class PayloadTags:
-    """Dictionary-codes up to two keyword payload fields into a per-row uint32 tag
-    (16 bits per field, code 0 = field absent) and compiles Qdrant `must` filters on those
-    fields into (mask, value) so the GPU scan filters with (tag & mask) == value.
-    Host-only logic (no device code)."""
-
-    def __init__(self, fields=DEFAULT_TAG_FIELDS):
-        if len(fields) > 2:
-            raise ValueError("at most two indexed keyword payload fields (16 bits each)")
-        self.fields = tuple(fields)
-        self.codes: list[dict[Any, int]] = [dict() for _ in self.fields]
-
-    def code(self, f: int, value, create: bool) -> int | None:
-        if isinstance(value, (list, dict)) or value is None:
-            return None
-        table = self.codes[f]
-        c = table.get(value)
-        if c is None and create:
-            if len(table) >= 0xFFFF:
-                raise OverflowError(f"more than 65535 distinct values for {self.fields[f]}")
-            c = len(table) + 1          # 0 = field absent
-            table[value] = c
-        return c
-
-    def value_of(self, f: int, code: int):
-        """The payload value behind code `code` of field f, the reverse of `code`: codes are
-        handed out in insertion order (1, 2, ...) and a dict keeps that order, so no second
-        table is kept."""
-        table = self.codes[f]
-        if not 1 <= code <= len(table):
-            raise KeyError(f"no value with code {code} for {self.fields[f]}")
-        return next(itertools.islice(table, code - 1, None))
-
-    def tag(self, payload: dict | None) -> int:
-        tag = 0
-        if payload:
-            for f, key in enumerate(self.fields):
-                if key in payload:
-                    c = self.code(f, payload[key], create=True)
-                    if c:
-                        tag |= c << (16 * f)
-        return tag
-
-    def compile(self, flt: models.Filter | None):
-        """Filter(must=[FieldCondition(key, MatchValue(v))...]) -> (mask, value); None when
-        nothing can match (a value never ingested); (0, 0) for no filter."""
-        if flt is None:
-            return (0, 0)
-        if flt.should or flt.must_not:
-            raise UnsupportedFilter("only `must` conditions are supported (main.py:218-236)")
-        mask = value = 0
-        for cond in flt.must or []:
-            if not isinstance(cond, models.FieldCondition) or cond.range is not None:
-                raise UnsupportedFilter("only FieldCondition(key, match=MatchValue) is supported")
-            if cond.key not in self.fields:
-                raise UnsupportedFilter(
-                    f"payload key {cond.key!r} is not an indexed keyword field "
-                    f"{self.fields}; create the collection with payload_tag_fields")
-            if not isinstance(cond.match, models.MatchValue):
-                raise UnsupportedFilter("only MatchValue matches are supported")
-            f = self.fields.index(cond.key)
-            c = self.code(f, cond.match.value, create=False)
-            if c is None:
-                return None
-            m = 0xFFFF << (16 * f)
-            if mask & m and (value & m) != (c << (16 * f)):
-                return None             # two different values for one field
-            mask |= m
-            value |= c << (16 * f)
-        return (mask, value)
-
-
-class _Req:
-    __slots__ = ("q", "limit", "filt", "result", "exc", "wake", "lead")
-
-    def __init__(self, q, limit, filt):
-        self.q, self.limit, self.filt = q, limit, filt
-        self.result = self.exc = None
-        self.wake = threading.Event()
-        self.lead = False
-
-
-class Coalescer:
-    """Rides concurrent single-query searches on one GPU scan.
-
-    The reference's batched service still searches per request: main2.py's batch_processor
-    fans a micro-batch out to process_independently tasks that each call
-    retrieve_from_qdrant -> query_points from an asyncio.to_thread worker (<= 25 at once,
-    main2.py:52-53,218,228). Unchanged, that is one full-corpus scan per query. Here the
-    first caller becomes the LEADER and searches; callers arriving while a search runs queue
-    up, and the next leader (the oldest queued request) searches all of them in ONE batched
-    scan (per-query payload filters ride inside the kernel). With no concurrency a request
-    runs at once (no added latency); `window_s` > 0 additionally holds a leader back for up
-    to that long to gather more callers. Results are bit-identical to individual calls: every
-    query's top-k is exact, independent of its batch-mates (tests/test_qdrant_gpu.py)."""
-
-    def __init__(self, col: "Collection", window_s: float = 0.0, max_batch: int = 32,
-                 search=None):
-        self.col = col
-        # what a leader calls for its batch: col.search (rows and scores), or for a Collection
-        # its search_points, whose hits are resolved to points before the collection's lock is
-        # released — a rider must not look rows up after a delete may have moved them
-        self.search_fn = search
-        self.window = float(window_s)
-        self.max_batch = int(max_batch)
-        self.lock = threading.Lock()
-        self.pending: list[_Req] = []
-        self.leader_active = False
-        self.batches = 0            # scans issued (stats)
-        self.requests = 0
-
-    def search(self, q: np.ndarray, limit: int, filt):
-        req = _Req(q, int(limit), filt)
-        with self.lock:
-            self.pending.append(req)
-            self.requests += 1
-            if not self.leader_active:
-                self.leader_active = True
-                req.lead = True
-        if not req.lead:
-            req.wake.wait()
-            if not req.lead:                       # served by another leader
-                if req.exc is not None:
-                    raise req.exc
-                return req.result
-        batch: list[_Req] = []
-        fatal = None
-        try:
-            if self.window > 0:
-                t_end = time.perf_counter() + self.window
-                while time.perf_counter() < t_end:
-                    with self.lock:
-                        if len(self.pending) >= self.max_batch:
-                            break
-                    time.sleep(min(5e-5, self.window / 4))
-            with self.lock:
-                batch = self.pending[:self.max_batch]
-                del self.pending[:self.max_batch]
-                self.batches += 1
-            hits = (self.search_fn or self.col.search)(
-                np.stack([r.q for r in batch]), max(r.limit for r in batch),
-                [r.filt for r in batch])
-            for r, h in zip(batch, hits):
-                r.result = h[:r.limit]
-        except BaseException as e:                 # every rider sees the failure
-            for r in batch:
-                r.exc = e
-            if not isinstance(e, Exception):       # KeyboardInterrupt, SystemExit: re-raise
-                fatal = e                          # after the hand-off below
-        finally:
-            # whatever was raised: hand leadership on and wake every rider, so no caller of
-            # this collection can block forever behind a leader that is gone
-            with self.lock:
-                if req in self.pending:            # interrupted before taking the batch
-                    self.pending.remove(req)
-                if self.pending:                   # hand leadership to the oldest waiter
-                    nxt = self.pending[0]
-                    nxt.lead = True
-                    nxt.wake.set()
-                else:
-                    self.leader_active = False
-            for r in batch:
-                if r is not req:
-                    r.wake.set()
-        if fatal is not None:
-            raise fatal
-        if req.exc is not None:
-            raise req.exc
-        return req.result
-
-
-def parse_selector(points_selector):
-    """The `points_selector` of QdrantClient.delete -> ("ids", [normalised ids]) or
-    ("filter", Filter): a plain list of ids, a PointIdsList, a FilterSelector or a bare
-    Filter."""
-    sel = points_selector
-    if isinstance(sel, models.FilterSelector):
-        if sel.filter is None:
-            raise ValueError("FilterSelector needs a filter")
-        return "filter", sel.filter
-    if isinstance(sel, models.Filter):
-        return "filter", sel
-    if isinstance(sel, models.PointIdsList):
-        sel = sel.points
-    if isinstance(sel, (str, bytes, dict)) or not hasattr(sel, "__iter__"):
-        raise ValueError("points_selector must be a list of ids, a PointIdsList, a "
-                         "FilterSelector or a Filter")
-    return "ids", [_norm_id(pid) for pid in sel]
+from .coalesce import Coalescer                                           # noqa: F401
+from .collection import Collection, _norm_id, parse_selector, stack_queries  # noqa: F401
+from .filters import (DEFAULT_TAG_FIELDS, PayloadTags, UnsupportedFilter,  # noqa: F401
+                      compile_filter)
+from .index import FUSION_MAX_LISTS, MAX_K, MMR_MAX_CANDIDATES
+from .shardset import parse_devices
 
 
 def _storage_of(vectors_config) -> str:
@@ -258,433 +51,6 @@ def _storage_of(vectors_config) -> str:
     if str(dt).lower() == "float16":
         return "fp16"
     raise NotImplementedError(f"vector datatype {dt!r} (float32 and float16 are supported)")
-
-
-class Collection:
-    """One COSINE collection: FlatIndex in HBM + host-side id/payload maps. With `devices`
-    (one device index per shard, ragmi.shardset.parse_devices) the rows are striped over a
-    ShardSet instead; rows, ids, payloads and tags stay global and host-side either way."""
-
-    def __init__(self, name: str, dim: int, device, tag_fields=DEFAULT_TAG_FIELDS,
-                 capacity: int = 1024, storage: str = "fp32", devices=None):
-        self.name = name
-        self.dim = dim
-        self.tags = PayloadTags(tag_fields)
-        devices = parse_devices(devices)
-        self.index = (ShardSet(dim=dim, devices=devices, capacity=capacity, storage=storage)
-                      if devices is not None else
-                      FlatIndex(dim=dim, capacity=capacity, device=device, storage=storage))
-        self.id_to_row: dict[Any, int] = {}
-        self.row_ids: list[Any] = []
-        self.payloads: list[dict | None] = []
-        self.versions: list[int] = []
-        self.op = 0
-        self._unanswered = 0     # index.unanswered() as last read (Collection.search)
-        self.rescued = 0         # queries re-answered on the full exact pass (stats)
-        self.group_stats = {}    # routes grouped searches took (ragmi.groups.search_groups)
-        self.lock = threading.RLock()
-        # 32 queries per scan pass at D = 384, 4 groups of 32 at D = 1024 (ragmi.h)
-        self.coalescer = Coalescer(self, 0.0, 32 if dim <= 384 else 128,
-                                   search=self.search_points)
-
-    def compile_filter(self, flt):
-        """A Filter as the searches take it: the (mask, value) pair of PayloadTags.compile for
-        every filter it accepts (today's path, untouched), else a FilterProgram
-        (ragmi.filters.compile_program: should, must_not, min_should, MatchAny, MatchExcept,
-        is-empty, nested filters); None when nothing can match. A filter neither accepts is
-        refused with the general compiler's message, which names the cause. A filter with
-        `min_should` goes to the general compiler at once: PayloadTags.compile never looked
-        at that clause."""
-        if getattr(flt, "min_should", None) is not None:
-            return compile_program(self.tags, flt)
-        try:
-            return self.tags.compile(flt)
-        except UnsupportedFilter:
-            return compile_program(self.tags, flt)
-
-    def _legacy_only(self, flt, what: str):
-        """PayloadTags.compile for a route that takes no general filter yet: its refusal says
-        that the route is the reason when the filter algebra would have accepted the filter."""
-        try:
-            if getattr(flt, "min_should", None) is not None:
-                raise UnsupportedFilter("min_should is not a `must` condition")
-            return self.tags.compile(flt)
-        except UnsupportedFilter as e:
-            compile_program(self.tags, flt)        # refused by both: the general message
-            raise UnsupportedFilter(
-                f"{what} takes only Filter(must=[FieldCondition(key, match=MatchValue)]); "
-                f"general filters (should, must_not, MatchAny, ...) are out of scope here: {e}"
-            ) from e
-
-    # ---------------------------------------------------------------- writes
-    def upsert(self, ids: list, vectors, payloads: list) -> int:
-        with self.lock:
-            self.op += 1
-            vec = np.asarray(vectors, dtype=np.float32) if not isinstance(
-                vectors, torch.Tensor) else vectors
-            if vec.ndim != 2 or vec.shape[1] != self.dim:
-                raise ValueError(f"vectors must be [n, {self.dim}]")
-            # last write wins for duplicate ids inside one batch (Qdrant semantics)
-            last: dict[Any, int] = {}
-            for i, pid in enumerate(ids):
-                last[_norm_id(pid)] = i
-            rows, sel, tags = [], [], []
-            new_count = len(self.row_ids)
-            for pid, i in last.items():
-                r = self.id_to_row.get(pid)
-                if r is None:
-                    r = new_count
-                    new_count += 1
-                    self.id_to_row[pid] = r
-                    self.row_ids.append(pid)
-                    self.payloads.append(None)
-                    self.versions.append(0)
-                p = payloads[i] if payloads is not None else None
-                self.payloads[r] = dict(p) if p is not None else None
-                self.versions[r] = self.op
-                rows.append(r)
-                sel.append(i)
-                tags.append(self.tags.tag(p))
-            if new_count > self.index.capacity:
-                self.index.reserve(max(new_count, 2 * self.index.capacity))
-            if rows:
-                sel_t = vec[sel] if isinstance(vec, torch.Tensor) else vec[np.asarray(sel)]
-                self.index.upsert(sel_t, np.asarray(rows, dtype=np.int64),
-                                  np.asarray(tags, dtype=np.uint32), new_count=new_count)
-            return self.op
-
-    def delete(self, points_selector) -> int:
-        """Remove the selected points (parse_selector). Unknown ids are ignored, duplicates
-        collapse, a filter on a never-ingested value selects nothing; a filter is resolved on
-        the device (select_rows over the tags), never by walking the payloads. The rows are
-        removed from the index by the removal rule (ragmi.index.plan_removal) and the same
-        (src, dst) moves are applied to the host maps: a moved point keeps its id, payload
-        and version. Returns the operation id. The device work has finished on return."""
-        kind, what = parse_selector(points_selector)
-        with self.lock:
-            # may refuse the filter
-            flt = self._legacy_only(what, "Collection.delete") if kind == "filter" else None
-            self.op += 1
-            if kind == "ids":
-                found = {self.id_to_row[pid] for pid in what if pid in self.id_to_row}
-                rows = np.fromiter(found, dtype=np.int64, count=len(found))
-            else:
-                if flt is None or not self.row_ids:
-                    rows = np.empty(0, np.int64)
-                elif flt == (0, 0):
-                    rows = np.arange(len(self.row_ids), dtype=np.int64)
-                else:
-                    rows = self.index.select_rows(flt[0], flt[1])[0].cpu().numpy()
-            if rows.size:
-                src, dst, n1 = self.index.remove_rows(rows)
-                self._apply_removal(rows, src, dst, n1)
-                torch.cuda.current_stream(self.index.device).synchronize()
-            return self.op
-
-    def _apply_removal(self, rows, src, dst, n1: int) -> None:
-        """The host side of a removal: forget the deleted rows' ids, give every moved row's
-        id, payload and version its new slot, truncate to the new count."""
-        for r in rows.tolist():
-            del self.id_to_row[self.row_ids[r]]
-        for s, d in zip(src.tolist(), dst.tolist()):
-            pid = self.row_ids[s]
-            self.row_ids[d] = pid
-            self.payloads[d] = self.payloads[s]
-            self.versions[d] = self.versions[s]
-            self.id_to_row[pid] = d
-        del self.row_ids[n1:], self.payloads[n1:], self.versions[n1:]
-
-    # ---------------------------------------------------------------- reads
-    def count_matching(self, flt) -> int:
-        """Points a Filter matches, counted on the device (select_rows with cap = 0)."""
-        with self.lock:
-            c = self.compile_filter(flt)
-            if c is None or not self.row_ids:
-                return 0
-            if c == (0, 0):
-                return len(self.row_ids)
-            if isinstance(c, FilterProgram):
-                return self.index.select_rows_view(pack_view([c]), cap=0)[1]
-            return self.index.select_rows(c[0], c[1], cap=0)[1]
-
-    def search_points(self, queries, limit: int, filters: list, with_vectors=False):
-        """search with every hit resolved to its ScoredPoint (payload attached) under the same
-        hold of the lock as the search that produced it: a delete moves rows, so a row number
-        means a point only while the lock is held. What query_points, query_batch_points and
-        the coalescer's leaders call."""
-        with self.lock:
-            return [[self.point(r, s, True, with_vectors) for r, s in h]
-                    for h in self.search(queries, limit, filters)]
-
-    def search(self, queries, limit: int, filters: list):
-        """queries [B, dim]; filters: per query compiled filter ((mask, value) or None)."""
-        with self.lock:
-            B = len(filters)
-            if limit < 1:
-                return [[] for _ in range(B)]
-            # Qdrant answers any limit with at most the collection's points (main.py:215,
-            # 232-237): k <= 32 on the scan, <= 4096 on the large-k pass, beyond that on the
-            # full exact pass (rag_index_search)
-            k = min(limit, max(1, self.index.count))
-            live = [i for i, f in enumerate(filters) if f is not None]
-            out = [[] for _ in range(B)]
-            if not live or self.index.count == 0:
-                return out
-            s, ids = self._lists(queries, filters, live, k)
-            s = s.cpu().numpy()
-            ids = ids.cpu().numpy()
-            for j, i in enumerate(live):
-                out[i] = [(int(r), float(sc)) for r, sc in zip(ids[j], s[j]) if r >= 0]
-            return out
-
-    def _lists(self, queries, filters: list, live: list, k: int):
-        """The exact top-k lists of the `live` requests. Every live filter a (mask, value)
-        pair: the path of every release so far, unchanged. Otherwise the view path
-        (_view_lists)."""
-        if not any(isinstance(filters[i], FilterProgram) for i in live):
-            q, use = self._live_queries(queries, filters, live)
-            return self._exact_lists(q, k, use)
-        return self._view_lists(queries, filters, live, k)
-
-    def _view_lists(self, queries, filters: list, live: list, k: int):
-        """_lists with general filters among the live ones: the batch's distinct programs
-        share view bits (a (mask, value) pair rides as its one-atom MASKEQ program; (0, 0)
-        needs no bit, over any view it passes every row), every query gets the filter
-        (1 << slot, 1 << slot), and one view search answers the batch. More than MAX_PROGRAMS
-        distinct programs: the queries are dealt into calls of at most that many, each query
-        into the first call that knows its program or has a free bit, and the results are
-        scattered back."""
-        q = queries if isinstance(queries, torch.Tensor) else np.asarray(queries, np.float32)
-        q = q[live] if len(live) != len(filters) else q
-        calls: list = []                       # (slots: {program: bit}, members, their filters)
-        for j, i in enumerate(live):
-            f = filters[i]
-            prog = (f if isinstance(f, FilterProgram) else
-                    None if tuple(f) == (0, 0) else FilterProgram.maskeq(*f))
-            for slots, members, fl in calls:
-                if prog is None or prog in slots or len(slots) < MAX_PROGRAMS:
-                    break
-            else:
-                slots, members, fl = {}, [], []
-                calls.append((slots, members, fl))
-            bit = 0 if prog is None else 1 << slots.setdefault(prog, len(slots))
-            members.append(j)
-            fl.append((bit, bit))
-        s = ids = None
-        for slots, members, fl in calls:
-            # every call holds a program: a call is opened for a query that brings one, except
-            # the first, and a batch without any program never comes here
-            blob = pack_view(list(slots))
-            use = np.asarray(fl, dtype=np.uint32).reshape(-1, 2)
-            if len(calls) == 1:
-                return self._exact_lists(q, k, use, programs=blob)
-            s1, i1 = self._exact_lists(q[members], k, use, programs=blob)
-            if s is None:
-                s = torch.empty((len(live), k), dtype=s1.dtype, device=s1.device)
-                ids = torch.empty((len(live), k), dtype=i1.dtype, device=i1.device)
-            sel = torch.as_tensor(members, device=s1.device)
-            s[sel] = s1
-            ids[sel] = i1
-        return s, ids
-
-    @staticmethod
-    def _live_queries(queries, filters: list, live: list):
-        """The queries of the `live` requests and their compiled filters as the index takes
-        them ([n, 2] uint32, or None when no request filters)."""
-        q = queries if isinstance(queries, torch.Tensor) else np.asarray(queries, np.float32)
-        q = q[live] if len(live) != len(filters) else q
-        fl = np.asarray([filters[i] for i in live], dtype=np.uint32).reshape(-1, 2)
-        return q, (fl if fl.any() else None)
-
-    def _exact_lists(self, q, k: int, use, programs=None):
-        """The exact top-k lists (scores, rows) of queries `q`, as the index's tensors, with
-        every query a large-k pass left unanswered re-answered on the full exact pass. What
-        search reports and what the MMR path re-selects from. Called under the lock.
-        `programs`: a filter-program blob; `use` then indexes the bits of its view, and the
-        re-run takes the same blob."""
-        view = {} if programs is None else {"programs": programs}
-        if isinstance(self.index, ShardSet):
-            # a shard that left a query unanswered hands the merge an all -1 list, which
-            # the merged top-k does not show: the set reads its per-shard flags and
-            # re-answers those queries itself (ShardSet.search, rescue)
-            before = self.index.rescued
-            s, ids = self.index.search(q, k, filters=use, rescue=True, **view)
-            self.rescued += self.index.rescued - before
-            return s, ids
-        s, ids = self.index.search(q, k, filters=use, **view)
-        short = (ids < 0).any(dim=1)
-        if bool(short.any()):
-            # a -1 is padding (fewer matching points than k) unless the pass left the
-            # query unanswered (tier 3: more than 16384 rows tied within the error band
-            # of its k-th best on the large-k pass). Only then, re-run those queries on
-            # the full exact pass: an unanswered query must never read as "no documents"
-            # (ADVICE r5).
-            n_un = self.index.unanswered()
-            if n_un > self._unanswered:
-                redo = torch.nonzero(short).reshape(-1).tolist()
-                s2, i2 = self.index.search(q[redo], k, filters=use[redo] if use is not None
-                                           else None, full=True, **view)
-                s[redo] = s2
-                ids[redo] = i2
-                self.rescued += len(redo)
-            self._unanswered = n_un
-        return s, ids
-
-    def search_mmr(self, queries, limits, filters: list, diversity, candidates):
-        """search with MMR re-selection, per request b: limits[b] hits chosen at diversity[b]
-        from its candidates[b] nearest points (clamped to the collection's count) — one
-        search at C = the largest of them, one MMR launch with per-query candidate counts.
-        A request at diversity 0 with candidates = its limit is the plain search. Returns
-        per request [(row, score)] in selection order."""
-        with self.lock:
-            B = len(filters)
-            out = [[] for _ in range(B)]
-            count = self.index.count
-            live = [i for i, f in enumerate(filters) if f is not None and limits[i] >= 1]
-            if not live or count == 0:
-                return out
-            ncand = np.minimum(np.asarray([candidates[i] for i in live], np.int64), count)
-            ncand = np.maximum(ncand, 1).astype(np.int32)
-            lim = [int(limits[i]) for i in live]
-            C = int(ncand.max())
-            k = min(max(lim), C)
-            s, ids = self._lists(queries, filters, live, C)
-            s, ids = self.index.mmr(s, ids, k, np.asarray([diversity[i] for i in live],
-                                                          np.float32), ncand)
-            s = s.cpu().numpy()
-            ids = ids.cpu().numpy()
-            for j, i in enumerate(live):
-                out[i] = [(int(r), float(sc)) for r, sc in zip(ids[j], s[j]) if r >= 0][:lim[j]]
-            return out
-
-    def search_points_mmr(self, queries, limits, filters: list, diversity, candidates,
-                          with_vectors=False):
-        """search_mmr with every hit resolved to its ScoredPoint under the same hold of the
-        lock (see search_points)."""
-        with self.lock:
-            return [[self.point(r, s, True, with_vectors) for r, s in h]
-                    for h in self.search_mmr(queries, limits, filters, diversity, candidates)]
-
-    def search_fusion(self, requests: list):
-        """Fusion queries. `requests`: per request (rrf_k, [(vector, Filter or
-        None, limit), ...], limit), as fusion_params returns them. Every prefetch of every
-        request rides one batched search at C = the largest prefetch limit (clamped to the
-        collection's count); the lists are arranged [B, Lmax, C] on the device, each cut to
-        its own limit by ncand, and fused by rag_fuse_rrf in one launch per distinct rrf_k. A
-        prefetch whose filter can match nothing, or whose limit is < 1, is an empty list and
-        is not searched. Returns per request [(row, fused score)], best first."""
-        with self.lock:
-            out = [[] for _ in requests]
-            count = self.index.count
-            # every filter is compiled, so that a refusal does not depend on the limits
-            compiled = [[self.compile_filter(f) for _, f, _ in pres] for _, pres, _ in requests]
-            qs, filters, where = [], [], []          # the searched prefetches, flattened
-            for b, (_, pres, limit) in enumerate(requests):
-                if limit < 1 or count == 0:
-                    continue
-                for l, (vec, _, plim) in enumerate(pres):
-                    if compiled[b][l] is not None and plim >= 1:
-                        qs.append(vec)
-                        filters.append(compiled[b][l])
-                        where.append((b, l, min(plim, count)))
-            if not qs:
-                return out
-            live = sorted({b for b, _, _ in where})
-            slot = {b: j for j, b in enumerate(live)}
-            Lmax = max(len(requests[b][1]) for b in live)
-            C = max(n for _, _, n in where)
-            if Lmax * C > FUSION_MAX_ENTRIES:
-                raise ValueError(f"fusion: {Lmax} prefetches of up to {C} hits are {Lmax * C} "
-                                 f"entries; at most {FUSION_MAX_ENTRIES} (prefetches x the "
-                                 "largest prefetch limit) are fused")
-            _, ids = self._lists(_stack_queries(qs, self.dim), filters, list(range(len(qs))), C)
-            dev = ids.device
-            rows = torch.full((len(live), Lmax, C), -1, dtype=torch.int64, device=dev)
-            at = np.asarray([(slot[b], l) for b, l, _ in where], dtype=np.int64)
-            rows[torch.from_numpy(at[:, 0]).to(dev), torch.from_numpy(at[:, 1]).to(dev)] = ids
-            ncand = np.zeros((len(live), Lmax), dtype=np.int32)
-            ncand[at[:, 0], at[:, 1]] = [n for _, _, n in where]
-            lim = [int(requests[b][2]) for b in live]
-            k = min(max(lim), Lmax * C)
-            by_k: dict[int, list] = {}
-            for j, b in enumerate(live):
-                by_k.setdefault(requests[b][0], []).append(j)
-            for rrf_k, members in by_k.items():
-                if len(members) == len(live):
-                    s, r = fuse_rrf(rows, k, rrf_k, ncand)
-                else:
-                    sel = torch.as_tensor(members, device=dev)
-                    s, r = fuse_rrf(rows[sel], k, rrf_k, ncand[members])
-                s = s.cpu().numpy()
-                r = r.cpu().numpy()
-                for m, j in enumerate(members):
-                    out[live[j]] = [(int(x), float(sc)) for x, sc in zip(r[m], s[m])
-                                    if x >= 0][:lim[j]]
-            return out
-
-    def search_points_fusion(self, requests: list, with_vectors=False):
-        """search_fusion with every hit resolved to its ScoredPoint (score = the fused score)
-        under the same hold of the lock (see search_points)."""
-        with self.lock:
-            return [[self.point(r, s, True, with_vectors) for r, s in h]
-                    for h in self.search_fusion(requests)]
-
-    def search_groups(self, queries, group_by: str, limit: int, group_size: int, filters: list,
-                      with_vectors=False, candidates: int | None = None,
-                      widen: int | None = None):
-        """Grouped search (ragmi.groups.search_groups): per request the `limit`
-        best groups of points sharing a value of tag field `group_by`, each with its
-        `group_size` best hits — exact, whatever `candidates` / `widen` (policy) say. Returns
-        per request a list of PointGroup (id = the payload value) whose hits are resolved to
-        ScoredPoints under the same hold of the lock (see search_points). The route counters
-        accumulate in `group_stats`."""
-        if group_by not in self.tags.fields:
-            raise UnsupportedFilter(
-                f"group_by {group_by!r} is not an indexed keyword field {self.tags.fields}; "
-                "create the collection with payload_tag_fields")
-        f = self.tags.fields.index(group_by)
-        shift = 16 * f
-        key_mask = 0xFFFF << shift
-        with self.lock:
-            B = len(filters)
-            out = [[] for _ in range(B)]
-            count = self.index.count
-            codes = self.tags.codes[f]
-            live = [i for i, fl in enumerate(filters) if fl is not None]
-            if any(isinstance(filters[i], FilterProgram) for i in live):
-                raise UnsupportedFilter(
-                    "query_points_groups takes only Filter(must=[FieldCondition(key, "
-                    "match=MatchValue)]); a grouped search under a general filter (should, "
-                    "must_not, MatchAny, ...) is out of scope: its exactness ladder composes "
-                    "(mask, value) pairs")
-            if limit < 1 or group_size < 1 or not live or count == 0 or not codes:
-                return out
-            # neither clamp can change a result: there are no more groups than codes, no
-            # more hits than points
-            G, S = min(int(limit), len(codes)), min(int(group_size), count)
-            if G > GROUPS_MAX or G * S > GROUPS_MAX_CELLS:
-                raise ValueError(f"grouped search: at most {GROUPS_MAX} groups and "
-                                 f"{GROUPS_MAX_CELLS} hits in all (limit x group_size)")
-            every = [c << shift for c in codes.values()]
-            possible = [[filters[i][1] & key_mask] if filters[i][0] & key_mask else every
-                        for i in live]
-            q, use = self._live_queries(queries, filters, live)
-            res = groups.search_groups(self.index, q, use, key_mask, possible, G, S, candidates,
-                                       widen, search=self._exact_lists, stats=self.group_stats)
-            for i, found in zip(live, res):
-                out[i] = [models.PointGroup(
-                    hits=[self.point(r, s, True, with_vectors) for r, s in hits],
-                    id=self.tags.value_of(f, key >> shift)) for key, hits in found]
-            return out
-
-    def point(self, row: int, score: float, with_payload=True, with_vectors=False):
-        payload = self.payloads[row] if with_payload else None
-        vec = None
-        if with_vectors:
-            vec = (self.index.export_rows32(row, 1)[0] if self.index.storage == "fp32" else
-                   self.index.export_rows(row, 1)[0].view(np.float16).astype(np.float32)).tolist()
-        return models.ScoredPoint(id=self.row_ids[row], version=self.versions[row],
-                                  score=score, payload=payload, vector=vec)
 
 
 MMR_DIVERSITY = 0.5          # Mmr(diversity=None)
@@ -784,19 +150,39 @@ def fusion_params(query, prefetch, limit, query_filter=None):
     return int(rrf_k), out
 
 
-def _stack_queries(qs: list, dim: int):
-    """Query vectors (lists, arrays, tensors) as one [n, dim] batch: a tensor when any of them
-    is one, else a float32 array."""
-    if any(isinstance(x, torch.Tensor) for x in qs):
-        dev = next(x.device for x in qs if isinstance(x, torch.Tensor))
-        Q = torch.stack([(x if isinstance(x, torch.Tensor) else
-                          torch.as_tensor(np.asarray(x, np.float32))).to(dev).reshape(-1)
-                         for x in qs])
-    else:
-        Q = np.stack([np.asarray(x, np.float32).reshape(-1) for x in qs])
-    if Q.shape[1] != dim:
-        raise ValueError(f"every query must be one {dim}-dim vector")
-    return Q
+FUSION, MMR, PLAIN = "fusion", "mmr", "plain"      # the routes of a request
+
+
+def route_of(query, prefetch=None) -> str:
+    """The route of a request, decided once: FUSION (prefetched lists fused), MMR (a
+    NearestQuery with an Mmr) or PLAIN."""
+    if prefetch is not None or isinstance(query, (models.FusionQuery, models.RrfQuery)):
+        return FUSION
+    return MMR if isinstance(query, models.NearestQuery) and query.mmr is not None else PLAIN
+
+
+def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=False) -> list:
+    """The requests of one route (QueryRequests, in order) answered by one call on the
+    collection: per request its resolved points. On the MMR route a request without an Mmr
+    rides at diversity 0 with its own limit as candidate count."""
+    if route == FUSION:
+        par = [fusion_params(r.query, r.prefetch, r.limit, r.filter) for r in reqs]
+        return col.search_points_fusion(
+            [(rrf_k, pres, int(r.limit)) for (rrf_k, pres), r in zip(par, reqs)], with_vectors)
+    qs, filters, limits, div, cand = [], [], [], [], []
+    for r in reqs:
+        q, mmr = nearest_of(r.query)
+        qs.append(q)
+        filters.append(compile_filter(col.tags, r.filter))
+        if route == MMR:
+            d, c = mmr_params(mmr, r.limit) if mmr is not None else (0.0, max(int(r.limit), 1))
+            div.append(d)
+            cand.append(c)
+        limits.append(int(r.limit))
+    Q = stack_queries(qs, col.dim, one=one)
+    if route == PLAIN:
+        return col.search_points(Q, max(limits), filters, with_vectors)
+    return col.search_points_mmr(Q, limits, filters, div, cand, with_vectors)
 
 
 def _payloads(points: list, with_payload) -> list:
@@ -939,90 +325,46 @@ class QdrantClient:
     def query_points(self, collection_name: str, query=None, limit: int = 10,
                      query_filter: models.Filter | None = None, with_payload=True,
                      with_vectors=False, prefetch=None, **kwargs) -> models.QueryResponse:
+        """One request on its route (route_of, answer). A plain request with a limit the scan
+        serves rides the coalescer; fusion and MMR requests never do: their prefetches, their
+        candidate search, are passes of their own."""
         col = self._col(collection_name)
-        if prefetch is not None or is_fusion(query):
-            # a fusion request never rides the coalescer: its prefetches are their own batch
-            rrf_k, pres = fusion_params(query, prefetch, limit, query_filter)
-            pts = col.search_points_fusion([(rrf_k, pres, int(limit))], with_vectors)[0]
-            return models.QueryResponse(points=_payloads(pts, with_payload))
-        query, mmr = nearest_of(query)
-        flt = col.compile_filter(query_filter)
-        if mmr is not None:
-            # an MMR request never rides the coalescer: its candidate search is its own pass
-            div, cand = mmr_params(mmr, limit)
-            q = query if isinstance(query, torch.Tensor) else np.asarray(query, dtype=np.float32)
-            pts = col.search_points_mmr(q.reshape(1, -1), [int(limit)], [flt], [div], [cand],
-                                        with_vectors)[0]
-        elif self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
-            q = (query.detach().float().cpu().numpy() if isinstance(query, torch.Tensor)
-                 else np.asarray(query, dtype=np.float32))
-            if q.shape != (col.dim,):
-                q = q.reshape(-1)
-                if q.shape != (col.dim,):
-                    raise ValueError(f"query must be one {col.dim}-dim vector")
+        route = route_of(query, prefetch)
+        if route == PLAIN and self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
+            flt = compile_filter(col.tags, query_filter)
+            q = stack_queries([nearest_of(query)[0]], col.dim, one=True, host=True)[0]
             pts = col.coalescer.search(q, int(limit), flt)
         else:
-            q = query if isinstance(query, torch.Tensor) else np.asarray(query, dtype=np.float32)
-            q = q.reshape(1, -1)
-            pts = col.search_points(q, int(limit), [flt], with_vectors)[0]
+            req = models.QueryRequest(query=query, filter=query_filter, limit=limit,
+                                      prefetch=prefetch)
+            pts = answer(col, route, [req], with_vectors, one=True)[0]
         return models.QueryResponse(points=_payloads(pts, with_payload))
 
     def query_batch_points(self, collection_name: str, requests: list,
                            **kwargs) -> list[models.QueryResponse]:
-        """One GPU scan for the whole batch (per-query filters ride along in the kernel). With
-        MMR requests in it (QueryRequest.query = NearestQuery(..., mmr=Mmr(...))): one search
-        at the batch's largest candidate count and one MMR launch, the plain requests riding
-        at diversity 0 with their own limit as candidate count — unless a plain limit exceeds
-        RAG_MMR_MAX_CANDIDATES, in which case the plain requests are searched on their own.
-        Fusion requests (QueryRequest.prefetch with a FusionQuery / RrfQuery) are answered
-        together by one search_points_fusion call, the remaining requests as a batch of their
-        own, and the results are scattered back in request order."""
+        """One GPU scan for the whole batch (per-query filters ride along in the kernel). The
+        requests are partitioned by route once, each non-empty route is answered by one call
+        (answer), fusion first, and the results are scattered back in request order. With MMR
+        requests in the batch the plain requests ride with them, at diversity 0 with their own
+        limit as candidate count: one search at the batch's largest candidate count and one
+        MMR launch — unless a plain limit exceeds RAG_MMR_MAX_CANDIDATES, in which case the
+        plain requests are searched on their own."""
         col = self._col(collection_name)
-        if not requests:
-            return []
-        fus = [i for i, r in enumerate(requests)
-               if getattr(r, "prefetch", None) is not None or is_fusion(r.query)]
-        if fus:
-            par = [fusion_params(requests[i].query, requests[i].prefetch, requests[i].limit,
-                                 requests[i].filter) for i in fus]
-            out: list = [None] * len(requests)
-            hits = col.search_points_fusion(
-                [(rrf_k, pres, int(requests[i].limit)) for i, (rrf_k, pres) in zip(fus, par)])
-            for i, h in zip(fus, hits):
-                out[i] = models.QueryResponse(points=_payloads(h, requests[i].with_payload))
-            rest = [i for i in range(len(requests)) if out[i] is None]
-            for i, resp in zip(rest, self.query_batch_points(
-                    collection_name, [requests[i] for i in rest], **kwargs)):
-                out[i] = resp
-            return out
-        unwrapped = [nearest_of(r.query) for r in requests]
-        qs = [v for v, _ in unwrapped]
-        Q = torch.stack([x if isinstance(x, torch.Tensor) else
-                         torch.as_tensor(np.asarray(x, np.float32)) for x in qs]) \
-            if any(isinstance(x, torch.Tensor) for x in qs) else np.asarray(qs, np.float32)
-        filters = [col.compile_filter(r.filter) for r in requests]
-        if all(m is None for _, m in unwrapped):
-            hits = col.search_points(Q, max(int(r.limit) for r in requests), filters)
-        else:
-            par = [mmr_params(m, r.limit) if m is not None else (0.0, max(int(r.limit), 1))
-                   for (_, m), r in zip(unwrapped, requests)]
-            limits = [int(r.limit) for r in requests]
-            if max(c for _, c in par) <= MMR_MAX_CANDIDATES:
-                hits = col.search_points_mmr(Q, limits, filters, [d for d, _ in par],
-                                             [c for _, c in par])
-            else:
-                plain = [i for i, (_, m) in enumerate(unwrapped) if m is None]
-                rest = [i for i, (_, m) in enumerate(unwrapped) if m is not None]
-                hits = [None] * len(requests)
-                for i, h in zip(plain, col.search_points(
-                        Q[plain], max(limits[i] for i in plain), [filters[i] for i in plain])):
-                    hits[i] = h
-                for i, h in zip(rest, col.search_points_mmr(
-                        Q[rest], [limits[i] for i in rest], [filters[i] for i in rest],
-                        [par[i][0] for i in rest], [par[i][1] for i in rest])):
-                    hits[i] = h
-        return [models.QueryResponse(points=_payloads(h[:int(r.limit)], r.with_payload))
-                for r, h in zip(requests, hits)]
+        routes: dict = {FUSION: [], PLAIN: [], MMR: []}
+        for i, r in enumerate(requests):
+            routes[route_of(r.query, getattr(r, "prefetch", None))].append(i)
+        if routes[MMR] and all(int(requests[i].limit) <= MMR_MAX_CANDIDATES
+                               for i in routes[PLAIN]):
+            routes = {FUSION: routes[FUSION], MMR: sorted(routes[MMR] + routes[PLAIN])}
+        out: list = [None] * len(requests)
+        for route, members in routes.items():
+            if members:
+                hits = answer(col, route, [requests[i] for i in members])
+                for i, h in zip(members, hits):
+                    r = requests[i]
+                    out[i] = models.QueryResponse(
+                        points=_payloads(h[:int(r.limit)], r.with_payload))
+        return out
 
     def query_points_groups(self, collection_name: str, query=None, group_by: str | None = None,
                             limit: int = 10, group_size: int = 3,
@@ -1045,9 +387,8 @@ class QdrantClient:
         if mmr is not None:
             raise ValueError("a grouped query cannot be an MMR query (NearestQuery.mmr)")
         flt = col.compile_filter(query_filter)
-        q = query if isinstance(query, torch.Tensor) else np.asarray(query, dtype=np.float32)
-        found = col.search_groups(q.reshape(1, -1), group_by, int(limit), int(group_size), [flt],
-                                  with_vectors)[0]
+        found = col.search_groups(stack_queries([query], col.dim, one=True), group_by, int(limit),
+                                  int(group_size), [flt], with_vectors)[0]
         for g in found:
             _payloads(g.hits, with_payload)
         return models.GroupsResult(groups=found)

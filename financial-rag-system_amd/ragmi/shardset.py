@@ -11,7 +11,7 @@ collection grows by `upsert` with no total known in advance (ingest.py:171-175);
 ranges would fill GPU 0 first, stripes fill every shard evenly at every size. Within a shard
 local order is global order, so each shard's exact top-k by (score desc, local row asc) is
 its exact top-k by (score desc, global row asc) and the merged list equals the unsharded one
-bit for bit. Everything here works in global rows: a ShardSet offers what `qdrant.Collection`
+bit for bit. Everything here works in global rows: a ShardSet offers what `collection.Collection`
 and `ragmi.store` use of a FlatIndex.
 """
 from __future__ import annotations
@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .index import FlatIndex, ListOps, _as_dev, host_or_tensor, plan_removal, view_blob
 
 MAX_SHARDS = 64      # RAG_MAX_SHARDS in include/ragmi.h
 SHARDSET_FULL = 1    # RAG_SHARDSET_FULL
@@ -159,13 +160,12 @@ def _keeps_device(fn):
     return wrapped
 
 
-class ShardSet:
+class ShardSet(ListOps):
     """N FlatIndex shards + the C shard-set handle, addressed in global rows. `devices`: one
     device index per shard (see parse_devices); `device`, the merge device, is the first."""
 
     @_keeps_device
     def __init__(self, dim: int = 384, devices=(0,), capacity: int = 0, storage: str = "fp16"):
-        from .index import FlatIndex
         devs = parse_devices(devices)
         if devs is None:
             raise ValueError("ShardSet needs a list of devices")
@@ -249,7 +249,7 @@ class ShardSet:
         """FlatIndex.upsert in global rows: each row goes to its shard."""
         r = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
         r = r.astype(np.int64).reshape(-1)
-        v = vectors if isinstance(vectors, torch.Tensor) else np.asarray(vectors, np.float32)
+        v = host_or_tensor(vectors)
         if v.ndim != 2 or v.shape[1] != self.dim or v.shape[0] != r.shape[0]:
             raise ValueError(f"vectors must be [n, {self.dim}] with one row slot each")
         if r.size and (int(r.min()) < 0 or int(r.max()) >= self.capacity):
@@ -283,7 +283,6 @@ class ShardSet:
         memory) and scattered there. Local sources lie at or past their shard's new count and
         local destinations below it, so no pair waits for another. Returns the global plan
         (src, dst, new_count)."""
-        from .index import plan_removal
         src, dst, n1 = plan_removal(self._count, global_rows)
         for (s, d), (ls, ld) in shard_moves(src, dst, self.n).items():
             cnt = shard_count(n1, d, self.n)
@@ -303,13 +302,13 @@ class ShardSet:
         return src, dst, n1
 
     @_keeps_device
-    def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None):
-        """FlatIndex.select_rows over the set: each shard's selection mapped to global rows,
-        merged ascending on the merge device: (rows int64 cuda tensor, total). The first
-        `cap` global matches lie among each shard's first `cap`."""
+    def _select(self, cap, select):
+        """`select(shard)`'s (local rows, total) of every shard mapped to global rows and merged
+        ascending on the merge device: (rows int64 cuda tensor, total). The first `cap` global
+        matches lie among each shard's first `cap`."""
         parts, total = [], 0
         for s, shard in enumerate(self.shards):
-            rows, n = shard.select_rows(tag_mask, tag_value, cap)
+            rows, n = select(shard)
             total += n
             if rows.numel():
                 parts.append((rows * self.n + s).to(self.device))
@@ -318,21 +317,18 @@ class ShardSet:
         merged = torch.sort(torch.cat(parts)).values
         return (merged if cap is None else merged[:int(cap)]), total
 
-    @_keeps_device
+    def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None):
+        """FlatIndex.select_rows over the set (_select)."""
+        return self._select(cap, lambda shard: shard.select_rows(tag_mask, tag_value, cap))
+
     def select_rows_view(self, programs, cap: int | None = None):
-        """FlatIndex.select_rows_view over the set, merged as select_rows merges."""
-        parts, total = [], 0
-        for s, shard in enumerate(self.shards):
-            rows, n = shard.select_rows_view(programs, cap)
-            total += n
-            if rows.numel():
-                parts.append((rows * self.n + s).to(self.device))
-        if not parts:
-            return torch.empty((0,), dtype=torch.int64, device=self.device), total
-        merged = torch.sort(torch.cat(parts)).values
-        return (merged if cap is None else merged[:int(cap)]), total
+        """FlatIndex.select_rows_view over the set (_select)."""
+        return self._select(cap, lambda shard: shard.select_rows_view(programs, cap))
 
     # ---------------------------------------------------------------- search
+    def _search_args(self, queries, k, filters):
+        return self.shards[0]._search_args(queries, k, filters)     # on the merge device
+
     @_keeps_device
     def search(self, queries, k: int, filters=None, full: bool = False, rescue: bool = False,
                programs=None, n_programs: int | None = None):
@@ -346,8 +342,7 @@ class ShardSet:
         Synchronises when rescue is set. `programs`: as FlatIndex.search — every shard
         searches over the blob's filter view of its tags (rag_shardset_search_view), and the
         rescue re-runs with the same blob."""
-        from .index import view_blob
-        q, B, f = self.shards[0]._search_args(queries, k, filters)
+        q, B, f = self._search_args(queries, k, filters)
         out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
         out_i = torch.empty((B, k), dtype=torch.int64, device=self.device)
         empty = torch.empty((self.n, B), dtype=torch.uint8, device=self.device)
@@ -384,7 +379,6 @@ class ShardSet:
     def _mmr_scratch(self, slots: int):
         """The scratch FlatIndex on the merge device that mmr copies the candidates' rows into
         (same dim and storage as the shards), created on first use and grown on demand."""
-        from .index import FlatIndex
         if self._scratch is None:
             self._scratch = FlatIndex(self.dim, slots, self.device, self.storage)
         elif self._scratch.capacity < slots:
@@ -400,7 +394,6 @@ class ShardSet:
         scratch FlatIndex at slot b * C + j; rag_index_mmr runs there over the slots and its
         positions are mapped back to global rows. The rows travel unchanged, so the result is
         FlatIndex.mmr's on the same rows bit for bit. On the merge device's current stream."""
-        from .index import _as_dev
         s = _as_dev(cand_scores, torch.float32, self.device)
         g = _as_dev(cand_rows, torch.int64, self.device)
         if s.dim() != 2 or s.shape != g.shape:
@@ -429,19 +422,6 @@ class ShardSet:
         rows = torch.where(pos >= 0, picked, -1)
         return (out_s, rows, pos) if with_pos else (out_s, rows)
 
-    def search_mmr(self, queries, k: int, diversity, candidates, filters=None):
-        """FlatIndex.search_mmr over the set: search at k = C (global rows), then mmr."""
-        from .index import MMR_MAX_CANDIDATES, per_query
-        q, B, f = self.shards[0]._search_args(queries, k, filters)
-        nc = per_query(candidates, B, np.int32, "candidates")
-        if B and int(nc.min()) < 1:
-            raise ValueError("candidates must be >= 1")
-        C = int(nc.max()) if B else 1
-        if C > MMR_MAX_CANDIDATES:
-            raise ValueError(f"at most {MMR_MAX_CANDIDATES} MMR candidates per query")
-        s, g = self.search(q, C, f)
-        return self.mmr(s, g, k, diversity, None if B and (nc == C).all() else nc)
-
     # ---------------------------------------------------------------- grouped search
     @_keeps_device
     def gather_tags(self, global_rows) -> torch.Tensor:
@@ -449,7 +429,6 @@ class ShardSet:
         (it is given -1 for the others, which the gather answers with 0), the per-shard results
         are copied to the merge device and combined. int32 tag bits, the shape of the rows,
         0 for a row outside [0, capacity)."""
-        from .index import _as_dev
         g = _as_dev(global_rows, torch.int64, self.device)
         valid = (g >= 0) & (g < self.capacity)
         out = torch.zeros(g.shape, dtype=torch.int32, device=self.device)
@@ -458,17 +437,6 @@ class ShardSet:
             local = torch.where(own, local_of(g, self.n), -1)
             out |= shard.gather_tags(local.to(shard.device)).to(self.device)
         return out
-
-    @_keeps_device
-    def group_select(self, cand_scores, cand_rows, key_mask: int, G: int, S: int, ncand=None,
-                     with_pos: bool = False):
-        """FlatIndex.group_select in global rows: gather_tags over the shards, then the same
-        rag_group_select on the merge device. The selection reads only the lists, and global
-        rows travel unchanged, so the result is the one-index result bit for bit."""
-        from .index import _as_dev, group_select_tags
-        g = _as_dev(cand_rows, torch.int64, self.device)
-        return group_select_tags(_as_dev(cand_scores, torch.float32, self.device), g,
-                                 self.gather_tags(g), key_mask, G, S, ncand, with_pos)
 
     @_keeps_device
     def unanswered(self) -> int:

@@ -11,7 +11,7 @@ A shard directory holds exactly what the GPU index stores, so loading is a byte 
                      (their fp16 scan copy is re-derived on load by the same rounding)
   tags.u32.npy       [N] uint32     — per-row payload tags (PayloadTags codes)
 
-A collection directory adds the host-side state of `qdrant.Collection`:
+A collection directory adds the host-side state of `collection.Collection`:
 
   collection.json    name, dim, distance, tag fields + codebooks, op counter
   points.jsonl       one line per row, in row order: {"id": ..., "version": v, "payload": {...}}
@@ -214,7 +214,7 @@ def load_sharded(sharded, path: str, chunk_rows: int = CHUNK_ROWS) -> int:
 
 # ---------------------------------------------------------------- collections
 def save_collection(col, path: str) -> None:
-    """qdrant.Collection -> collection directory."""
+    """collection.Collection -> collection directory."""
     os.makedirs(path, exist_ok=True)
     with col.lock:
         save_index(col.index, os.path.join(path, "shard"))
@@ -231,10 +231,10 @@ def save_collection(col, path: str) -> None:
 
 
 def load_collection(path: str, device=None, devices=None):
-    """collection directory -> qdrant.Collection (rows, tags, ids, payloads, versions).
+    """collection directory -> collection.Collection (rows, tags, ids, payloads, versions).
     `devices`: load into a ShardSet over these devices. The directory holds the rows in global
     order whatever the shard count was at save time, so any count loads any directory."""
-    from .qdrant import Collection
+    from .collection import Collection
     with open(os.path.join(path, "collection.json")) as f:
         cj = json.load(f)
     meta = read_meta(os.path.join(path, "shard"))

@@ -5,12 +5,13 @@ index."""
 import ctypes
 import os
 import re
-import threading
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+
+import _stubs as S
 
 
 # ------------------------------------------------------------------ 1. the removal rule
@@ -238,21 +239,13 @@ class _StubIndex:
 
 def stub_collection(monkeypatch):
     import torch
-    from ragmi.qdrant import Collection, PayloadTags
 
     class _NoStream:
         def synchronize(self):
             pass
 
     monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: _NoStream())
-    col = Collection.__new__(Collection)
-    col.name, col.dim = "t", 2
-    col.index = _StubIndex()
-    col.lock = threading.RLock()
-    col.tags = PayloadTags()
-    col.id_to_row, col.row_ids, col.payloads, col.versions = {}, [], [], []
-    col.op = 0
-    return col
+    return S.stub_collection(_StubIndex(), dim=2)
 
 
 def consistent(col, alive):

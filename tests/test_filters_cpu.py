@@ -6,11 +6,11 @@ index."""
 import itertools
 import os
 import re
-import threading
 
 import numpy as np
 import pytest
 
+import _stubs as S
 from _filters_ref import absent, cond_matches, matches   # noqa: F401
 from conftest import ROOT
 
@@ -269,12 +269,7 @@ def legacy_filters():
 
 
 def bare_collection():
-    from ragmi.qdrant import Collection
-    col = Collection.__new__(Collection)
-    col.name, col.dim = "t", 2
-    col.tags = ingested_tags()
-    col.lock = threading.RLock()
-    return col
+    return S.stub_collection(_StubIndex([]), dim=2, tags=ingested_tags())
 
 
 def test_compile_filter_keeps_the_legacy_path():
@@ -328,7 +323,8 @@ class _StubIndex:
     def unanswered(self):
         return 0
 
-    def search(self, q, k, filters=None, full=False, programs=None, n_programs=None):
+    def search(self, q, k, filters=None, full=False, programs=None, n_programs=None,
+               rescue=False):
         import torch
         from ragmi.filters import eval_view_np, view_programs
         col = self.tag if programs is None else eval_view_np(programs, self.tag)
@@ -356,14 +352,12 @@ class _StubIndex:
 
 def routed_collection():
     rng = np.random.default_rng(3)
-    col = bare_collection()
     n = 500
-    col.payloads = [payload_of(int(rng.integers(0, 7)), int(rng.integers(0, 5)), int(v))
-                    for v in rng.integers(0, 4, n)]
-    col.row_ids = list(range(n))
-    col.index = _StubIndex([col.tags.tag(p) for p in col.payloads])
-    col._unanswered = col.rescued = 0
-    return col
+    payloads = [payload_of(int(rng.integers(0, 7)), int(rng.integers(0, 5)), int(v))
+                for v in rng.integers(0, 4, n)]
+    tags = ingested_tags()
+    return S.stub_collection(_StubIndex([tags.tag(p) for p in payloads]), dim=2,
+                             payloads=payloads, tags=tags)
 
 
 def brute(col, flt, k):

@@ -5,7 +5,6 @@ index."""
 import ctypes
 import os
 import re
-import threading
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import pytest
 from conftest import ROOT
 
 import _mmr_ref as R
+import _stubs as S
 
 
 # ------------------------------------------------------------------ 1. models and defaults
@@ -147,7 +147,7 @@ class _StubIndex:
         self.count = count
         self.calls = []
 
-    def search(self, q, k, filters=None, full=False):
+    def search(self, q, k, filters=None, full=False, rescue=False):
         import torch
         B = len(q)
         self.calls.append(("search", B, k, None if filters is None else filters.tolist()))
@@ -165,25 +165,9 @@ class _StubIndex:
 
 
 def stub_client(count=40):
-    from ragmi.qdrant import Coalescer, Collection, PayloadTags, QdrantClient
-    col = Collection.__new__(Collection)
-    col.name, col.dim = "t", 4
-    col.index = _StubIndex(count)
-    col.lock = threading.RLock()
-    col.tags = PayloadTags()
-    col.row_ids = list(range(100, 100 + count))
-    col.id_to_row = {pid: r for r, pid in enumerate(col.row_ids)}
-    col.payloads = [{"ticker": "AMD" if r % 2 else "AAPL", "n": r} for r in range(count)]
-    for p in col.payloads:
-        col.tags.tag(p)
-    col.versions = [1] * count
-    col.op = 1
-    col._unanswered = 0
-    col.rescued = 0
-    col.coalescer = Coalescer(col, 0.0, 32, search=col.search_points)
-    client = QdrantClient()
-    client._collections["t"] = col
-    return client, col
+    return S.stub_client(S.stub_collection(
+        _StubIndex(count), dim=4, ids=range(100, 100 + count),
+        payloads=[{"ticker": "AMD" if r % 2 else "AAPL", "n": r} for r in range(count)]))
 
 
 def test_nearest_query_without_mmr_is_the_plain_path():

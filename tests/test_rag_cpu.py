@@ -111,15 +111,26 @@ def test_retrieve_swallows_like_the_reference(monkeypatch):
 class _StubIndex:
     """FlatIndex stand-in for Collection.search's host logic: the first search leaves query 1
     unanswered (ids -1, unanswered() + 1) as a large-k pass does past 16384 near-ties; the full
-    pass answers it."""
+    pass answers it. `launch` stands for the one launch behind FlatIndex.search, and search
+    applies the index's own rescue rule (ragmi.index.rescue_unanswered) around it."""
 
     def __init__(self, count, k_full_ids):
         self.count = count
         self.n_un = 0
         self.calls = []
         self.k_full_ids = k_full_ids
+        self._unanswered = 0
+        self.rescued = 0
 
-    def search(self, q, k, filters=None, full=False):
+    def search(self, q, k, filters=None, full=False, rescue=False):
+        from ragmi.index import rescue_unanswered
+        s, ids = self.launch(q, k, filters, full)
+        if rescue and not full:
+            rescue_unanswered(self, s, ids, lambda redo: self.launch(
+                q[redo], k, None if filters is None else filters[redo], True))
+        return s, ids
+
+    def launch(self, q, k, filters=None, full=False):
         import torch
         B = len(q)
         self.calls.append((B, k, full))
@@ -139,23 +150,17 @@ class _StubIndex:
 
 def test_collection_reanswers_unanswered_queries_on_the_full_pass():
     import numpy as np
-    import threading
-    from ragmi.qdrant import Collection, PayloadTags
-    col = Collection.__new__(Collection)
-    col.index = _StubIndex(count=100, k_full_ids=list(range(50, 100)))
-    col.lock = threading.RLock()
-    col._unanswered = 0
-    col.rescued = 0
-    col.tags = PayloadTags()
+    import _stubs as S
+    col = S.stub_collection(_StubIndex(count=100, k_full_ids=list(range(50, 100))), dim=384)
     out = col.search(np.zeros((3, 384), np.float32), 40, [(0, 0)] * 3)
     assert col.index.calls == [(3, 40, False), (1, 40, True)]
     assert [r for r, _ in out[1]] == list(range(50, 90))      # answered, not "no documents"
     assert [r for r, _ in out[0]] == list(range(40))
-    assert col.rescued == 1 and col._unanswered == 1
+    assert col.rescued == 1 and col.index._unanswered == 1
     # padding -1 (fewer matching points than k) with no unanswered query: no second pass
     col.index.n_un = 0
-    col._unanswered = 0
-    col.index.search = lambda q, k, filters=None, full=False: (
+    col.index._unanswered = 0
+    col.index.launch = lambda q, k, filters=None, full=False: (
         __import__("torch").tensor([[0.9, float("-inf")]]),
         __import__("torch").tensor([[3, -1]]))
     col.index.unanswered = lambda: 0
