@@ -136,7 +136,10 @@ struct ExactStats {
 //     tier 2 (rescan_kernel): otherwise the shard is streamed once more for this query by
 //       the rescan kernel launched after every select (its workgroups split the shard); here
 //       select only records L and e_k. Only inputs with more than 32 in-band rows inside one
-//       wave's share of the tiles (or a seed above L) get there. (Round 2 ran this pass
+//       wave's share of the tiles (or a seed above L) get there. After an int8 prescan
+//       (scan_kernel_i8) the list scores are upper bounds u >= e: a row outside A has
+//       e <= u <= a_32, the same check with a := u and eps the prescan's slack; a true top-k
+//       row has u >= e >= e_k >= L, so tier 1 reads the same lists. (Round 2 ran this pass
 //       inside select, on the query's one workgroup: a single-CU pass over the whole shard,
 //       ~0.1 s at 10M rows — unbounded by the chip's bandwidth; VERDICT/ADVICE r2.)
 // ----------------------------------------------------------------------------------------
@@ -159,7 +162,8 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
                                                      float* __restrict__ out_s,
                                                      int64_t* __restrict__ out_i,
                                                      int32_t* __restrict__ out_packed,
-                                                     const float* __restrict__ rows32) {
+                                                     const float* __restrict__ rows32,
+                                                     const float* __restrict__ eps_t2 = nullptr) {
   __shared__ float w_s[4][32];
   __shared__ int64_t w_i[4][32];
   __shared__ int sel[32];
@@ -446,7 +450,9 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
     // here (the rescan writes this query's output)
     if (tid == 0) {
       fb.tier[bq] = 2;
-      fb.t2[2 * bq] = L;
+      // the rescan bands on fp16 MFMA scores: after an int8 prescan (eps_t2 = qprep's fp16
+      // bound; `eps` is then the prescan's) its floor is e_k - the fp16 bound, not this L
+      fb.t2[2 * bq] = eps_t2 ? floor_E - eps_t2[bq] : L;
       fb.t2[2 * bq + 1] = floor_E;
       atomicAdd(&fb.cnt[1], 1ull);
     }

@@ -71,6 +71,11 @@ struct Workspace {
   float* t2_s = nullptr;
   int* t2_i = nullptr;
   int* t2_tk = nullptr;
+  // int8 prescan (indexes that keep the int8 copy): the queries' int8 planes, their u_bound
+  // parameters [32][4] and the certificate's eps for a pass ranked by u (qprep8_kernel)
+  char* qfrag8 = nullptr;
+  float* qp8 = nullptr;
+  float* eps8 = nullptr;
   // large-k path (k > RAG_MAX_K; lk_* kernels), allocated on first use: sample maxima
   // [32][kLkSampleMax], per query thr / count / round flag, round flags, candidates
   // [32][kLkCap]
@@ -219,6 +224,12 @@ struct rag_index {
   // rescoring reads — Qdrant's default Float32 datatype
   int storage = RAG_STORE_FP16;
   float* rows32 = nullptr;
+  // int8 scan copy (dim 384, fp16 storage; prep_kernels.hip): the tile16x64 image and the
+  // per-row (scale, error) meta, both over cap_rows / 16 + 1 tiles (the prescan walks tile
+  // pairs); rebuilt from the stored fp16 rows after every write of `corpus` (requant)
+  char* c8 = nullptr;
+  float* meta8 = nullptr;
+  int prescan = 1;        // rag_index_set_prescan: 0 off, 1 auto, 2 always
   int n_cu = 256;
   int max_wgs = 0;        // scan workgroups at full occupancy
   int scan_wgs = 0;       // D <= 384 scan grid cap: 3/4 of the CUs (launch_search_pass)
@@ -257,7 +268,7 @@ int64_t round16(int64_t n) { return (n + 15) & ~int64_t(15); }
 // The buffers every Workspace of `h` holds from creation to destruction (h->dim, groups and
 // max_wgs set), in allocation order: rag_index_create_ex gives each its own hipMalloc in this
 // order, rag_index_destroy frees them.
-std::array<WsBuf, 19> ws_buffers(const rag_index* h, Workspace& w) {
+std::array<WsBuf, 22> ws_buffers(const rag_index* h, Workspace& w) {
   using namespace ragmi;
   const size_t G = (size_t)h->groups, Q = kQ, dim = (size_t)h->dim;
   const size_t max_lists = (size_t)std::min(h->max_wgs * kWavesPerWG, kMaxLists);
@@ -279,7 +290,38 @@ std::array<WsBuf, 19> ws_buffers(const rag_index* h, Workspace& w) {
           ws_buf(w.t2, G * Q * 2 * 4),
           ws_buf(w.t2_s, G * Q * kRescanMaxWG * 32 * 4),
           ws_buf(w.t2_i, G * Q * kRescanMaxWG * 32 * 4),
-          ws_buf(w.t2_tk, 64, true)};
+          ws_buf(w.t2_tk, 64, true),
+          ws_buf(w.qfrag8, h->c8 ? 4 * (dim / 64) * 64 * 16 : 0),
+          ws_buf(w.qp8, h->c8 ? Q * 4 * 4 : 0),
+          ws_buf(w.eps8, h->c8 ? Q * 4 : 0)};
+}
+
+// Which indexes keep the int8 scan copy
+bool keeps_copy8(const rag_index* h) { return h->dim == 384 && h->storage == RAG_STORE_FP16; }
+
+size_t copy8_bytes(const rag_index* h, int64_t cap_rows) {
+  return (size_t)(cap_rows / 16 + 1) * (h->dim / 64) * 1024;
+}
+size_t meta8_bytes(int64_t cap_rows) { return (size_t)(cap_rows / 16 + 1) * 32 * 4; }
+
+// the copy's two buffers for `cap_rows` rows, zeroed (freed by the caller's DeviceBufs on error)
+int alloc_copy8(const rag_index* h, int64_t cap_rows, DeviceBuf<char>& c8, DeviceBuf<float>& m8) {
+  if (c8.alloc(copy8_bytes(h, cap_rows)) != hipSuccess ||
+      m8.alloc(meta8_bytes(cap_rows)) != hipSuccess)
+    return ragmi::fail(RAG_ENOMEM, "hipMalloc(int8 scan copy) failed");
+  RAG_HIP(hipMemset(c8.p, 0, copy8_bytes(h, cap_rows)));
+  RAG_HIP(hipMemset(m8.p, 0, meta8_bytes(cap_rows)));
+  return RAG_OK;
+}
+
+// The int8 copy of rows[i] (device list) or row0 + i, i < n, rebuilt from the stored fp16 rows:
+// enqueued on `st` right after the kernel that wrote them
+int requant(rag_index* h, const int64_t* rows, int64_t row0, int64_t n, hipStream_t st) {
+  if (!h->c8 || n <= 0) return RAG_OK;
+  ragmi::requant_kernel<384><<<dim3((unsigned)n), dim3(64), 0, st>>>(
+      h->corpus, rows, row0, n, h->cap_rows, h->c8, h->meta8);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
 }
 
 int alloc_corpus(rag_index* h, int64_t cap_rows, half8** corpus, uint32_t** tags) {
@@ -407,6 +449,35 @@ void launch_seed(rag_index* h, Workspace& w, int groups, hipStream_t st,
   thresh_kernel<kCap><<<dim3(kQ, groups), dim3(256), 0, st>>>(w.smax, n_sample, w.eps, w.seed);
 }
 
+// Does a k <= RAG_MAX_K pass of `h` scan the int8 copy (rag_index_set_prescan)? Only an index
+// that keeps the copy (dim 384, fp16 storage). Auto: passes over at least RAG_PRESCAN_MIN_ROWS
+// rows, filtered or not (10M rows: unfiltered 1.82x, per-query ticker filter 1.82x; 500K rows
+// 1.03x; DESIGN.md "int8 prescan"); below that a step is launch-bound and the wider
+// certificate band (tier 1 for a sixth to a third of the queries) buys nothing.
+bool use_prescan(const rag_index* h, int k) {
+  return h->c8 && RAG_PRESCAN_ROUTES(h->prescan, h->dim, h->storage, k, h->count);
+}
+
+// Query prep and seeds of an int8 prescan pass: qprep's outputs plus the int8 planes
+// (qprep8_kernel), then launch_seed's sample of the shard scored with the prescan's own upper
+// bound u (sample_kernel_i8) and thresh_kernel on it
+template <int D>
+void launch_prep8(rag_index* h, Workspace& w, const float* q, int Bq, const uint32_t* filt,
+                  const uint32_t* tags, hipStream_t st) {
+  using namespace ragmi;
+  qprep8_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(q, Bq, filt, w.qn, w.qfrag, w.filt, w.eps,
+                                                  w.qfrag8, w.qp8, w.eps8);
+  const int nt = (int)((h->count + 15) / 16);
+  if (nt == 0) return;   // the scan visits no tile; seeds are never read
+  const int n_sample = std::min({nt, std::max(256, nt / sample_div()), kMaxSample});
+  with_filter(filt, [&](auto f) {
+    sample_kernel_i8<D, decltype(f)::value><<<dim3((n_sample + 7) / 8), dim3(256), 0, st>>>(
+        h->c8, h->meta8, tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
+        (int)h->count, nt, n_sample, w.smax);
+  });
+  thresh_kernel<kMaxSample><<<dim3(kQ, 1), dim3(256), 0, st>>>(w.smax, n_sample, w.eps8, w.seed);
+}
+
 template <int D>
 int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_t st) {
   using namespace ragmi;
@@ -414,12 +485,17 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   const int Bq = a.Bq;
   // Bq <= 32 * h->groups queries: `groups` query groups of 32 (one for D <= 384)
   const int groups = (Bq + kQ - 1) / kQ;
+  bool i8 = false;
+  if constexpr (D == 384) i8 = use_prescan(h, a.k);
   // fused qprep + sample only in free scan order (small shards, several scans overlapping):
   // there it is +1.1% (1.25M rows, 4 in flight, profiles/r03d_fused_prep_ab.jsonl); with the
   // scans chained (>= 4M rows) its 256-thread workgroups of ~180 registers, which cannot share a
   // CU with scan workgroups, landed between a scan's workgroups and stretched the scan launch
   // (10M rows: scan 0.76 vs 0.83 of the roofline, same qps, profiles/r03i_headline_prep_ab.jsonl)
-  if (D <= 384 && groups == 1 && fused_prep() && h->serial_scans == 0) {
+  if (i8) {
+    // the seed is then a lower bound of the 32nd-best u, which the prescan's thresholds compare
+    if constexpr (D == 384) launch_prep8<D>(h, w, a.q, Bq, filt, a.tags, st);
+  } else if (D <= 384 && groups == 1 && fused_prep() && h->serial_scans == 0) {
     with_filter(filt, [&](auto f) {
       launch_seed<D, decltype(f)::value>(h, w, groups, st, a.q, Bq, filt, a.tags);
     });
@@ -464,7 +540,9 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
     // 222-223K qps vs 205K at 48, 210-218K at 128, and 206-208K for 4 unpartitioned streams at
     // the default grid (scripts/diag/cu_partition.py, profiles/r05c_cu_partition.jsonl; bench lines
     // 222.7-223.3K vs 207.0-207.6K, profiles/r05d_partition_lines.jsonl)
-    const int wg_cap = wg_env ? wg_env : filt ? max_wgs : part ? w.cus : h->scan_wgs;
+    // the int8 prescan holds both query planes in VGPRs (one workgroup per CU at most), so its
+    // filtered passes take the unfiltered grid
+    const int wg_cap = wg_env ? wg_env : (filt && !i8) ? max_wgs : part ? w.cus : h->scan_wgs;
     grid = (int)std::min<int64_t>(std::min(max_wgs, wg_cap),
                                   std::max<int64_t>(1, (n_tiles + 3) / 4));
     grid = std::min(grid, kMaxLists / kWavesPerWG);
@@ -539,8 +617,26 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
         launch(std::false_type{});
     }
   } else {
-    const int rc = with_filter(filt, [&](auto f) {
+    const int rc = with_filter(filt, [&](auto f) -> int {
       constexpr bool F = decltype(f)::value;
+      if constexpr (D == 384) {
+        if (i8) {
+          // timed exactly as the fp16 launch is (its own dispatch packet)
+          const auto go = [&](auto... args) -> int {
+            if (timed)
+              RAG_HIP(launch_fixed_timed<kScanBlock>(scan_kernel_i8<D, F>, dim3(grid), 0, st, pp.a,
+                                                     pp.b, args...));
+            else
+              launch_fixed<kScanBlock>(scan_kernel_i8<D, F>, dim3(grid), 0, st, args...);
+            return RAG_OK;
+          };
+          return go(static_cast<const char*>(h->c8), static_cast<const float*>(h->meta8), a.tags,
+                    static_cast<const uint32_t*>(w.filt),
+                    reinterpret_cast<const intx4*>(w.qfrag8), static_cast<const float*>(w.qp8),
+                    (int)h->count, (int)n_tiles, static_cast<const float*>(w.seed), w.part_s,
+                    w.part_i, w.heads_s, w.heads_i, w.heads_n);
+        }
+      }
       return with_scan_args(
           [&](auto... args) -> int {
             // the timed launch carries its own start / end timestamps (launch_fixed_timed)
@@ -575,8 +671,8 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   with_filter(filt, [&](auto f) {
     select_kernel<D, decltype(f)::value><<<dim3(Bq), dim3(256), 0, st>>>(
         w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, a.tags, w.filt,
-        w.qfrag, (int)h->count, w.qn, a.k, w.eps, w.seed, fb, a.id_offset, a.out_s, a.out_i,
-        a.out_packed, h->rows32);
+        w.qfrag, (int)h->count, w.qn, a.k, i8 ? w.eps8 : w.eps, w.seed, fb, a.id_offset, a.out_s,
+        a.out_i, a.out_packed, h->rows32, i8 ? w.eps : nullptr);
   });
   // tier 2 of the certificate (rescan_kernel): returns at once unless select marked a query
   // of the pass; otherwise its R workgroups stream the shard once per 16 marked queries.
@@ -829,6 +925,8 @@ int import_rows(rag_index* h, int64_t row0, int64_t n, const T* rows, const uint
     });
     if (rc) return rc;
     RAG_HIP(hipGetLastError());
+    rc = requant(h, nullptr, row0, n, nullptr);
+    if (rc) return rc;
     if (tags)
       RAG_HIP(hipMemcpy(h->tags + row0, tags, (size_t)n * 4, hipMemcpyHostToDevice));
     RAG_HIP(hipDeviceSynchronize());
@@ -866,6 +964,7 @@ int upsert_locked(rag_index* h, const float* vecs, const int64_t* rows, const ui
     });
     if (rc) return rc;
     RAG_HIP(hipGetLastError());
+    if (const int rq = requant(h, rows, 0, n, st)) return rq;
   }
   h->count = new_count;
   return RAG_OK;
@@ -987,6 +1086,35 @@ int bench_scan(rag_index* h, const float* q, int B, int variant, int reps, doubl
     rows64_kernel<D><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr>>>(
         h->corpus, h->count, rows64.p);
     qchunk_kernel<D><<<dim3(kQ), dim3(64), 0, nullptr>>>(w.qn, qc.p);
+  }
+#endif
+#ifdef RAGMI_DIAG_BUILD
+  // variants 17 / 18 / 19: the int8 prescan (scan_kernel_i8) at the production grid —
+  // production, MFMA + bound only (no top-k), loads only
+  if (variant >= 17) {
+    if constexpr (D == 384) {
+      if (!h->c8) return ragmi::fail(RAG_EINVAL, "variants 17-19: index keeps no int8 copy");
+      launch_prep8<D>(h, w, q, std::min(B, kQ), nullptr, h->tags, nullptr);
+      const auto go = [&](auto mode) {
+        launch_fixed<kScanBlock>(scan_kernel_i8<D, false, decltype(mode)::value>, dim3(grid), 0,
+                                 nullptr, h->c8, h->meta8, h->tags, w.filt,
+                                 reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, (int)h->count,
+                                 (int)n_tiles, w.seed, w.part_s, w.part_i, w.heads_s, w.heads_i,
+                                 w.heads_n);
+      };
+      float ms8 = 0.f;
+      const int rc8 = time_launches(reps, [&]() {
+        if (variant == 17) go(std::integral_constant<int, 0>{});
+        else if (variant == 18) go(std::integral_constant<int, 1>{});
+        else go(std::integral_constant<int, 2>{});
+      }, &ms8);
+      if (rc8) return rc8;
+      RAG_HIP(hipGetLastError());
+      *avg_ms = ms8 / reps;
+      return RAG_OK;
+    } else {
+      return ragmi::fail(RAG_EINVAL, "variants 17-19: dim 384 only");
+    }
   }
 #endif
   auto one = [&]() {
@@ -1120,6 +1248,8 @@ int copy_rows(rag_index* h, const int64_t* src_rows, const int64_t* dst_rows, in
     });
     if (rc) return rc;
     RAG_HIP(hipGetLastError());
+    if constexpr (MODE != ragmi::kRowsGather)   // move / scatter wrote the rows dst_rows
+      if (const int rq = requant(h, dst_rows, 0, n, st)) return rq;
   }
   if (new_count >= 0) h->count = new_count;
   return RAG_OK;
@@ -1158,6 +1288,17 @@ int rag_index_create_ex(int dim, int64_t capacity_rows, int device, int storage,
   if (rc) {
     delete h;
     return rc;
+  }
+  if (keeps_copy8(h)) {
+    DeviceBuf<char> c8;
+    DeviceBuf<float> m8;
+    rc = alloc_copy8(h, h->cap_rows, c8, m8);
+    if (rc) {
+      rag_index_destroy(h);
+      return rc;
+    }
+    h->c8 = c8.release();
+    h->meta8 = m8.release();
   }
   if (storage == RAG_STORE_FP32) {
     const size_t b32 = (size_t)h->cap_rows * dim * 4;
@@ -1227,6 +1368,8 @@ int rag_index_destroy(rag_index_t* h) {
   if (h->corpus) (void)hipFree(h->corpus);
   if (h->tags) (void)hipFree(h->tags);
   if (h->rows32) (void)hipFree(h->rows32);
+  if (h->c8) (void)hipFree(h->c8);
+  if (h->meta8) (void)hipFree(h->meta8);
   if (h->stage) (void)hipFree(h->stage);
   for (auto& v : h->views)
     if (v.p) (void)hipFree(v.p);
@@ -1254,12 +1397,29 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
     if (n32.alloc(b32) != hipSuccess) return ragmi::fail(RAG_ENOMEM, "hipMalloc(rows32) failed");
     RAG_HIP(hipMemset(n32.p, 0, b32));
   }
+  DeviceBuf<char> n8;
+  DeviceBuf<float> nm8;
+  if (h->c8) {
+    rc = alloc_copy8(h, cap, n8, nm8);
+    if (rc) return rc;
+  }
   RAG_HIP(hipDeviceSynchronize());
   RAG_HIP(hipMemcpy(nc.p, h->corpus, (size_t)h->cap_rows * h->dim * 2, hipMemcpyDeviceToDevice));
   RAG_HIP(hipMemcpy(nt.p, h->tags, (size_t)h->cap_rows * 4, hipMemcpyDeviceToDevice));
   if (n32.p)
     RAG_HIP(hipMemcpy(n32.p, h->rows32, (size_t)h->cap_rows * h->dim * 4,
                       hipMemcpyDeviceToDevice));
+  if (n8.p) {
+    // whole tiles of the old capacity (its spare tile holds no row)
+    RAG_HIP(hipMemcpy(n8.p, h->c8, (size_t)(h->cap_rows / 16) * (h->dim / 64) * 1024,
+                      hipMemcpyDeviceToDevice));
+    RAG_HIP(hipMemcpy(nm8.p, h->meta8, (size_t)(h->cap_rows / 16) * 32 * 4,
+                      hipMemcpyDeviceToDevice));
+    (void)hipFree(h->c8);
+    (void)hipFree(h->meta8);
+    h->c8 = n8.release();
+    h->meta8 = nm8.release();
+  }
   (void)hipFree(h->corpus);
   (void)hipFree(h->tags);
   if (h->rows32) (void)hipFree(h->rows32);
@@ -2074,7 +2234,7 @@ int rag_bench_scan(rag_index_t* h, const float* queries_dev, int B, int variant,
     return ragmi::fail(RAG_EINVAL, "variant: 0 (production) or 7 (dim 384: seeds at +inf); the "
                                    "scan's timing probes are in the diagnostic build only");
 #endif
-  if (!h || !queries_dev || B < 1 || reps < 1 || !avg_ms || variant < 0 || variant > 16)
+  if (!h || !queries_dev || B < 1 || reps < 1 || !avg_ms || variant < 0 || variant > 19)
     return ragmi::fail(RAG_EINVAL, "bad bench args");
   std::lock_guard<std::mutex> lk(h->mu);
   RAG_HIP(hipSetDevice(h->device));
@@ -2144,6 +2304,43 @@ int rag_index_set_scan_order(rag_index_t* h, int serial) {
   h->serial_scans = serial < 0 || serial > 2 ? 1 : serial;
   h->scan_last = nullptr;
   h->scan_any = false;
+  return RAG_OK;
+}
+
+int rag_index_set_prescan(rag_index_t* h, int mode) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
+  if (mode < RAG_PRESCAN_OFF || mode > RAG_PRESCAN_ALWAYS)
+    return ragmi::fail(RAG_EINVAL, "prescan mode must be 0 (off), 1 (auto) or 2 (always)");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->prescan = mode;
+  return RAG_OK;
+}
+
+int rag_index_prescan(const rag_index_t* h) { return h ? h->prescan : -1; }
+
+int rag_index_prescan_bounds(rag_index_t* h, const float* q, int B, const int64_t* rows_dev,
+                             int64_t n, float* out_u) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
+  if (B < 1 || B > ragmi::kQ || !q || n < 0 || (n > 0 && (!rows_dev || !out_u)))
+    return ragmi::fail(RAG_EINVAL, "bad prescan_bounds args (1 <= B <= 32)");
+  if (n > 0x7fffffff) return ragmi::fail(RAG_ERANGE, "n too large for one call");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->c8)
+    return ragmi::fail(RAG_EINVAL, "index keeps no int8 scan copy (dim 384, fp16 storage only)");
+  if (n == 0) return RAG_OK;
+  RAG_HIP(hipSetDevice(h->device));
+  RAG_HIP(hipDeviceSynchronize());   // workspace 0 may belong to a running pass
+  Workspace& w = h->ws[0];
+  using namespace ragmi;
+  qprep8_kernel<384><<<dim3(kQ), dim3(64), 0, nullptr>>>(q, B, nullptr, w.qn, w.qfrag, w.filt,
+                                                         w.eps, w.qfrag8, w.qp8, w.eps8);
+  prescan_bounds_kernel<384><<<dim3((unsigned)n), dim3(64), 0, nullptr>>>(
+      h->c8, h->meta8, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, rows_dev, n, h->count, B,
+      out_u);
+  RAG_HIP(hipGetLastError());
+  RAG_HIP(hipDeviceSynchronize());
   return RAG_OK;
 }
 

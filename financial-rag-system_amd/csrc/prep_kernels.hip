@@ -1,5 +1,7 @@
 // prep_kernels.hip — the storage layout of the in-HBM flat cosine index for gfx950 (MI355X)
-// and the two kernels that write into it: ingest (upsert_kernel) and query prep (qprep_*).
+// and the kernels that write into it: ingest (upsert_kernel) and query prep (qprep_*); then
+// the int8 scan copy of the rows (dim 384, fp16 storage): its layout, the one quantiser
+// (quantise_row / requant_kernel), the upper bound u_bound and the int8 query prep (qprep8_*).
 // First of the device headers index_capi.hip includes; the scan, seed, certify, merge, large-k,
 // re-select and row headers after it all read this layout.
 //
@@ -145,6 +147,199 @@ __device__ __forceinline__ void qprep_slot(const float* __restrict__ q, int B, i
     e = e * (1.0 + 0x1p-10) + 0x1p-22;
     eps[b] = live ? (float)(e * (1.0 + 0x1p-20)) : 0.0f;   // rounded up past fp32's RNE
   }
+}
+
+// ----------------------------------------------------------------------------------------
+// int8 scan copy (D = 384, fp16 storage; DESIGN.md "int8 prescan"). A second image of the
+// corpus for v_mfma_i32_16x16x64_i8, layout "tile16x64":
+//     tile t, k-step s (64 dims), lane l = h*16 + r  ->  16 bytes  row 16t+r, dims 64s+16h..+15
+//     byte offset = ((t*(D/64) + s)*64 + l)*16
+// and per row its scale s_r and its measured error E_r = ||c16 - s_r c8||_2 (rounded up), in
+// `meta` as [tile][32] floats: the tile's 16 scales, then its 16 errors. Both are pure
+// functions of the stored fp16 row (quantise_row), rebuilt by requant_kernel after every write
+// of `corpus`.
+// ----------------------------------------------------------------------------------------
+typedef int intx4 __attribute__((ext_vector_type(4)));
+
+template <int D>
+__host__ __device__ constexpr int steps8() { return D / 64; }
+
+// byte offset of piece c (dims 8c .. 8c+7, 8 bytes) of row `row` in the tile16x64 layout
+template <int D>
+__device__ __forceinline__ int64_t tile8_byte(int64_t row, int c) {
+  return (((row >> 4) * steps8<D>() + (c >> 3)) * 64 + ((c >> 1) & 3) * 16 + (row & 15)) * 16 +
+         (c & 1) * 8;
+}
+
+// first float of row `row`'s scale in meta (its error: + 16)
+__device__ __forceinline__ int64_t meta_slot(int64_t row) { return (row >> 4) * 32 + (row & 15); }
+
+// The one quantiser of a stored row, by one wave: lane c < D/8 passes piece c (x: the fp16
+// values widened, dims 8c .. 8c+7), other lanes zeros. Max-abs scale s = max|x| / 127, bytes
+// rint(x / s) in [-127, 127]; err = ||x - s*bytes||_2 measured in fp64 and rounded up to fp32.
+// The zero row gives scale 0, bytes 0, error 0. Every lane returns the same s and err.
+__device__ __forceinline__ uint2 quantise_row(const float (&x)[8], float& s, float& err) {
+  float m = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[j]));
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+  s = m / 127.0f;
+  uint32_t w[2] = {0u, 0u};
+  double e2 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float v = s > 0.f ? rintf(x[j] / s) : 0.f;
+    v = fminf(fmaxf(v, -127.f), 127.f);
+    const double dd = (double)x[j] - (double)s * (double)v;
+    e2 = fma(dd, dd, e2);
+    w[j >> 2] |= ((uint32_t)(int)v & 0xffu) << (8 * (j & 3));
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) e2 += __shfl_xor(e2, d, 64);
+  // fp64 sum of <= D squares: relative error << 2^-40; 2^-20 covers it and the fp32 RNE
+  err = e2 > 0.0 ? (float)(sqrt(e2) * (1.0 + 0x1p-20)) : 0.f;
+  return uint2{w[0], w[1]};
+}
+
+// rows[i] (rows != nullptr) or row0 + i, i < n: the int8 copy and meta of the stored fp16 row.
+// One wave per row; launched after every kernel that writes `corpus`, on the same stream.
+template <int D>
+__global__ __launch_bounds__(64) void requant_kernel(const half8* __restrict__ corpus,
+                                                     const int64_t* __restrict__ rows,
+                                                     int64_t row0, int64_t n, int64_t cap_rows,
+                                                     char* __restrict__ c8,
+                                                     float* __restrict__ meta) {
+  static_assert(D / 8 <= 64, "one piece per lane");
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  const int lane = threadIdx.x;
+  const int64_t row = rows ? rows[i] : row0 + i;
+  if (row < 0 || row >= cap_rows) return;   // never read or write out of bounds
+  float x[8];
+  const bool has = lane < D / 8;
+  half8 h = {};
+  if (has) h = corpus[tile_slot<D>(row, lane)];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = has ? (float)h[j] : 0.f;
+  float s, err;
+  const uint2 b = quantise_row(x, s, err);
+  if (has) *reinterpret_cast<uint2*>(c8 + tile8_byte<D>(row, lane)) = b;
+  if (lane == 0) {
+    meta[meta_slot(row)] = s;
+    meta[meta_slot(row) + 16] = err;
+  }
+}
+
+// ----------------------------------------------------------------------------------------
+// int8 query prep, one wave per query slot, after qprep_slot: the normalised query y as two
+// int8 planes, y ~ qh = sq * (254 hi + lo) with s1 = max|y| / 127, hi = rint(y / s1),
+// sq = s1 / 254 and lo = rint((y - s1 hi) / sq) (|y - s1 hi| <= s1 / 2, so |lo| <= 127).
+//   qfrag8 [2 query tiles][2 planes: hi, lo][D/64][64] x 16 bytes: B-operand fragments of
+//          v_mfma_i32_16x16x64_i8, lane l -> query 16 qt + (l & 15), dims 64s + 16(l>>4) .. +15
+//          (the corpus copy's k-map; integer accumulation is exact and order-free)
+//   qp8    [32][4] floats: sq, A = ||y|| + F, C = kRowNorm F + slack, 0
+//   eps8   [32] the certificate's eps for a pass that ranks by u (u_bound): u >= e already
+//          holds, so eps only keeps select's fp32 comparisons conservative
+// F = ||y - qh||_2 is measured in fp64 against the fp32 value of sq actually used, so it is
+// the error of the represented query whatever the quantisation's own roundings were.
+//
+// Upper bound. With c the stored fp16 row, c8 / s_r / E_r its int8 copy, I = sum c8 (254 hi +
+// lo) (exact in int32: |I| <= D 127 (254 127 + 127) < 2^31) and e = fp32(sum c y):
+//   sum c y = sum (s_r c8 + (c - s_r c8)) (qh + (y - qh))
+//           = s_r sq I + sum (c - s_r c8) qh + sum c (y - qh)
+//          <= s_r sq I + E_r (||y|| + F) + ||c|| F                 (Cauchy-Schwarz, ||c|| <= kRowNorm)
+// u_bound evaluates the right side in fp32 as fma(If, s_r sq, fma(E_r, A, C)) with If =
+// fma(float(hi dot), 254, float(lo dot)): both dots are < 2^24 in magnitude (D 127^2 =
+// 6.2e6), so their conversions are exact and If, which can exceed 2^24, carries one rounding
+// (2^-24 relative). The product s_r sq and the two fmas add one each; every term is at most
+// (||c|| + E_r)(||y|| + F) < 1.1 in magnitude, so the four roundings stay below 4 * 1.1 * 2^-24
+// < 2^-21.7, and e's own fp32 rounding below 2^-24 * 1.01. The slack 2^-20 in C covers both
+// (A and C themselves are rounded up from fp64).
+// ----------------------------------------------------------------------------------------
+constexpr float kU8Slack = 0x1p-20f;
+
+__device__ __forceinline__ float u_bound(int hi, int lo, float s_r, float e_r, float sq, float A,
+                                         float C) {
+  // fma_scalar: same values as fmaf, never paired into packed fp32 ops beside the MFMAs
+  const float If = fma_scalar((float)hi, 254.0f, (float)lo);
+  return fma_scalar(If, s_r * sq, fma_scalar(e_r, A, C));
+}
+
+template <int D>
+__device__ __forceinline__ void qprep8_slot(const float* __restrict__ q, int B, int b, int lane,
+                                            char* __restrict__ qfrag8, float* __restrict__ qp8,
+                                            float* __restrict__ eps8) {
+  static_assert(D / 8 <= 64, "one piece per lane");
+  const bool live = b < B;
+  double norm = 0.0;
+  if (live) norm = sqrt(canon_sumsq<D>(q + (int64_t)b * D, lane));
+  const bool has = lane < D / 8;
+  float y[8];
+  float m = 0.f;
+  double y2 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    y[j] = (live && has) ? canon_scale(q[(int64_t)b * D + 8 * lane + j], norm) : 0.0f;
+    m = fmaxf(m, fabsf(y[j]));
+    y2 = fma((double)y[j], (double)y[j], y2);
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+  const float s1 = m / 127.0f, sq = s1 / 254.0f;
+  uint32_t wh[2] = {0u, 0u}, wl[2] = {0u, 0u};
+  double f2 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float hi = s1 > 0.f ? rintf(y[j] / s1) : 0.f;
+    hi = fminf(fmaxf(hi, -127.f), 127.f);
+    const double rho = (double)y[j] - (double)s1 * (double)hi;
+    float lo = sq > 0.f ? rintf((float)(rho / (double)sq)) : 0.f;
+    lo = fminf(fmaxf(lo, -127.f), 127.f);
+    const double dd = (double)y[j] - (double)sq * (254.0 * (double)hi + (double)lo);
+    f2 = fma(dd, dd, f2);
+    wh[j >> 2] |= ((uint32_t)(int)hi & 0xffu) << (8 * (j & 3));
+    wl[j >> 2] |= ((uint32_t)(int)lo & 0xffu) << (8 * (j & 3));
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    f2 += __shfl_xor(f2, d, 64);
+    y2 += __shfl_xor(y2, d, 64);
+  }
+  if (has) {
+    const int qt = b >> 4, c16 = b & 15, c = lane;
+    const int lane_l = ((c >> 1) & 3) * 16 + c16;
+    const int64_t o_hi = ((int64_t)((qt * 2 + 0) * steps8<D>() + (c >> 3)) * 64 + lane_l) * 16 +
+                         (c & 1) * 8;
+    const int64_t o_lo = ((int64_t)((qt * 2 + 1) * steps8<D>() + (c >> 3)) * 64 + lane_l) * 16 +
+                         (c & 1) * 8;
+    *reinterpret_cast<uint2*>(qfrag8 + o_hi) = uint2{wh[0], wh[1]};
+    *reinterpret_cast<uint2*>(qfrag8 + o_lo) = uint2{wl[0], wl[1]};
+  }
+  if (lane == 0) {
+    const double F = sqrt(f2) * (1.0 + 0x1p-20), Y = sqrt(y2) * (1.0 + 0x1p-20);
+    qp8[4 * b + 0] = sq;
+    qp8[4 * b + 1] = (float)((Y + F) * (1.0 + 0x1p-20));
+    qp8[4 * b + 2] = (float)((kRowNorm * F + (double)kU8Slack) * (1.0 + 0x1p-20));
+    qp8[4 * b + 3] = 0.f;
+    eps8[b] = live ? kU8Slack : 0.0f;
+  }
+}
+
+// qprep for a pass that scans the int8 copy: everything qprep_kernel writes (select rescoring,
+// the tier-2 rescan and its fp16 bound `eps` read it), then the int8 planes
+template <int D>
+__global__ __launch_bounds__(64) void qprep8_kernel(const float* __restrict__ q, int B,
+                                                    const uint32_t* __restrict__ filt_in,
+                                                    float* __restrict__ qn,
+                                                    half8* __restrict__ qfrag,
+                                                    uint32_t* __restrict__ filt,
+                                                    float* __restrict__ eps,
+                                                    char* __restrict__ qfrag8,
+                                                    float* __restrict__ qp8,
+                                                    float* __restrict__ eps8) {
+  qprep_slot<D>(q, B, blockIdx.x, threadIdx.x, filt_in, qn, qfrag, filt, eps, 0.0, true);
+  qprep8_slot<D>(q, B, blockIdx.x, threadIdx.x, qfrag8, qp8, eps8);
 }
 
 template <int D>

@@ -5,7 +5,8 @@
 // Three top-k structures and the kernel each serves: ScanTopK / scan_kernel (D = 384, query
 // fragments in VGPRs, pending candidates in LDS), RegTopK / scan_lds_kernel (D = 1024, query
 // fragments in LDS, pending in VGPRs), WideTopK / scan_wide_kernel (D = 1024, one query tile
-// per wave), plus the VALU ablation of the scan. The tile helpers the later passes share
+// per wave), plus the int8 prescan on ScanTopK (scan_kernel_i8: D = 384, both int8 query planes
+// in VGPRs, rows ranked by an upper bound of their exact score) and the VALU ablation of the scan. The tile helpers the later passes share
 // (tile_mfma, tile_rsrc, tile_load, tile_sequence) live here, next to their first user.
 namespace ragmi {
 
@@ -536,6 +537,211 @@ __global__ __launch_bounds__(kScanBlock, 2) void scan_kernel(
   }
   topk_finish<MODE == 3 ? 0 : MODE == 4 ? 1 : 2>(st, lane, gw, nw, part_s, part_i, heads_s,
                                                  heads_i, heads_n);
+}
+
+// ----------------------------------------------------------------------------------------
+// int8 prescan (D = 384, fp16 storage): the scan over the int8 copy of the corpus
+// (prep_kernels.hip "int8 scan copy"), half the bytes of the fp16 scan. What enters the top-k
+// is not an approximate score but the upper bound u(r, q) >= e(r, q) of u_bound, so a row
+// outside the lists has e <= u <= the 32nd-best u, and select's certificate keeps its shape
+// with a := u and a tiny eps (certify_kernels.hip). Same ScanTopK / topk_tile_tg / topk_finish
+// and list format as scan_kernel.
+// ----------------------------------------------------------------------------------------
+// Per-lane constants of the int8 query batch: the planes' B-fragments of both query tiles and
+// the u_bound parameters of the lane's two queries (16 qt + (lane & 15)).
+template <int D>
+struct Query8 {
+  intx4 h0[steps8<D>()], l0[steps8<D>()], h1[steps8<D>()], l1[steps8<D>()];
+  float sq0, A0, C0, sq1, A1, C1;
+};
+
+template <int D>
+__device__ __forceinline__ void query8_load(Query8<D>& q, const intx4* __restrict__ qfrag8,
+                                            const float* __restrict__ qp8, int lane) {
+  constexpr int S = steps8<D>();
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    q.h0[s] = qfrag8[(0 * S + s) * 64 + lane];
+    q.l0[s] = qfrag8[(1 * S + s) * 64 + lane];
+    q.h1[s] = qfrag8[(2 * S + s) * 64 + lane];
+    q.l1[s] = qfrag8[(3 * S + s) * 64 + lane];
+  }
+  const float4 p0 = *reinterpret_cast<const float4*>(qp8 + 4 * (lane & 15));
+  const float4 p1 = *reinterpret_cast<const float4*>(qp8 + 4 * (16 + (lane & 15)));
+  q.sq0 = p0.x; q.A0 = p0.y; q.C0 = p0.z;
+  q.sq1 = p1.x; q.A1 = p1.y; q.C1 = p1.z;
+}
+
+// One int8 tile (a: its D/64 A-fragments; sc / er: scales and errors of the lane's four C/D
+// rows 4(lane >> 4) + r) against the 32 queries -> the upper bounds u, in the accumulator
+// layout of tile_mfma (u0: queries 0-15, u1: 16-31). The one place u is evaluated: the scan,
+// the seed sample and rag_index_prescan_bounds all come here.
+template <int D>
+__device__ __forceinline__ void tile_u8(const intx4 (&a)[steps8<D>()], const Query8<D>& q,
+                                        const float4& sc, const float4& er, floatx4& u0,
+                                        floatx4& u1) {
+  intx4 h0 = {0, 0, 0, 0}, l0 = h0, h1 = h0, l1 = h0;
+#pragma unroll
+  for (int s = 0; s < steps8<D>(); ++s) {
+    h0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.h0[s], h0, 0, 0, 0);
+    h1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.h1[s], h1, 0, 0, 0);
+    l0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.l0[s], l0, 0, 0, 0);
+    l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.l1[s], l1, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float s_r = r == 0 ? sc.x : r == 1 ? sc.y : r == 2 ? sc.z : sc.w;
+    const float e_r = r == 0 ? er.x : r == 1 ? er.y : r == 2 ? er.z : er.w;
+    u0[r] = u_bound(h0[r], l0[r], s_r, e_r, q.sq0, q.A0, q.C0);
+    u1[r] = u_bound(h1[r], l1[r], s_r, e_r, q.sq1, q.A1, q.C1);
+  }
+}
+
+// The scan walks PAIRS of tiles (32 rows, 12 KiB + 256 B of meta per load batch, two batches
+// in flight): the same bytes in flight per wave as the fp16 scan's two 12 KiB tiles, which is
+// what keeps HBM busy at one wave per SIMD. c8 / meta hold an even number of tiles (the index
+// allocates one spare); the tag column ends at n_tiles * 16 rows, so the pair's tag
+// descriptor is clipped there (out-of-range buffer loads return 0) and the rows of a spare
+// tile fail topk_tile_tg's bound check.
+// MODE as scan_kernel's: 0 production, 1 MFMA + bound only (no top-k), 2 loads only.
+template <int D, bool FILTER, int MODE = 0>
+__global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i8(
+    const char* __restrict__ c8, const float* __restrict__ meta,
+    const uint32_t* __restrict__ tags, const uint32_t* __restrict__ filt,
+    const intx4* __restrict__ qfrag8, const float* __restrict__ qp8, int n_rows, int n_tiles,
+    const float* __restrict__ seed_thr, float* __restrict__ part_s, int* __restrict__ part_i,
+    float* __restrict__ heads_s, int* __restrict__ heads_i, int* __restrict__ heads_n) {
+  constexpr int S = steps8<D>();
+  __shared__ int lds[kWavesPerWG * kLdsPerWave];
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  ScanTopK st;
+  topk_init<FILTER>(st, lds, wid, lane, seed_thr, filt);
+
+  const int gw = blockIdx.x * kWavesPerWG + __builtin_amdgcn_readfirstlane(wid);
+  const int nw = gridDim.x * kWavesPerWG;
+  const int n_pairs = (n_tiles + 1) / 2;
+  int p_first, p_step, n_mine;
+  tile_sequence<true>(gw, nw, n_pairs, p_first, p_step, n_mine);
+
+  Query8<D> q;
+  query8_load<D>(q, qfrag8, qp8, lane);
+
+  struct Batch {
+    intx4 a[2][S];
+    float4 sc[2], er[2];
+    uint4 tg[2];
+  };
+  const int voff = lane * 16, goff = (lane >> 4) * 16;
+  auto load = [&](Batch& b, int j) __attribute__((always_inline)) {
+    const int p = __builtin_amdgcn_readfirstlane(p_first + j * p_step);
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(c8 + (int64_t)p * (2 * S * 1024), 2 * S * 1024);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int s = 0; s < S; ++s)
+        b.a[u][s] = __builtin_bit_cast(
+            intx4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (u * S + s) * 1024, 2));
+    const __amdgpu_buffer_rsrc_t rm = tile_rsrc(meta + (int64_t)p * 64, 256);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      b.sc[u] = __builtin_bit_cast(float4,
+                                   __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128, 0));
+      b.er[u] = __builtin_bit_cast(
+          float4, __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128 + 64, 0));
+    }
+    if constexpr (FILTER) {
+      const int left = min(2, n_tiles - 2 * p);   // tiles of this pair the tag column holds
+      const __amdgpu_buffer_rsrc_t rt =
+          tile_rsrc(tags + (int64_t)p * (2 * kTileRows), left * kTileRows * 4);
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        b.tg[u] = __builtin_bit_cast(
+            uint4, __builtin_amdgcn_raw_buffer_load_b128(rt, goff, u * (kTileRows * 4), 0));
+    } else {
+      b.tg[0] = b.tg[1] = uint4{0u, 0u, 0u, 0u};
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  float vmax = kNegInf;   // MODE 1/2: keeps the work alive
+  auto process = [&](const Batch& b, int j) __attribute__((always_inline)) {
+    const int p = p_first + j * p_step;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if constexpr (MODE == 2) {
+        intx4 x = b.a[u][0];
+#pragma unroll
+        for (int s = 1; s < S; ++s) x += b.a[u][s];
+        vmax = fmaxf(vmax, (float)(x[0] + x[1] + x[2] + x[3]) + b.sc[u].x + b.er[u].x);
+      } else {
+        floatx4 u0, u1;
+        tile_u8<D>(b.a[u], q, b.sc[u], b.er[u], u0, u1);
+        if constexpr (MODE == 0)
+          topk_tile_tg<FILTER>(st, u0, u1, 2 * p + u, n_rows, b.tg[u], lane);
+        else
+          vmax = fmaxf(vmax, fmaxf(fmaxf(fmaxf(u0[0], u0[1]), fmaxf(u0[2], u0[3])),
+                                   fmaxf(fmaxf(u1[0], u1[1]), fmaxf(u1[2], u1[3]))));
+      }
+    }
+  };
+  if (n_mine > 0) {
+    Batch b0, b1;
+    load(b0, 0);
+    int j = 0;
+    while (true) {
+      load(b1, min(j + 1, n_mine - 1));
+      process(b0, j);
+      if (++j >= n_mine) break;
+      load(b0, min(j + 1, n_mine - 1));
+      process(b1, j);
+      if (++j >= n_mine) break;
+    }
+  }
+  if constexpr (MODE != 0) {
+    if (vmax == 12345.0f) part_s[gw] = vmax;   // never true in practice; defeats DCE
+    return;
+  }
+  topk_finish<2>(st, lane, gw, nw, part_s, part_i, heads_s, heads_i, heads_n);
+}
+
+// u of the 16 rows of tile t against the pass's 32 queries, by one wave, through tile_u8:
+// out[q * n + i] for the requested row i = 16 t + (its position in the tile). One wave per
+// requested row (rag_index_prescan_bounds; a test's direct view of the certificate's premise).
+template <int D>
+__global__ __launch_bounds__(64) void prescan_bounds_kernel(
+    const char* __restrict__ c8, const float* __restrict__ meta,
+    const intx4* __restrict__ qfrag8, const float* __restrict__ qp8,
+    const int64_t* __restrict__ rows, int64_t n, int64_t n_rows, int B,
+    float* __restrict__ out) {
+  constexpr int S = steps8<D>();
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  const int lane = threadIdx.x;
+  const int64_t row = rows[i];
+  if (row < 0 || row >= n_rows) {   // not a stored row: never dereferenced
+    if (lane < B) out[(int64_t)lane * n + i] = kNegInf;
+    return;
+  }
+  Query8<D> q;
+  query8_load<D>(q, qfrag8, qp8, lane);
+  const int64_t t = row >> 4;
+  intx4 a[S];
+  const intx4* tp = reinterpret_cast<const intx4*>(c8) + t * (S * 64) + lane;
+#pragma unroll
+  for (int s = 0; s < S; ++s) a[s] = tp[s * 64];
+  const float4 sc = *reinterpret_cast<const float4*>(meta + t * 32 + 4 * (lane >> 4));
+  const float4 er = *reinterpret_cast<const float4*>(meta + t * 32 + 16 + 4 * (lane >> 4));
+  floatx4 u0, u1;
+  tile_u8<D>(a, q, sc, er, u0, u1);
+  // lane holds rows 4(lane >> 4) + r of queries (lane & 15), 16 + (lane & 15)
+  const int r = (int)(row & 15) - 4 * (lane >> 4);
+  if (r >= 0 && r < 4) {
+    const int qa = lane & 15, qb = 16 + (lane & 15);
+    const float va = r == 0 ? u0[0] : r == 1 ? u0[1] : r == 2 ? u0[2] : u0[3];
+    const float vb = r == 0 ? u1[0] : r == 1 ? u1[1] : r == 2 ? u1[2] : u1[3];
+    if (qa < B) out[(int64_t)qa * n + i] = va;
+    if (qb < B) out[(int64_t)qb * n + i] = vb;
+  }
 }
 
 // ---- register-pending top-k (LDS-query scan): the pending candidates of a lane live in

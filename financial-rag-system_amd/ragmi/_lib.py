@@ -152,6 +152,10 @@ INDEX_API = {
     "rag_bench_scan": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(ctypes.c_double)]),
     "rag_index_set_scan_order": (ctypes.c_int, [c_vp, ctypes.c_int]),
+    "rag_index_set_prescan": (ctypes.c_int, [c_vp, ctypes.c_int]),
+    "rag_index_prescan": (ctypes.c_int, [c_vp]),
+    "rag_index_prescan_bounds": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int64,
+                                                c_vp]),
     "rag_stream_create_cu_partition": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                       ctypes.POINTER(c_vp)]),
     "rag_stream_create_cu_mask": (ctypes.c_int, [ctypes.c_int, c_u32p, ctypes.c_int,

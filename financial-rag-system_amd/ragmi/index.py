@@ -31,6 +31,8 @@ FUSION_MAX_LISTS = 16          # RAG_FUSION_MAX_LISTS: lists per request rag_fus
 FUSION_MAX_ENTRIES = 4096      # RAG_FUSION_MAX_ENTRIES: lists x entries per list
 SEARCH_FULL = 1     # RAG_SEARCH_FULL (rag_index_search_view)
 STORAGE = {"fp16": 0, "fp32": 1}   # RAG_STORE_FP16 / RAG_STORE_FP32
+PRESCAN_OFF, PRESCAN_AUTO, PRESCAN_ALWAYS = 0, 1, 2   # RAG_PRESCAN_*: FlatIndex.set_prescan
+PRESCAN_MIN_ROWS = 500000      # RAG_PRESCAN_MIN_ROWS: auto mode's smallest shard
 CREATE_DIAGNOSTIC = 0x100          # RAG_CREATE_DIAGNOSTIC: honour the RAGMI_* A/B knobs
 
 
@@ -544,6 +546,27 @@ class FlatIndex(ListOps):
         (rag_index_set_scan_order); prep / seeding / select still overlap across streams."""
         mode = serial if isinstance(serial, int) and not isinstance(serial, bool) else int(bool(serial))
         check(self._L.rag_index_set_scan_order(self._h, mode))
+
+    def set_prescan(self, mode: int) -> None:
+        """0 off / 1 auto (default) / 2 always: whether k <= 32 passes stream the int8 copy of
+        the rows (dim 384, fp16 storage) and certify the exact top-k from the fp16 rows;
+        results are the same in every mode (rag_index_set_prescan)."""
+        check(self._L.rag_index_set_prescan(self._h, int(mode)))
+
+    def prescan(self) -> int:
+        """The prescan mode set (rag_index_prescan)."""
+        return int(self._L.rag_index_prescan(self._h))
+
+    def prescan_bounds(self, queries, rows) -> torch.Tensor:
+        """[B, n] upper bounds u of the prescan for stored rows `rows` against `queries`
+        (B <= 32), from the stored int8 copy (rag_index_prescan_bounds; diagnostic)."""
+        q = _as_dev(queries, torch.float32, self.device)
+        r = _as_dev(rows, torch.int64, self.device)
+        out = torch.empty((q.shape[0], r.shape[0]), dtype=torch.float32, device=self.device)
+        torch.cuda.synchronize(self.device)
+        check(self._L.rag_index_prescan_bounds(self._h, q.data_ptr(), int(q.shape[0]),
+                                               r.data_ptr(), int(r.shape[0]), out.data_ptr()))
+        return out
 
     def exactness_stats(self, n_last: int = 0):
         """(tier1 total, tier2 total, tiers of the last pass's first n_last queries): which

@@ -472,6 +472,41 @@ int rag_index_unanswered(rag_index_t* index, int64_t* n);
  * (main.py:232-237); this is serving-loop plumbing for main2.py:281-295's batch processor
  * with several batches in flight. */
 int rag_index_set_scan_order(rag_index_t* index, int serial);
+
+/* int8 prescan (dim 384, RAG_STORE_FP16 only). Such an index keeps, beside its fp16 rows, an
+ * int8 copy of them with a scale and a measured quantisation error per row: memory is
+ * 3 B + 8 B / dim per element instead of 2 B (+50 %: 3.9 GB more at 10M x 384), rebuilt on the
+ * device by every call that writes rows (upsert, import, move, scatter, reserve). A pass with
+ * k <= RAG_MAX_K may stream that copy (half the bytes) ranking rows by an UPPER BOUND of their
+ * exact score; select then rescores the listed rows on the fp16 rows and certifies the exact
+ * top-k as it does after the fp16 scan: returned ids and scores are the same in every mode,
+ * bit for bit. The wider error band makes the list re-scoring fallback (tier 1 of
+ * rag_index_exactness_stats) common, which is why the default is by size:
+ *   RAG_PRESCAN_OFF     always the fp16 scan
+ *   RAG_PRESCAN_AUTO    (default) the int8 prescan for passes (filtered ones included) over
+ *                       at least RAG_PRESCAN_MIN_ROWS rows, else the fp16 scan
+ *   RAG_PRESCAN_ALWAYS  the int8 prescan for every k <= RAG_MAX_K pass
+ * Indexes without the copy (dim 1024, fp32 storage) accept any mode and stay on the fp16 scan.
+ * No reference counterpart (Qdrant's scalar quantisation with rescoring is approximate; this
+ * one is certified exact). */
+enum { RAG_PRESCAN_OFF = 0, RAG_PRESCAN_AUTO = 1, RAG_PRESCAN_ALWAYS = 2 };
+#define RAG_PRESCAN_MIN_ROWS 500000
+/* The routing rule itself (the library calls this; no device involved): 1 when a pass of `k`
+ * over `count` rows of a (dim, storage) index in `mode` streams the int8 copy. */
+#define RAG_PRESCAN_ROUTES(mode, dim, storage, k, count)                                   \
+  ((dim) == 384 && (storage) == RAG_STORE_FP16 && (k) >= 1 && (k) <= RAG_MAX_K &&          \
+   ((mode) == RAG_PRESCAN_ALWAYS ||                                                        \
+    ((mode) == RAG_PRESCAN_AUTO && (count) >= RAG_PRESCAN_MIN_ROWS)))
+int rag_index_set_prescan(rag_index_t* index, int mode);
+/* The mode set (-1 for NULL). */
+int rag_index_prescan(const rag_index_t* index);
+/* Diagnostic view of the certificate's premise: out_u_dev[b * n + i] = the prescan's upper
+ * bound u of stored row rows_dev[i] against query b (q_dev: B <= 32 queries, as for a search),
+ * computed from the stored copy by the device function the prescan itself uses; -inf for a
+ * row outside [0, count). u >= the exact score of every pair is what the certificate rests
+ * on. RAG_EINVAL for an index without the copy. Synchronous. */
+int rag_index_prescan_bounds(rag_index_t* index, const float* q_dev, int B,
+                             const int64_t* rows_dev, int64_t n, float* out_u_dev);
 /* Spatial partition of the batches in flight (serving option): a HIP stream restricted to CU
  * share `part` of `parts` (contiguous CU ids, hipExtStreamCreateWithCUMask). Searches issued
  * on such a stream size their scan grids to the stream's CUs (one scan workgroup per CU), so

@@ -22,7 +22,14 @@ def main():
     os.makedirs(out, exist_ok=True)
     f = glob.glob(os.path.join(pmc_dir, "**", "*counter_collection.csv"), recursive=True)[0]
     kb = [float(r["Counter_Value"]) for r in csv.DictReader(open(f))
-          if "scan_kernel" in r.get("Kernel_Name", "") and r.get("Counter_Name") == "FETCH_SIZE"]
+          if "scan_kernel" in r.get("Kernel_Name", "") and "rescan" not in r.get("Kernel_Name", "")
+          and r.get("Counter_Name") == "FETCH_SIZE"]
+    # which scan ran: scan_kernel_i8 (the int8 prescan, about half the fp16 rows' bytes plus
+    # 8 B of meta per row) or scan_kernel; algorithmic_bytes stays the fp16 rows' rows * D * 2
+    names = {r["Kernel_Name"].split("(")[0].split("<")[0].split("::")[-1]
+             for r in csv.DictReader(open(f))
+             if "scan_kernel" in r.get("Kernel_Name", "") and "rescan" not in r["Kernel_Name"]}
+    kname = "+".join(sorted(names))
     shutil.copy(f, os.path.join(out, f"{tag}_pmc_fetch_size.csv"))
     cur = os.path.join(out, "scan_pmc.json")
     src = cur if os.path.exists(cur) else os.path.join(ROOT, "profiles", "scan_pmc.json")
@@ -30,7 +37,8 @@ def main():
     avg = sum(kb) / len(kb)
     p.setdefault("by_rows_per_gpu", {})[str(rows)] = {
         "hbm_bytes_per_launch": avg * 1024 * 2, "fetch_size_kB_raw": avg, "launches": len(kb),
-        "algorithmic_bytes": rows * 768, "source": f"profiles/{tag}_pmc_fetch_size.csv",
+        "algorithmic_bytes": rows * 768, "kernel": kname,
+        "source": f"profiles/{tag}_pmc_fetch_size.csv",
         "commit": os.environ.get("COMMIT", "")}
     json.dump(p, open(cur, "w"), indent=1)
     print(rows, "rows:", len(kb), "launches,", round(avg * 2048 / (rows * 768), 4), "x algorithmic")
