@@ -6,6 +6,7 @@
 namespace ragmi {
 
 constexpr int kCandCap = 256;   // select: compacted heads at/above the lane-max threshold
+constexpr int kBandLists = 32;  // select tier 1: lists gathered per chunk (8 per wave)
 
 // Wave 0 merges the four waves' top-32 lists (best first, one row of ws / wi per wave) out of
 // LDS: lanes 0..31 end with the best 32 of the 128 entries, best first. `none` pads list 0 in
@@ -132,7 +133,14 @@ struct ExactStats {
 //     a >= L = e_k - eps_q, and:
 //     tier 1 (here): if L >= the scan's seed (no such row was pruned) and no per-wave list
 //       whose tail is >= L is full (none dropped one), every row with a >= L sits in some
-//       list: rescore all of them exactly and emit their top-k.
+//       list. The lists whose head is >= L come from the head scores step 1 still holds in
+//       registers; their entries are gathered a half-wave per list, every load of a chunk of
+//       kBandLists lists issued before the first use (the list's tail rides on lane 31 of the
+//       same load: the fullness check). Entries >= L that are not in A go to an LDS band
+//       buffer and are rescored 32 per round (8 per wave); the result is the top-k of A's 32
+//       exact scores and theirs. One gather round trip, one rescoring round trip per 32 new
+//       rows and one merge per round, whatever the number of lists below kBandLists; more
+//       lists cost a chunk each, with a running top-32 across chunks.
 //     tier 2 (rescan_kernel): otherwise the shard is streamed once more for this query by
 //       the rescan kernel launched after every select (its workgroups split the shard); here
 //       select only records L and e_k. Only inputs with more than 32 in-band rows inside one
@@ -178,11 +186,17 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
   __shared__ int e_i[32];
   __shared__ int qlist[kMaxLists];   // tier 1: lists whose head is >= L
   __shared__ int n_q;
+  __shared__ int band[kBandLists * kKS];   // tier 1: a chunk's rows with a >= L outside A
+  __shared__ int n_band;
+  __shared__ float n_s[2][32];       // tier 1: a round's exact scores / rows (two rounds in
+  __shared__ int n_i[2][32];         // flight: one barrier per round)
   __shared__ int verdict;            // 0 exact, 1 tier 1, 2 tier 2
   __shared__ float floor_L, floor_E;
   // query bq of the batch = slot b of query group grp (the scan's per-group lists)
   const int bq = blockIdx.x, grp = bq / kQ, b = bq % kQ;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  // the check's two constants, read here: their round trip is over long before step 5
+  const float eps_q = eps[bq], seed_q = seed_thr[bq];
   part_s += (int64_t)grp * n_lists * (kQ * kKS);
   part_i += (int64_t)grp * n_lists * (kQ * kKS);
   heads_s += (int64_t)grp * kQ * n_lists;
@@ -228,6 +242,7 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
   if (tid == 0) {
     n_cand = 0;
     n_q = 0;
+    n_band = 0;
     verdict = 0;
   }
   __syncthreads();
@@ -399,21 +414,24 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
   };
 
   // ---- 4. order by exact score; 5. exactness check
+  float rs = kNegInf;   // wave 0, lanes 0..31: A by exact score, best first; under tier 1 the
+  int ri = kIdNone32;   // running exact top-32
   if (wid == 0) {
-    float s = lane < 32 ? e_s[lane] : kNegInf;
-    int id = lane < 32 ? e_i[lane] : kIdNone32;
-    bitonic_sort64(s, id, lane);
+    if (lane < 32) {
+      rs = e_s[lane];
+      ri = e_i[lane];
+    }
+    bitonic_sort64(rs, ri, lane);
     int v = 0;
     {
-      const float ek = __shfl(s, k - 1, 64);
+      const float ek = __shfl(rs, k - 1, 64);
       const float a32 = c_s[0][kKS - 1];
-      const float e = eps[bq];
       float L = 0.0f;
       // a32 == -inf: fewer than 32 finite candidates, i.e. A holds every matching row (a
       // finite seed implies >= 32 rows above it)
-      if (!(a32 == kNegInf || ek > a32 + e)) {
-        L = ek - e;
-        v = (L >= seed_thr[bq]) ? 1 : 2;
+      if (!(a32 == kNegInf || ek > a32 + eps_q)) {
+        L = ek - eps_q;
+        v = (L >= seed_q) ? 1 : 2;
       }
       if (lane == 0) {
         verdict = v;
@@ -422,28 +440,90 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
       }
     }
     if (v == 0) {
-      emit(s, id);
+      emit(rs, ri);
       if (lane == 0) fb.tier[bq] = 0;
     }
   }
   __syncthreads();
   if (verdict == 0) return;
 
-  // ---- tier 1: every row with approximate score >= L is in a list (checked below)
+  // ---- tier 1: every row with approximate score >= L is in a list (checked by the gather).
+  //      The qualifying lists, from step 1's head scores (list of hs[j] = (4j + wid) 64 + lane)
   const float L = floor_L;
-  if (verdict == 1)
-  for (int l = tid; l < n_lists; l += 256) {
-    const float h = heads_s[(int64_t)b * n_lists + l];
-    if (h != kNegInf && h >= L) {
-      const int n = heads_n[(int64_t)b * n_lists + l];
-      if (n >= kKS && part_s[at(l, kKS - 1)] >= L) verdict = 2;   // full list: may have dropped one
-      const int p = atomicAdd(&n_q, 1);
-      qlist[p] = l;
-    }
+  const bool seeded = verdict == 1;   // read before the gather may write it
+  if (seeded) {
+#pragma unroll
+    for (int j = 0; j < kCols; ++j)
+      if (hs[j] != kNegInf && hs[j] >= L) qlist[atomicAdd(&n_q, 1)] = (j * 4 + wid) * 64 + lane;
   }
   __syncthreads();
-  float rs = kNegInf;   // each wave's running exact top-32 (lanes 0..31, best first)
-  int ri = kIdNone32;
+  const int nql = seeded ? n_q : 0;
+  const int a_row = e_i[lane & 31];   // A's rows, one per lane: their exact scores are known
+  int rnd = 0;
+  for (int c0 = 0; c0 < nql; c0 += kBandLists) {
+    // gather: a half-wave per list, a lane per entry; wave w takes the chunk's lists w, w + 4,
+    // ... Every load is issued before the first use (clamped, selects afterwards: step 1).
+    constexpr int kG = kBandLists / 8;
+    const int pos = lane & (kKS - 1);
+    float gs[kG];
+    int gi[kG], gn[kG];
+#pragma unroll
+    for (int j = 0; j < kG; ++j) {
+      const int l = qlist[min(c0 + (2 * j + (lane >> 5)) * 4 + wid, nql - 1)];
+      gs[j] = part_s[at(l, pos)];
+      gi[j] = part_i[at(l, pos)];
+      gn[j] = heads_n[(int64_t)b * n_lists + l];
+    }
+#pragma unroll
+    for (int j = 0; j < kG; ++j) {
+      // entries past a list's length are stale memory
+      const bool in = c0 + (2 * j + (lane >> 5)) * 4 + wid < nql && pos < gn[j] && gs[j] >= L;
+      // lane 31 of the half-wave holds the tail: a full list may have dropped a row >= L
+      if (in && gn[j] >= kKS && pos == kKS - 1) verdict = 2;
+      bool in_a = false;
+#pragma unroll
+      for (int t = 0; t < 32; ++t) in_a |= gi[j] == __builtin_amdgcn_readlane(a_row, t);
+      if (in && !in_a) band[atomicAdd(&n_band, 1)] = gi[j];
+    }
+    __syncthreads();
+    if (verdict == 2) break;
+    // rescoring: the band rows 32 per round, 8 per wave; wave 0 folds each round into the
+    // running exact top-32 (which starts as A)
+    const int nb = n_band;
+    for (int r0 = 0; r0 < nb; r0 += 32, ++rnd) {
+      int rows[8];
+      float es[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = r0 + wid * 8 + j;
+        const int r = band[min(c, nb - 1)];
+        rows[j] = c < nb ? r : -1;
+      }
+      exact_scores_wave<D, 8>(corpus, rows, qq, lane, es, rows32);
+      if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          n_s[rnd & 1][wid * 8 + j] = es[j];
+          n_i[rnd & 1][wid * 8 + j] = rows[j] >= 0 ? rows[j] : kIdNone32;
+        }
+      }
+      // one barrier per round: round r + 2 overwrites this slot only after round r + 1's
+      // barrier, which wave 0 reaches after the read below
+      __syncthreads();
+      if (wid == 0) {
+        if (lane >= 32) {
+          rs = n_s[rnd & 1][lane - 32];
+          ri = n_i[rnd & 1][lane - 32];
+        }
+        bitonic_sort64(rs, ri, lane);
+      }
+    }
+    if (c0 + kBandLists < nql) {   // the band buffer is reused by the next chunk
+      __syncthreads();
+      if (tid == 0) n_band = 0;
+      __syncthreads();
+    }
+  }
   if (verdict == 2) {
     // ---- tier 2: handed to rescan_kernel (launched after every select, many workgroups):
     // its floor L and the k-th exact score of A go to the hand-off record; nothing is emitted
@@ -457,61 +537,13 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
       atomicAdd(&fb.cnt[1], 1ull);
     }
     return;
-  } else {   // tier 1
+  }
+  // tier 1 certified: the top-k of A and the band rows, by (exact score desc, row asc)
   if (tid == 0) {
     fb.tier[bq] = 1;
     atomicAdd(&fb.cnt[0], 1ull);
   }
-  // each wave: its share of the qualifying lists, entries >= L (a prefix of each sorted
-  // list) rescored 8 at a time into the running exact top-32
-  const int nql = n_q;
-  for (int i = wid; i < nql; i += 4) {
-    const int l = qlist[i];
-    const int n = heads_n[(int64_t)b * n_lists + l];
-    float s = kNegInf;
-    int id = kIdNone32;
-    if (lane < kKS && lane < n) {
-      s = part_s[at(l, lane)];
-      id = part_i[at(l, lane)];
-    }
-    const int m = __popcll(__ballot(lane < kKS && lane < n && s >= L));
-    for (int c0 = 0; c0 < m; c0 += 8) {
-      int rows[8];
-      float es[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int r = __shfl(id, min(c0 + j, 63), 64);
-        rows[j] = c0 + j < m ? r : -1;
-      }
-      exact_scores_wave<D, 8>(corpus, rows, qq, lane, es, rows32);
-      float ns = kNegInf;
-      int ni = kIdNone32;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (lane == 32 + j && rows[j] >= 0) {
-          ns = es[j];
-          ni = rows[j];
-        }
-      }
-      if (lane >= 32) {
-        rs = ns;
-        ri = ni;
-      }
-      bitonic_sort64(rs, ri, lane);
-    }
-  }
-  }   // tier 1
-  if (lane < 32) {
-    c_s[wid][lane] = rs;
-    c_i[wid][lane] = ri;
-  }
-  __syncthreads();
-  if (wid == 0) {
-    float s;
-    int id;
-    merge4_top32(c_s, c_i, lane, kIdNone32, s, id);
-    emit(s, id);
-  }
+  if (wid == 0) emit(rs, ri);
 }
 
 // ----------------------------------------------------------------------------------------
