@@ -219,6 +219,10 @@ struct rag_index {
   int64_t count = 0;
   half8* corpus = nullptr;
   uint32_t* tags = nullptr;
+  // key columns (rag_index_keys_create; rows_kernels.hip): n_keys int64 columns of cap_rows
+  // keys, the tag array's extent; entries at or past n_keys are nullptr
+  int64_t* keys[RAG_KEYS_MAX_COLS] = {};
+  int n_keys = 0;
   // storage (rag_index_create_ex): RAG_STORE_FP16 keeps only the scan's fp16 tile16 rows;
   // RAG_STORE_FP32 also the normalised fp32 rows (row-major [cap][dim]), which the exact
   // rescoring reads — Qdrant's default Float32 datatype
@@ -1217,6 +1221,28 @@ int bench_wide(rag_index* h, const float* q, int B, int mode, int reps, double* 
   return RAG_OK;
 }
 
+// the handle's key columns as the kernels take them
+ragmi::KeyCols key_cols(const rag_index* h) {
+  ragmi::KeyCols kc;
+  for (int c = 0; c < RAG_KEYS_MAX_COLS; ++c) kc.col[c] = h->keys[c];
+  return kc;
+}
+
+// A new key column of `cap` rows: rows [0, keep) copied from `old` (may be NULL with keep = 0),
+// rows [keep, cap) RAG_KEY_ABSENT. On the null stream; the caller synchronises the device
+// before and after.
+int alloc_keys(int64_t cap, const int64_t* old, int64_t keep, DeviceBuf<int64_t>& out) {
+  if (out.alloc((size_t)cap * 8) != hipSuccess)
+    return ragmi::fail(RAG_ENOMEM, "hipMalloc(key column) failed");
+  if (keep > 0) RAG_HIP(hipMemcpy(out.p, old, (size_t)keep * 8, hipMemcpyDeviceToDevice));
+  if (cap > keep) {
+    const dim3 grid((unsigned)((cap - keep + ragmi::kKeyBlock - 1) / ragmi::kKeyBlock));
+    ragmi::fill_keys_kernel<<<grid, dim3(ragmi::kKeyBlock), 0, nullptr>>>(out.p, keep, cap);
+    RAG_HIP(hipGetLastError());
+  }
+  return RAG_OK;
+}
+
 // The three indexed row copies behind move / gather / scatter: the shared argument checks,
 // then one copy_rows_kernel launch on `st` under the handle's lock. pk32 goes with fp32
 // storage exactly; new_count < 0 leaves the count alone (gather).
@@ -1248,6 +1274,13 @@ int copy_rows(rag_index* h, const int64_t* src_rows, const int64_t* dst_rows, in
     });
     if (rc) return rc;
     RAG_HIP(hipGetLastError());
+    if constexpr (MODE == ragmi::kRowsMove)
+      if (h->n_keys > 0) {   // the keys are a stored form of the row: they move with it
+        const dim3 kgrid((unsigned)((n + ragmi::kKeyBlock - 1) / ragmi::kKeyBlock));
+        ragmi::move_keys_kernel<<<kgrid, dim3(ragmi::kKeyBlock), 0, st>>>(
+            key_cols(h), h->n_keys, src_rows, dst_rows, n, h->cap_rows);
+        RAG_HIP(hipGetLastError());
+      }
     if constexpr (MODE != ragmi::kRowsGather)   // move / scatter wrote the rows dst_rows
       if (const int rq = requant(h, dst_rows, 0, n, st)) return rq;
   }
@@ -1367,6 +1400,8 @@ int rag_index_destroy(rag_index_t* h) {
   if (h->scan_stream) (void)hipStreamDestroy(h->scan_stream);
   if (h->corpus) (void)hipFree(h->corpus);
   if (h->tags) (void)hipFree(h->tags);
+  for (auto* k : h->keys)
+    if (k) (void)hipFree(k);
   if (h->rows32) (void)hipFree(h->rows32);
   if (h->c8) (void)hipFree(h->c8);
   if (h->meta8) (void)hipFree(h->meta8);
@@ -1404,6 +1439,11 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
     if (rc) return rc;
   }
   RAG_HIP(hipDeviceSynchronize());
+  // the key columns regrow with the tags: old rows keep their keys, new rows hold ABSENT
+  DeviceBuf<int64_t> nk[RAG_KEYS_MAX_COLS];
+  for (int c = 0; c < h->n_keys; ++c)
+    if ((rc = alloc_keys(cap, h->keys[c], h->cap_rows, nk[c]))) return rc;
+  if (h->n_keys > 0) RAG_HIP(hipDeviceSynchronize());
   RAG_HIP(hipMemcpy(nc.p, h->corpus, (size_t)h->cap_rows * h->dim * 2, hipMemcpyDeviceToDevice));
   RAG_HIP(hipMemcpy(nt.p, h->tags, (size_t)h->cap_rows * 4, hipMemcpyDeviceToDevice));
   if (n32.p)
@@ -1426,6 +1466,10 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
   h->corpus = nc.release();
   h->tags = nt.release();
   h->rows32 = n32.release();
+  for (int c = 0; c < h->n_keys; ++c) {
+    (void)hipFree(h->keys[c]);
+    h->keys[c] = nk[c].release();
+  }
   h->cap_rows = cap;
   return RAG_OK;
 }
@@ -1627,13 +1671,23 @@ int launch_filter_view(rag_index* h, const uint32_t* progs, int64_t words, int n
   if (h->cap_rows == 0) return RAG_OK;
   const int64_t chunks = (h->cap_rows + kFvBlock * 4 - 1) / (kFvBlock * 4);
   const dim3 grid((unsigned)std::min<int64_t>(chunks, (int64_t)kFvWgPerCu * h->n_cu));
-  if (words <= kFvLdsWords)
-    filter_view_kernel<true><<<grid, dim3(kFvBlock), (size_t)words * 4, st>>>(
-        h->tags, h->count, h->cap_rows, progs, (uint32_t)words, n_programs, view);
-  else
-    filter_view_kernel<false><<<grid, dim3(kFvBlock),
-                                (size_t)n_programs * RAG_FILTER_REC_WORDS * 4, st>>>(
-        h->tags, h->count, h->cap_rows, progs, (uint32_t)words, n_programs, view);
+  // an index with key columns: the instantiations that know the RANGE atom (one more word of
+  // LDS, the mask of the columns the blob names); without columns, the kernel as it always was
+  const bool pool = words <= kFvLdsWords;
+  const size_t lds = (pool ? (size_t)words : (size_t)n_programs * RAG_FILTER_REC_WORDS) * 4;
+  const KeyCols kc = key_cols(h);
+  const auto launch = [&](auto pool_lds, auto with_keys) {
+    constexpr bool P = decltype(pool_lds)::value, K = decltype(with_keys)::value;
+    filter_view_kernel<P, K><<<grid, dim3(kFvBlock), lds + (K ? 4 : 0), st>>>(
+        h->tags, h->count, h->cap_rows, progs, (uint32_t)words, n_programs, view, kc, h->n_keys);
+  };
+  if (h->n_keys > 0) {
+    if (pool) launch(std::true_type{}, std::true_type{});
+    else launch(std::false_type{}, std::true_type{});
+  } else {
+    if (pool) launch(std::true_type{}, std::false_type{});
+    else launch(std::false_type{}, std::false_type{});
+  }
   RAG_HIP(hipGetLastError());
   return RAG_OK;
 }
@@ -1816,6 +1870,78 @@ int rag_index_gather_tags(rag_index_t* h, const int64_t* rows, int64_t n, uint32
   const dim3 grid((unsigned)((n + ragmi::kTagBlock - 1) / ragmi::kTagBlock));
   ragmi::gather_tags_kernel<<<grid, dim3(ragmi::kTagBlock), 0, st>>>(h->tags, rows, n, h->cap_rows,
                                                                      out_tags);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// ---- key columns (rows_kernels.hip; the RANGE atom of filter_kernels.hip reads them) ----
+
+int rag_index_keys_create(rag_index_t* h, int n_cols) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "keys_create: index is NULL");
+  if (n_cols < 1 || n_cols > RAG_KEYS_MAX_COLS)
+    return ragmi::fail(RAG_ERANGE, "keys_create: n_cols must be in [1, RAG_KEYS_MAX_COLS=4]");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (n_cols <= h->n_keys) return RAG_OK;
+  RAG_HIP(hipSetDevice(h->device));
+  DeviceBuf<int64_t> nk[RAG_KEYS_MAX_COLS];
+  for (int c = h->n_keys; c < n_cols; ++c)
+    if (const int rc = alloc_keys(h->cap_rows, nullptr, 0, nk[c])) return rc;
+  // searches in flight read the handle's columns by value: drain them before the count changes
+  RAG_HIP(hipDeviceSynchronize());
+  for (int c = h->n_keys; c < n_cols; ++c) h->keys[c] = nk[c].release();
+  h->n_keys = n_cols;
+  return RAG_OK;
+}
+
+int rag_index_keys_cols(const rag_index_t* h) { return h ? h->n_keys : -1; }
+
+namespace {
+
+// the shared argument checks of write_keys / gather_keys; *go = false when there is nothing to do
+int keys_args(rag_index* h, const int64_t* rows, const void* other, int64_t n, bool* go) {
+  *go = false;
+  if (n < 0) return ragmi::fail(RAG_EINVAL, "keys: n must be >= 0");
+  if (n > 0 && (!rows || !other)) return ragmi::fail(RAG_EINVAL, "keys: a NULL rows or keys pointer");
+  if (!h) return ragmi::fail(RAG_EINVAL, "keys: index is NULL");
+  *go = n > 0;
+  return RAG_OK;
+}
+
+}  // namespace
+
+int rag_index_write_keys(rag_index_t* h, int col, const int64_t* rows, const int64_t* keys,
+                         int64_t n, void* stream) {
+  ragmi::clear_error();
+  bool go = false;
+  if (const int rc = keys_args(h, rows, keys, n, &go)) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (col < 0 || col >= h->n_keys)
+    return ragmi::fail(RAG_ERANGE, "keys: no such column (call rag_index_keys_create)");
+  if (!go) return RAG_OK;
+  RAG_HIP(hipSetDevice(h->device));
+  const dim3 grid((unsigned)((n + ragmi::kKeyBlock - 1) / ragmi::kKeyBlock));
+  ragmi::write_keys_kernel<<<grid, dim3(ragmi::kKeyBlock), 0, st>>>(h->keys[col], rows, keys, n,
+                                                                     h->cap_rows);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+int rag_index_gather_keys(rag_index_t* h, int col, const int64_t* rows, int64_t n,
+                          int64_t* out_keys, void* stream) {
+  ragmi::clear_error();
+  bool go = false;
+  if (const int rc = keys_args(h, rows, out_keys, n, &go)) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (col < 0 || col >= h->n_keys)
+    return ragmi::fail(RAG_ERANGE, "keys: no such column (call rag_index_keys_create)");
+  if (!go) return RAG_OK;
+  RAG_HIP(hipSetDevice(h->device));
+  const dim3 grid((unsigned)((n + ragmi::kKeyBlock - 1) / ragmi::kKeyBlock));
+  ragmi::gather_keys_kernel<<<grid, dim3(ragmi::kKeyBlock), 0, st>>>(h->keys[col], rows, n,
+                                                                      h->cap_rows, out_keys);
   RAG_HIP(hipGetLastError());
   return RAG_OK;
 }

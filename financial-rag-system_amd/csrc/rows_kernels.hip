@@ -1,12 +1,13 @@
 // rows_kernels.hip — row-wise access to the flat index (included by index_capi.hip last; it
 // needs only the tile16 layout of prep_kernels.hip): the ordered tag select and the indexed row
 // copies behind rag_index_select_rows / move_rows / gather_rows / scatter_rows, the grouped
-// search's tag gather behind rag_index_gather_tags (include/ragmi.h), and the export / import
-// of rows between tile16 and row-major (persistence).
+// search's tag gather behind rag_index_gather_tags (include/ragmi.h), the export / import
+// of rows between tile16 and row-major (persistence), and the key columns' fill / write /
+// gather / move (rag_index_keys_create, write_keys, gather_keys, move_rows).
 //
 // A deleted row is physically removed: a surviving row from the tail takes its slot in every
-// stored form (the fp16 tile16 pieces, the fp32 row of an fp32-storage index, the tag), bit
-// for bit, and the count shrinks. The index stays dense, so the scan, select, large-k and
+// stored form (the fp16 tile16 pieces, the fp32 row of an fp32-storage index, the tag, the key
+// of every key column), bit for bit, and the count shrinks. The index stays dense, so the scan, select, large-k and
 // full-pass kernels never learn that a delete happened ("Deleting points").
 // No reference counterpart beyond QdrantClient.delete itself: the reference only ever upserts
 // (ingest.py:171-175) and leaves removal to the Qdrant server.
@@ -277,6 +278,59 @@ __global__ void import32_kernel(const float* __restrict__ in, int64_t row0, int6
     h[j] = f32_to_f16(src[j]);
   }
   corpus[tile_slot<D>(row, c)] = h;
+}
+
+// ----------------------------------------------------------------------------------------
+// key columns (include/ragmi.h "Key columns"): up to RAG_KEYS_MAX_COLS int64 columns of
+// cap_rows keys beside the tags, what the RANGE atom of filter_view_kernel compares. One thread
+// per element in all four kernels; a row index outside [0, cap_rows) is never dereferenced.
+//   fill_keys_kernel    keys[r] = RAG_KEY_ABSENT for r in [row0, cap_rows) (create, reserve)
+//   write_keys_kernel   keys[rows[i]] = vals[i]                  (rows distinct)
+//   gather_keys_kernel  out[i] = keys[rows[i]], RAG_KEY_ABSENT outside — gather_tags' guard
+//   move_keys_kernel    every column's key of row src[i] -> row dst[i], a pair with either row
+//                       outside skipped, as copy_rows_kernel skips it (sets disjoint)
+// ----------------------------------------------------------------------------------------
+constexpr int kKeyBlock = 256;
+
+// the index's columns as a kernel argument; entries at or past the column count are nullptr
+struct KeyCols {
+  int64_t* col[RAG_KEYS_MAX_COLS];
+};
+
+__global__ __launch_bounds__(kKeyBlock) void fill_keys_kernel(int64_t* __restrict__ keys,
+                                                              int64_t row0, int64_t cap_rows) {
+  const int64_t r = row0 + (int64_t)blockIdx.x * kKeyBlock + threadIdx.x;
+  if (r < cap_rows) keys[r] = RAG_KEY_ABSENT;
+}
+
+__global__ __launch_bounds__(kKeyBlock) void write_keys_kernel(
+    int64_t* __restrict__ keys, const int64_t* __restrict__ rows,
+    const int64_t* __restrict__ vals, int64_t n, int64_t cap_rows) {
+  const int64_t i = (int64_t)blockIdx.x * kKeyBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = rows[i];
+  if (r >= 0 && r < cap_rows) keys[r] = vals[i];
+}
+
+__global__ __launch_bounds__(kKeyBlock) void gather_keys_kernel(
+    const int64_t* __restrict__ keys, const int64_t* __restrict__ rows, int64_t n,
+    int64_t cap_rows, int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kKeyBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = rows[i];
+  out[i] = (r >= 0 && r < cap_rows) ? keys[r] : RAG_KEY_ABSENT;
+}
+
+__global__ __launch_bounds__(kKeyBlock) void move_keys_kernel(
+    KeyCols keys, int n_cols, const int64_t* __restrict__ src_rows,
+    const int64_t* __restrict__ dst_rows, int64_t n, int64_t cap_rows) {
+  const int64_t i = (int64_t)blockIdx.x * kKeyBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t s = src_rows[i], d = dst_rows[i];
+  if (s < 0 || s >= cap_rows || d < 0 || d >= cap_rows) return;
+#pragma unroll
+  for (int c = 0; c < RAG_KEYS_MAX_COLS; ++c)
+    if (c < n_cols) keys.col[c][d] = keys.col[c][s];
 }
 
 }  // namespace ragmi

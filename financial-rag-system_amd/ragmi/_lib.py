@@ -122,6 +122,12 @@ INDEX_API = {
     "rag_index_mmr": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rag_index_gather_tags": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
+    "rag_index_keys_create": (ctypes.c_int, [c_vp, ctypes.c_int]),
+    "rag_index_keys_cols": (ctypes.c_int, [c_vp]),
+    "rag_index_write_keys": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int64,
+                                            c_vp]),
+    "rag_index_gather_keys": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int64, c_vp,
+                                             c_vp]),
     "rag_group_select": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                         c_vp, c_vp, c_vp, c_vp, c_vp]),

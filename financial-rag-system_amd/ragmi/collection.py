@@ -17,8 +17,9 @@ import torch
 from . import groups
 from . import qdrant_models as models
 from .coalesce import Coalescer
-from .filters import (DEFAULT_TAG_FIELDS, MAX_PROGRAMS, FilterProgram, PayloadTags,
-                      UnsupportedFilter, compile_filter, compile_legacy_only, pack_view)
+from .filters import (DEFAULT_TAG_FIELDS, MAX_PROGRAMS, FilterProgram, PayloadRanges,
+                      PayloadTags, UnsupportedFilter, compile_filter, compile_legacy_only,
+                      pack_view)
 from .index import (FUSION_MAX_ENTRIES, GROUPS_MAX, GROUPS_MAX_CELLS, FlatIndex, fuse_rrf,
                     hits_of, host_or_tensor)
 from .shardset import ShardSet, parse_devices
@@ -85,13 +86,25 @@ class Collection:
     (one device index per shard, ragmi.shardset.parse_devices) the rows are striped over a
     ShardSet instead; rows, ids, payloads and tags stay global and host-side either way.
     `index`: an object to use as the index (the protocol of DESIGN.md "Where the front end
-    lives"); no FlatIndex / ShardSet is created then."""
+    lives"); no FlatIndex / ShardSet is created then.
+    `range_fields`: the numeric payload fields `range` conditions may name, a mapping of field
+    to kind ("number" or "datetime") or a sequence of names all meaning "number" (at most 4;
+    ragmi.filters.PayloadRanges). Each is a key column of the index, written with every upsert.
+    A collection without any never calls the index's key methods."""
+
+    BACKFILL_ROWS = 1 << 16      # rows per write_keys call of add_range_field
 
     def __init__(self, name: str, dim: int, device, tag_fields=DEFAULT_TAG_FIELDS,
-                 capacity: int = 1024, storage: str = "fp32", devices=None, *, index=None):
+                 capacity: int = 1024, storage: str = "fp32", devices=None, *, index=None,
+                 range_fields=None):
         self.name = name
         self.dim = dim
         self.tags = PayloadTags(tag_fields)
+        self.ranges = PayloadRanges(range_fields)
+        clash = set(self.ranges.fields) & set(self.tags.fields)
+        if clash:
+            raise ValueError(f"{sorted(clash)}: a field is a keyword tag field or a range field, "
+                             "not both")
         devices = parse_devices(devices)
         self.index = (index if index is not None else
                       ShardSet(dim=dim, devices=devices, capacity=capacity, storage=storage)
@@ -107,6 +120,8 @@ class Collection:
         # 32 queries per scan pass at D = 384, 4 groups of 32 at D = 1024 (ragmi.h)
         self.coalescer = Coalescer(self, 0.0, 32 if dim <= 384 else 128,
                                    search=self.search_points)
+        if len(self.ranges):
+            self.index.keys_create(len(self.ranges))
 
     @property
     def rescued(self) -> int:
@@ -119,8 +134,32 @@ class Collection:
         self.index.rescued = n
 
     def compile_filter(self, flt):
-        """ragmi.filters.compile_filter over this collection's tags."""
-        return compile_filter(self.tags, flt)
+        """ragmi.filters.compile_filter over this collection's tags and range fields."""
+        return compile_filter(self.tags, flt, self.ranges)
+
+    def add_range_field(self, name: str, kind: str) -> bool:
+        """Declare range field `name` ("number" or "datetime") on a collection that may hold
+        points — the engine of create_payload_index. Under the lock: the index grows a key
+        column, the column is back-filled from the host payloads of all current rows in chunks
+        of BACKFILL_ROWS, and the stream is synchronised. False when the field was declared
+        already (with the same kind); ValueError for another kind, a tag field, or a fifth
+        field."""
+        with self.lock:
+            if name in self.tags.fields:
+                raise ValueError(f"{name!r} is a keyword tag field, it cannot be a range field")
+            if name in self.ranges.fields:
+                self.ranges.add(name, kind)          # same kind, or ValueError
+                return False
+            col = self.ranges.add(name, kind)
+            self.index.keys_create(col + 1)
+            n = len(self.row_ids)
+            for r0 in range(0, n, self.BACKFILL_ROWS):
+                rows = np.arange(r0, min(n, r0 + self.BACKFILL_ROWS), dtype=np.int64)
+                keys = [self.ranges.keys(p)[col] for p in self.payloads[r0:r0 + len(rows)]]
+                self.index.write_keys(col, rows, np.asarray(keys, dtype=np.int64))
+            if n:
+                torch.cuda.current_stream(self.index.device).synchronize()
+            return True
 
     # ---------------------------------------------------------------- writes
     def upsert(self, ids: list, vectors, payloads: list) -> int:
@@ -133,7 +172,7 @@ class Collection:
             last: dict[Any, int] = {}
             for i, pid in enumerate(ids):
                 last[_norm_id(pid)] = i
-            rows, sel, tags = [], [], []
+            rows, sel, tags, keys = [], [], [], []
             new_count = len(self.row_ids)
             for pid, i in last.items():
                 r = self.id_to_row.get(pid)
@@ -150,12 +189,19 @@ class Collection:
                 rows.append(r)
                 sel.append(i)
                 tags.append(self.tags.tag(p))
+                if len(self.ranges):
+                    keys.append(self.ranges.keys(p))
             if new_count > self.index.capacity:
                 self.index.reserve(max(new_count, 2 * self.index.capacity))
             if rows:
                 sel_t = vec[sel] if isinstance(vec, torch.Tensor) else vec[np.asarray(sel)]
                 self.index.upsert(sel_t, np.asarray(rows, dtype=np.int64),
                                   np.asarray(tags, dtype=np.uint32), new_count=new_count)
+                # every column of every written row, under this hold of the lock: an overwrite
+                # whose payload lacks the field writes KEY_ABSENT
+                for c, col_keys in enumerate(np.asarray(keys, dtype=np.int64).T if keys else ()):
+                    self.index.write_keys(c, np.asarray(rows, dtype=np.int64),
+                                          np.ascontiguousarray(col_keys))
             return self.op
 
     def delete(self, points_selector) -> int:
@@ -168,7 +214,7 @@ class Collection:
         kind, what = parse_selector(points_selector)
         with self.lock:
             # may refuse the filter
-            flt = (compile_legacy_only(self.tags, what, "Collection.delete")
+            flt = (compile_legacy_only(self.tags, what, "Collection.delete", self.ranges)
                    if kind == "filter" else None)
             self.op += 1
             if kind == "ids":

@@ -373,6 +373,39 @@ class FlatIndex(ListOps):
                                                 _stream_ptr(self.device)))
         return out
 
+    # ---------------------------------------------------------------- key columns
+    def keys_create(self, n_cols: int) -> None:
+        """Make the index hold `n_cols` key columns (1..4; rag_index_keys_create): int64
+        [capacity] each, what the RANGE atom of a filter program compares. The number only
+        grows; new columns hold KEY_ABSENT. Synchronises the device."""
+        check(self._L.rag_index_keys_create(self._h, int(n_cols)))
+
+    def keys_cols(self) -> int:
+        """The number of key columns (rag_index_keys_cols)."""
+        return int(self._L.rag_index_keys_cols(self._h))
+
+    def write_keys(self, col: int, rows, keys) -> None:
+        """keys[col][rows[i]] = keys[i] (int64 [n]; rag_index_write_keys): distinct rows, one
+        outside [0, capacity) is skipped. Enqueued on the current stream."""
+        r = _as_dev(rows, torch.int64, self.device).reshape(-1)
+        k = _as_dev(keys, torch.int64, self.device).reshape(-1)
+        if r.shape != k.shape:
+            raise ValueError("rows and keys must pair up")
+        check(self._L.rag_index_write_keys(self._h, int(col), r.data_ptr() if r.numel() else None,
+                                           k.data_ptr() if r.numel() else None, r.numel(),
+                                           _stream_ptr(self.device)))
+
+    def gather_keys(self, col: int, rows) -> torch.Tensor:
+        """The keys of column `col` at `rows` (int64, any shape; rag_index_gather_keys): an
+        int64 tensor of the same shape, KEY_ABSENT for a row outside [0, capacity) — such a row
+        is never dereferenced. Enqueued on the current stream."""
+        r = _as_dev(rows, torch.int64, self.device)
+        out = torch.empty(r.shape, dtype=torch.int64, device=self.device)
+        check(self._L.rag_index_gather_keys(self._h, int(col), r.data_ptr() if r.numel() else None,
+                                            r.numel(), out.data_ptr() if r.numel() else None,
+                                            _stream_ptr(self.device)))
+        return out
+
     # ---------------------------------------------------------------- row removal
     def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None,
                     out: torch.Tensor | None = None):

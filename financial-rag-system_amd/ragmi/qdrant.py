@@ -173,7 +173,7 @@ def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=Fals
     for r in reqs:
         q, mmr = nearest_of(r.query)
         qs.append(q)
-        filters.append(compile_filter(col.tags, r.filter))
+        filters.append(col.compile_filter(r.filter))
         if route == MMR:
             d, c = mmr_params(mmr, r.limit) if mmr is not None else (0.0, max(int(r.limit), 1))
             div.append(d)
@@ -249,7 +249,10 @@ class QdrantClient:
 
     def create_collection(self, collection_name: str, vectors_config: models.VectorParams,
                           payload_tag_fields: Iterable[str] = DEFAULT_TAG_FIELDS,
-                          capacity: int = 1024, **kwargs) -> bool:
+                          capacity: int = 1024, payload_range_fields=None, **kwargs) -> bool:
+        """`payload_range_fields`: the numeric payload fields `range` conditions may name, a
+        mapping of field to "number" / "datetime" or a sequence of number fields
+        (Collection(range_fields=...)); create_payload_index adds one later."""
         if vectors_config.distance != models.Distance.COSINE:
             raise NotImplementedError("only Distance.COSINE collections (database.py:126)")
         storage = _storage_of(vectors_config)
@@ -258,10 +261,36 @@ class QdrantClient:
                 raise ValueError(f"collection {collection_name!r} already exists")
             col = Collection(collection_name, int(vectors_config.size), self.device,
                              tuple(payload_tag_fields), capacity, storage,
-                             devices=self.devices)
+                             devices=self.devices, range_fields=payload_range_fields)
             col.coalescer.window = self.coalesce_window_s
             self._collections[collection_name] = col
         return True
+
+    def create_payload_index(self, collection_name: str, field_name: str, field_schema=None,
+                             **kwargs) -> models.UpdateResult:
+        """Qdrant's create_payload_index. PayloadSchemaType.INTEGER / FLOAT declare `field_name`
+        a number range field, DATETIME a datetime range field (Collection.add_range_field: a
+        key column in HBM, back-filled from the points the collection holds); KEYWORD on one of
+        the collection's payload_tag_fields is accepted as a no-op. Repeating a call with the
+        same schema is a no-op; a fifth range field is a ValueError; any other schema is
+        NotImplementedError."""
+        col = self._col(collection_name)
+        schema = getattr(field_schema, "value", field_schema)
+        schema = schema.lower() if isinstance(schema, str) else schema
+        kinds = {models.PayloadSchemaType.INTEGER.value: "number",
+                 models.PayloadSchemaType.FLOAT.value: "number",
+                 models.PayloadSchemaType.DATETIME.value: "datetime"}
+        if schema == models.PayloadSchemaType.KEYWORD.value:
+            if field_name not in col.tags.fields:
+                raise NotImplementedError(
+                    f"a keyword index on {field_name!r}: keyword fields are fixed when the "
+                    f"collection is created (payload_tag_fields={col.tags.fields})")
+        elif schema in kinds:
+            col.add_range_field(field_name, kinds[schema])
+        else:
+            raise NotImplementedError(f"payload index schema {field_schema!r} is not supported "
+                                      "(keyword, integer, float and datetime are)")
+        return models.UpdateResult(operation_id=col.op, status=models.UpdateStatus.COMPLETED)
 
     def recreate_collection(self, collection_name: str, vectors_config, **kwargs) -> bool:
         self.delete_collection(collection_name)
@@ -331,7 +360,7 @@ class QdrantClient:
         col = self._col(collection_name)
         route = route_of(query, prefetch)
         if route == PLAIN and self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
-            flt = compile_filter(col.tags, query_filter)
+            flt = col.compile_filter(query_filter)
             q = stack_queries([nearest_of(query)[0]], col.dim, one=True, host=True)[0]
             pts = col.coalescer.search(q, int(limit), flt)
         else:

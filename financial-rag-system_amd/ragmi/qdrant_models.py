@@ -71,7 +71,42 @@ class MatchExcept:
 
 
 @dataclass
+class Range:
+    """FieldCondition(key, range=Range(...)) on a number field: the value lies above `gt` /
+    at or above `gte` and below `lt` / at or below `lte`; None = no bound on that side."""
+    lt: Optional[float] = None
+    gt: Optional[float] = None
+    gte: Optional[float] = None
+    lte: Optional[float] = None
+
+
+@dataclass
+class DatetimeRange:
+    """Range on a datetime field: the bounds are RFC 3339 / ISO-8601 strings, or datetime /
+    date objects (naive values are UTC, a date is its midnight)."""
+    lt: Any = None
+    gt: Any = None
+    gte: Any = None
+    lte: Any = None
+
+
+class PayloadSchemaType(str, enum.Enum):
+    """field_schema of QdrantClient.create_payload_index. INTEGER / FLOAT / DATETIME declare a
+    range field, KEYWORD names an existing tag field; the others are refused."""
+    KEYWORD = "keyword"
+    INTEGER = "integer"
+    FLOAT = "float"
+    DATETIME = "datetime"
+    BOOL = "bool"
+    GEO = "geo"
+    TEXT = "text"
+    UUID = "uuid"
+
+
+@dataclass
 class FieldCondition:
+    """`match` or `range` (a Range, a DatetimeRange, or a dict with the keys lt / gt / gte /
+    lte), not both."""
     key: str
     match: Any = None
     range: Any = None

@@ -123,10 +123,13 @@ def _match(value):
     return models.MatchValue(value=value.upper())
 
 
-def _filter(ticker, document_type=None):
+def _filter(ticker, document_type=None, ingested_since=None, ingested_until=None):
     must = [models.FieldCondition(key="ticker", match=_match(ticker))]
     if document_type:
         must.append(models.FieldCondition(key="document_type", match=_match(document_type)))
+    if ingested_since is not None or ingested_until is not None:
+        must.append(models.FieldCondition(key="ingested_at", range=models.DatetimeRange(
+            gte=ingested_since, lt=ingested_until)))
     return models.Filter(must=must)
 
 
@@ -155,8 +158,15 @@ def _fusion(vector, rewrites, flt, limit, rrf_k, diversity, candidates):
 
 
 def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEVE_LIMIT, *,
-                         diversity=None, candidates=None, rewrites=None, rrf_k=None):
-    """diversity / candidates (keyword-only, not in the reference): MMR re-selection of the
+                         diversity=None, candidates=None, rewrites=None, rrf_k=None,
+                         ingested_since=None, ingested_until=None):
+    """ingested_since / ingested_until (keyword-only, not in the reference): only chunks whose
+    `ingested_at` timestamp lies in [since, until) — RFC 3339 strings or datetime / date objects,
+    either may be None; a DatetimeRange on `ingested_at` joins the `must` list. The collection
+    needs `ingested_at` declared a datetime range field (one
+    create_payload_index line); without it the filter is refused, which reads as no documents
+    here, as every failure does. Both None is today's call.
+    diversity / candidates (keyword-only, not in the reference): MMR re-selection of the
     `limit` hits from the `candidates` nearest (Mmr's defaults where one is None), so
     near-duplicate chunks do not fill the list; both None is the reference's call.
     rewrites (keyword-only): extra query vectors for the same question; the lists of the
@@ -166,8 +176,9 @@ def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEV
     if _testing():
         return type("obj", (object,), {"points": []})
     if rewrites is not None:
-        query, prefetch = _fusion(query_vector, rewrites, _filter(ticker, document_type), limit,
-                                  rrf_k, diversity, candidates)
+        query, prefetch = _fusion(query_vector, rewrites,
+                                  _filter(ticker, document_type, ingested_since, ingested_until),
+                                  limit, rrf_k, diversity, candidates)
         try:
             return get_qdrant().query_points(collection_name=COLLECTION_NAME, query=query,
                                              prefetch=prefetch, limit=limit)
@@ -180,7 +191,8 @@ def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEV
         return get_qdrant().query_points(collection_name=COLLECTION_NAME,
                                          query=_query(query_vector, diversity, candidates),
                                          limit=limit,
-                                         query_filter=_filter(ticker, document_type))
+                                         query_filter=_filter(ticker, document_type,
+                                                              ingested_since, ingested_until))
     except Exception:
         return type("obj", (object,), {"points": []})
 

@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .filters import KEY_ABSENT
 from .index import FlatIndex, ListOps, _as_dev, host_or_tensor, plan_removal, view_blob
 
 MAX_SHARDS = 64      # RAG_MAX_SHARDS in include/ragmi.h
@@ -273,6 +274,46 @@ class ShardSet(ListOps):
             self._settle(shard)
         self._count = int(new_count)
 
+    # ---------------------------------------------------------------- key columns
+    @_keeps_device
+    def keys_create(self, n_cols: int) -> None:
+        """FlatIndex.keys_create on every shard."""
+        for shard in self.shards:
+            shard.keys_create(n_cols)
+
+    def keys_cols(self) -> int:
+        return self.shards[0].keys_cols()
+
+    @_keeps_device
+    def write_keys(self, col: int, rows, keys) -> None:
+        """FlatIndex.write_keys in global rows, striped like upsert: each key goes to the shard
+        of its row."""
+        r = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        k = keys.detach().cpu().numpy() if isinstance(keys, torch.Tensor) else np.asarray(keys)
+        r, k = r.astype(np.int64).reshape(-1), k.astype(np.int64).reshape(-1)
+        if r.shape != k.shape:
+            raise ValueError("rows and keys must pair up")
+        for s, shard in enumerate(self.shards):
+            sel = np.nonzero((r >= 0) & (shard_of(r, self.n) == s))[0]
+            if sel.size:
+                shard.write_keys(col, local_of(r[sel], self.n), k[sel])
+                self._settle(shard)
+
+    @_keeps_device
+    def gather_keys(self, col: int, global_rows) -> torch.Tensor:
+        """FlatIndex.gather_keys in global rows, as gather_tags: every shard gathers the keys of
+        its own rows and the results are merged on the merge device; KEY_ABSENT for a row
+        outside [0, capacity)."""
+        g = _as_dev(global_rows, torch.int64, self.device)
+        valid = (g >= 0) & (g < self.capacity)
+        out = torch.full(g.shape, KEY_ABSENT, dtype=torch.int64, device=self.device)
+        for sh, shard in enumerate(self.shards):
+            own = valid & (shard_of(g, self.n) == sh)
+            local = torch.where(own, local_of(g, self.n), -1)
+            out = torch.where(own, shard.gather_keys(col, local.to(shard.device)).to(self.device),
+                              out)
+        return out
+
     # ---------------------------------------------------------------- row removal
     @_keeps_device
     def remove_rows(self, global_rows):
@@ -293,6 +334,8 @@ class ShardSet(ListOps):
                 to = self.shards[d].device
                 self.shards[d].scatter_rows(ld, f16.to(to), f32.to(to) if f32 is not None
                                             else None, tags.to(to), cnt)
+                for c in range(self.keys_cols()):     # the keys travel with the staged rows
+                    self.shards[d].write_keys(c, ld, self.shards[s].gather_keys(c, ls).to(to))
         for s, shard in enumerate(self.shards):
             cnt = shard_count(n1, s, self.n)
             if shard.count != cnt:

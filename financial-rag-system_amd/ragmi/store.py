@@ -13,7 +13,9 @@ A shard directory holds exactly what the GPU index stores, so loading is a byte 
 
 A collection directory adds the host-side state of `collection.Collection`:
 
-  collection.json    name, dim, distance, tag fields + codebooks, op counter
+  collection.json    name, dim, distance, tag fields + codebooks, op counter, and
+                     "range_fields": [[field, kind], ...] when the collection has range fields
+                     (their key columns are not saved: load re-derives them from the payloads)
   points.jsonl       one line per row, in row order: {"id": ..., "version": v, "payload": {...}}
   shard/             the shard above
 
@@ -223,11 +225,13 @@ def save_collection(col, path: str) -> None:
             for pid, ver, pl in zip(col.row_ids, col.versions, col.payloads):
                 f.write(json.dumps({"id": pid, "version": ver, "payload": pl}) + "\n")
         os.replace(tmp, os.path.join(path, "points.jsonl"))
-        _write_json(os.path.join(path, "collection.json"), {
-            "name": col.name, "dim": col.dim, "distance": "Cosine", "op": col.op,
-            "storage": col.index.storage,
-            "tag_fields": list(col.tags.fields),
-            "codebooks": [[[v, c] for v, c in t.items()] for t in col.tags.codes]})
+        cj = {"name": col.name, "dim": col.dim, "distance": "Cosine", "op": col.op,
+              "storage": col.index.storage,
+              "tag_fields": list(col.tags.fields),
+              "codebooks": [[[v, c] for v, c in t.items()] for t in col.tags.codes]}
+        if len(col.ranges):      # only then: a collection without range fields saves as it did
+            cj["range_fields"] = [[f, k] for f, k in zip(col.ranges.fields, col.ranges.kinds)]
+        _write_json(os.path.join(path, "collection.json"), cj)
 
 
 def load_collection(path: str, device=None, devices=None):
@@ -240,7 +244,8 @@ def load_collection(path: str, device=None, devices=None):
     meta = read_meta(os.path.join(path, "shard"))
     col = Collection(cj["name"], int(cj["dim"]), device, tuple(cj["tag_fields"]),
                      capacity=max(meta["count"], 1024),
-                     storage=cj.get("storage", meta.get("storage", "fp16")), devices=devices)
+                     storage=cj.get("storage", meta.get("storage", "fp16")), devices=devices,
+                     range_fields=dict(cj.get("range_fields", [])) or None)
     for f_i, book in enumerate(cj["codebooks"]):
         col.tags.codes[f_i] = {v: int(c) for v, c in book}
     with open(os.path.join(path, "points.jsonl")) as f:
@@ -255,4 +260,12 @@ def load_collection(path: str, device=None, devices=None):
         raise ValueError(f"{path}: {len(col.row_ids)} points but {meta['count']} shard rows")
     col.op = int(cj["op"])
     load_into(col.index, os.path.join(path, "shard"))
+    # the keys are not saved: they are re-derived from the loaded payloads, column by column
+    n = len(col.row_ids)
+    for r0 in range(0, n if len(col.ranges) else 0, col.BACKFILL_ROWS):
+        m = min(col.BACKFILL_ROWS, n - r0)
+        keys = np.asarray([col.ranges.keys(p) for p in col.payloads[r0:r0 + m]], dtype=np.int64)
+        for c in range(len(col.ranges)):
+            col.index.write_keys(c, np.arange(r0, r0 + m, dtype=np.int64),
+                                 np.ascontiguousarray(keys[:, c]))
     return col

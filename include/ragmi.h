@@ -201,8 +201,9 @@ int rag_index_export_tags(rag_index_t* index, int64_t row0, int64_t n, uint32_t*
 int rag_index_select_rows(rag_index_t* index, uint32_t tag_mask, uint32_t tag_value,
                           int64_t* out_rows_dev, int64_t cap, int64_t* out_n_dev, void* stream);
 /* Copy every stored form of row src_rows_dev[i] into slot dst_rows_dev[i] (int64 [n], device):
- * the fp16 tile16 pieces, the fp32 row of an fp32-storage index and the tag, bit for bit (no
- * renormalisation), one read and one write per byte; then count = new_count.
+ * the fp16 tile16 pieces, the fp32 row of an fp32-storage index, the tag and the key of every
+ * key column ("Key columns" below), bit for bit (no renormalisation), one read and one write per
+ * byte; then count = new_count.
  * Precondition: the src and dst sets are disjoint (a row is never both read and written). */
 int rag_index_move_rows(rag_index_t* index, const int64_t* src_rows_dev,
                         const int64_t* dst_rows_dev, int64_t n, int64_t new_count, void* stream);
@@ -393,14 +394,23 @@ int rag_shardset_search(rag_shardset_t* set, const float* queries_dev, int B, in
  *       [9 + 4 i .. 12 + 4 i], i < 8: atom i = (kind, p0, p1, p2); unused atoms are zero
  *   words [41 U, words): the bitmap pool; an INSET atom's p1 is a word offset from the blob's
  *       start.
+ *   RAG_FILTER_ATOM_RANGE  (p0 = key column, p1 = word offset of the bounds, p2 = 0):
+ *       with key = keys[p0][row] (the index's key columns, below): key != RAG_KEY_ABSENT and
+ *       lo <= key <= hi as signed 64-bit integers. The bounds are 4 words of the pool, at p1:
+ *       lo low, lo high, hi low, hi high. An absent key is in no range.
  * The blob is never trusted: a bitmap word is read only when its index is < words (a code whose
- * word lies outside is "not a member"), so a malformed blob gives wrong bits, never a read
- * outside the blob.
+ * word lies outside is "not a member"), and a RANGE atom is false, with neither its bounds nor a
+ * key read, when p0 >= the index's number of key columns or p1 + 3 >= words; so a malformed
+ * blob gives wrong bits, never a read outside the blob or a column. An index WITHOUT key columns
+ * runs the kernel of the releases before RANGE existed, to which kind 2 is an unknown kind, read
+ * as MASKEQ like every unknown kind: create the columns (rag_index_keys_create) before sending
+ * RANGE atoms.
  *
  * rag_index_filter_view: out_view_dev[r] (uint32 [capacity], 16-byte aligned, device) = sum
  * over s < n_programs of pass_s(tag[r]) << s for r < count, 0 for count <= r < capacity; nothing
  * past out_view_dev[capacity - 1] is written. One streaming launch: 4 B read and 4 B written per
- * row.
+ * row, plus 8 B read per row for every key column that a RANGE atom of the blob names (each such
+ * column is read once, however many atoms name it).
  * rag_index_search_view: rag_index_search over that view instead of the stored tags, under one
  * hold of the handle's lock: filter_view_kernel runs once on `stream` ahead of the first pass
  * into a view column the handle keeps per stream (4 B per row of capacity, allocated on a
@@ -423,6 +433,7 @@ int rag_shardset_search(rag_shardset_t* set, const float* queries_dev, int B, in
 #define RAG_FILTER_REC_WORDS 41
 #define RAG_FILTER_ATOM_MASKEQ 0
 #define RAG_FILTER_ATOM_INSET 1
+#define RAG_FILTER_ATOM_RANGE 2
 #define RAG_SEARCH_FULL 1
 int rag_index_filter_view(rag_index_t* index, const uint32_t* progs_dev, int64_t words,
                           int n_programs, uint32_t* out_view_dev, void* stream);
@@ -438,6 +449,43 @@ int rag_shardset_search_view(rag_shardset_t* set, const float* queries_dev, int 
                              const uint32_t* progs_dev, int64_t words, int n_programs,
                              const uint32_t* filters_dev, int flags, float* out_scores_dev,
                              int64_t* out_ids_dev, uint8_t* out_empty_dev, void* stream);
+
+/* Key columns (range and datetime filters: the numeric payload fields of a collection, in HBM).
+ * An index holds 0 to RAG_KEYS_MAX_COLS columns, each int64 [capacity] (8 B per row, the tag
+ * array's extent: a multiple of 16 rows). A column holds KEYS: for a double x, -0.0 taken as
+ * +0.0, with b its IEEE-754 bits as int64, key(x) = b if b >= 0, else b ^ 0x7FFFFFFFFFFFFFFF,
+ * so that a signed compare of keys is the numeric compare of the doubles (ragmi.filters.key_of).
+ * RAG_KEY_ABSENT = INT64_MIN is "no value"; no double maps to it (key(-inf) =
+ * 0x800FFFFFFFFFFFFF). The RANGE atom of a filter program compares them ("Filter programs").
+ *
+ * rag_index_keys_create: make the index hold n_cols columns (1..RAG_KEYS_MAX_COLS; RAG_ERANGE
+ * outside). The number only ever grows: fewer than the index has is a no-op. New columns are
+ * filled with RAG_KEY_ABSENT, existing ones keep their content. Synchronises the device.
+ * rag_index_keys_cols: the number of columns (-1 for NULL).
+ * rag_index_write_keys: keys[col][rows_dev[i]] = keys_dev[i], i < n (int64, device). A row
+ * outside [0, capacity) is skipped and never dereferenced; the rows must be distinct.
+ * rag_index_gather_keys: out_keys_dev[i] = keys[col][rows_dev[i]], RAG_KEY_ABSENT for a row
+ * outside [0, capacity) (never dereferenced) — rag_index_gather_tags for a key column.
+ * Both are asynchronous on `stream`; col outside [0, columns) is RAG_ERANGE.
+ *
+ * The keys are a stored form of the row: rag_index_move_rows moves every column's key with the
+ * row (a kernel of its own on the same stream under the same hold of the lock, launched only
+ * when the index has columns), rag_index_reserve regrows the columns (old rows keep their keys,
+ * new rows hold RAG_KEY_ABSENT), rag_index_destroy frees them. rag_index_upsert, the imports,
+ * rag_index_gather_rows and rag_index_scatter_rows do NOT touch them: the host layer writes
+ * every column of every row it upserts, and carries the keys of rows it moves between indexes
+ * (gather_keys / write_keys). Row invariant: the keys of rows >= count are unspecified (a
+ * delete leaves stale values in the tail); nothing exposes them, the filter view being 0 for
+ * those rows. No reference counterpart: the reference leaves range conditions to the Qdrant
+ * server and sends none itself. */
+#define RAG_KEYS_MAX_COLS 4
+#define RAG_KEY_ABSENT INT64_MIN
+int rag_index_keys_create(rag_index_t* index, int n_cols);
+int rag_index_keys_cols(const rag_index_t* index);
+int rag_index_write_keys(rag_index_t* index, int col, const int64_t* rows_dev,
+                         const int64_t* keys_dev, int64_t n, void* stream);
+int rag_index_gather_keys(rag_index_t* index, int col, const int64_t* rows_dev, int64_t n,
+                          int64_t* out_keys_dev, void* stream);
 
 /* Exactness bookkeeping (tests, bench): tier1 / tier2 = number of queries, since the index
  * was created, whose top-k was certified by the list re-scoring fallback / needed the second

@@ -14,6 +14,15 @@ each timed by a HIP event pair around the call:
                 2-atom programs
   d  shared     (c) with all 32 queries sharing query 0's program (one view bit)
   v  view_only  filter_view_kernel alone over (b)'s blob (rag_index_filter_view)
+  r  range      the 32 filters of (b), each with one RANGE atom on key column 0 that passes
+                about half the rows (program j: key in [j, j + 499] of a key r % 1000)
+  r4 range4     the same with four RANGE atoms, one on each of four key columns
+  rv range_view_only  filter_view_kernel alone over (r)'s blob
+--kinds takes the letters run together ("abv") or, with the two-letter kinds, a comma list
+("a,b,v,r,r4,rv"). --key-cols N gives the index N key columns (column c of row r holds the key
+of (r // (c + 1)) % 1000) whatever the kinds, so that a, b and v can be timed on an index with
+columns; r and rv need one, r4 four, and get them. For rv the line also reports the achieved
+bytes/s against 8 B + 8 B per referenced column per row.
 One JSON line with the medians and ranges, to stdout and appended to --out (default
 profiles/filters_timing.jsonl). --kinds picks a subset; `--kinds a --pkg DIR` times the legacy
 path of ANOTHER checkout's package (the parent commit's, built in place), interleaved process
@@ -56,14 +65,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--kinds", default="abcdv")
+    ap.add_argument("--key-cols", type=int, default=0)
     ap.add_argument("--pkg", default=os.path.join(ROOT, "financial-rag-system_amd"))
     ap.add_argument("--label", default="this")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filters_timing.jsonl"))
     args = ap.parse_args()
+    kinds = set(args.kinds.split(",")) if "," in args.kinds else set(args.kinds)
+    args.kinds = "".join(k for k in kinds if len(k) == 1)
+    n_cols = max(args.key_cols, 4 if "r4" in kinds else 1 if kinds & {"r", "rv"} else 0)
     sys.path.insert(0, os.path.abspath(args.pkg))
     from ragmi.index import FlatIndex
     dev = torch.device("cuda", 0)
     idx = FlatIndex(D, args.rows, dev, storage="fp16")
+    if n_cols:
+        idx.keys_create(n_cols)
     g = torch.Generator(device=dev)
     g.manual_seed(1000)
     q = None
@@ -75,6 +90,8 @@ def main():
             q = x[:B] + 0.05 * torch.randn((B, D), generator=g, device=dev)
         tags = (rows % TICKERS + 1) | (((rows // TICKERS) % TYPES + 1) << 16)
         idx.upsert(x, rows, tags.to(torch.int32), new_count=r0 + n)
+        for c in range(n_cols):     # a non-negative double's key is its bits
+            idx.write_keys(c, rows, ((rows // (c + 1)) % 1000).double().view(torch.int64))
     torch.cuda.synchronize()
     pairs = [(0xFFFF, 1 + j) if j < TICKERS else (0xFFFFFFFF, (1 + j - TICKERS) | (1 << 16))
              for j in range(B)]
@@ -82,7 +99,7 @@ def main():
     runs = {}
     if "a" in args.kinds:
         runs["legacy"] = lambda: idx.search(q, K, legacy)
-    if set(args.kinds) & set("bcdv"):
+    if set(args.kinds) & set("bcdv") or kinds & {"r", "r4", "rv"}:
         from ragmi.filters import FilterProgram, pack_view
         bit = lambda s: [1 << s, 1 << s]
         own = torch.from_numpy(np.array([bit(j) for j in range(B)], np.uint32).view(np.int32)).to(dev)
@@ -106,6 +123,24 @@ def main():
         if "v" in args.kinds:
             out = torch.empty((idx.capacity,), dtype=torch.int32, device=dev)
             runs["view_only"] = lambda: idx.filter_view(blob_b, n_programs=B, out=out)
+        if kinds & {"r", "r4", "rv"}:
+            from ragmi.filters import key_of_float
+
+            def ranged(j, cols):  # (b)'s filter j and key in [j, j + 499] on each of `cols`
+                m, v = pairs[j]
+                atoms = [("maskeq", m, v)] + [("range", c, key_of_float(float(j)),
+                                               key_of_float(float(j + 499))) for c in range(cols)]
+                return FilterProgram(tuple(atoms), 1 << ((1 << len(atoms)) - 1))
+
+            blob_r = as_dev(pack_view([ranged(j, 1) for j in range(B)]))
+            if "r" in kinds:
+                runs["range"] = lambda: idx.search(q, K, own, programs=blob_r, n_programs=B)
+            if "r4" in kinds:
+                blob_r4 = as_dev(pack_view([ranged(j, 4) for j in range(B)]))
+                runs["range4"] = lambda: idx.search(q, K, own, programs=blob_r4, n_programs=B)
+            if "rv" in kinds:
+                out_r = torch.empty((idx.capacity,), dtype=torch.int32, device=dev)
+                runs["range_view_only"] = lambda: idx.filter_view(blob_r, n_programs=B, out=out_r)
     for _ in range(args.warmup):
         for fn in runs.values():
             fn()
@@ -116,11 +151,17 @@ def main():
             times[name].append(event_ms(fn))
     rec = {"bench": "filters", "label": args.label, "rows": args.rows, "dim": D, "storage": "fp16",
            "tickers": TICKERS, "types": TYPES, "B": B, "k": K, "warmup": args.warmup,
-           "iters": args.iters}
+           "iters": args.iters, "key_cols": n_cols}
     rec.update({f"{name}_ms_median_min_max": spread(t) for name, t in times.items()})
     if "view" in times and "legacy" in times:
         rec["view_minus_legacy_ms"] = round(float(np.median(times["view"]) -
                                                   np.median(times["legacy"])), 4)
+    if "range_view_only" in times:       # tag + one key column read, the view written
+        rec["range_view_only_GBps"] = round(
+            idx.capacity * 16 / (float(np.median(times["range_view_only"])) * 1e-3) / 1e9, 1)
+    if "view_only" in times:             # tag read, view written
+        rec["view_only_GBps"] = round(
+            idx.capacity * 8 / (float(np.median(times["view_only"])) * 1e-3) / 1e9, 1)
     rec["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(rec)
     print(line)
