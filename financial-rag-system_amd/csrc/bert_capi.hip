@@ -366,7 +366,7 @@ bool pipe_ok(int M, int N, int K) {
 }
 
 // Runtime value -> compile-time constant, handed to a generic lambda that reads it as
-// decltype(tag)::value (with_filter / with_dim in index_capi.hip): a flag as a bool_constant ...
+// decltype(tag)::value (with_filter / with_dim in index_host.hpp): a flag as a bool_constant ...
 template <typename F>
 auto with_flag(bool on, F&& f) {
   if (on) return f(std::true_type{});

@@ -1,4 +1,4 @@
-// certify_kernels.hip — the exactness certificate of a search pass (included by index_capi.hip
+// certify_kernels.hip — the exactness certificate of a search pass (included by index_search.hip
 // after scan_kernels.hip and seed_kernels.hip): the canonical exact score (exact_scores_*),
 // select_kernel (the scan's per-wave lists -> the exact top-k, or a verdict that the lists do
 // not prove it) and rescan_kernel (tier 2: the shard streamed once more for the queries select

@@ -78,7 +78,7 @@ class Knob {
   std::atomic<bool> warned_{false};
 };
 
-// ---- device buffers of the host layers (index_capi.hip, bert_capi.hip) ---------------------
+// ---- device buffers of the host layers (index_*.hip, bert_capi.hip) ----------------------
 // a hipMalloc buffer freed on every return path; release() hands it to a longer-lived owner
 template <typename T>
 struct DeviceBuf {

@@ -1,4 +1,4 @@
-// filter_kernels.hip — the filter algebra's one kernel (included by index_capi.hip after
+// filter_kernels.hip — the filter algebra's one kernel (included by index_store.hip after
 // rows_kernels.hip, whose row access it follows): filter_view_kernel evaluates up to
 // RAG_FILTER_MAX_PROGRAMS filter programs against every row's tag (and, on an index with key
 // columns, its keys: the RANGE atom) and writes a derived tag column, bit s of

@@ -1,5 +1,5 @@
 // largek_kernels.hip — the exact passes for k beyond the scan's 32 per-wave candidates
-// (included by index_capi.hip after seed_kernels.hip and certify_kernels.hip): the radix
+// (included by index_search.hip after seed_kernels.hip and certify_kernels.hip): the radix
 // select, the large-k pass (lk_bound / lk_collect / lk_rescore / lk_final) and the full exact
 // pass for any k (full_score / full_emit).
 namespace ragmi {

@@ -1,5 +1,5 @@
 // merge_kernels.hip — merges of exact per-shard result lists into one (included by
-// index_capi.hip after certify_kernels.hip): where the lists lie (StackedLists, GatheredLists),
+// index_search.hip after certify_kernels.hip): where the lists lie (StackedLists, GatheredLists),
 // the k <= 32 merge (merge_exact_*, merge_gather_kernel), the k <= kLkMerge merge
 // (merge_large_*, merge_gather_large_kernel), the shard set's id remap, and the key / position
 // kernels of the any-k merge (merge_any_*).

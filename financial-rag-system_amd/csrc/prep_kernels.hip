@@ -2,7 +2,7 @@
 // and the kernels that write into it: ingest (upsert_kernel) and query prep (qprep_*); then
 // the int8 scan copy of the rows (dim 384, fp16 storage): its layout, the one quantiser
 // (quantise_row / requant_kernel), the upper bound u_bound and the int8 query prep (qprep8_*).
-// First of the device headers index_capi.hip includes; the scan, seed, certify, merge, large-k,
+// First of the device headers index_search.hip includes; the scan, seed, certify, merge, large-k,
 // re-select and row headers after it all read this layout.
 //
 // Replaces the Qdrant server's COSINE collection behind QdrantClient.query_points / upsert

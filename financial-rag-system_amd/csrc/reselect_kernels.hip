@@ -1,5 +1,5 @@
 // reselect_kernels.hip — re-selection from a query's exact candidate list (included by
-// index_capi.hip after certify_kernels.hip): mmr_kernel picks k diverse hits (rag_index_mmr),
+// index_search.hip after certify_kernels.hip): mmr_kernel picks k diverse hits (rag_index_mmr),
 // group_select_kernel deals the list into groups by payload key (rag_group_select),
 // rrf_fuse_kernel fuses a request's L lists by reciprocal rank (rag_fuse_rrf). All take one
 // workgroup per query and read candidate lists, never the scan's state.

@@ -1,4 +1,4 @@
-// rows_kernels.hip — row-wise access to the flat index (included by index_capi.hip last; it
+// rows_kernels.hip — row-wise access to the flat index (included by index_store.hip last; it
 // needs only the tile16 layout of prep_kernels.hip): the ordered tag select and the indexed row
 // copies behind rag_index_select_rows / move_rows / gather_rows / scatter_rows, the grouped
 // search's tag gather behind rag_index_gather_tags (include/ragmi.h), the export / import

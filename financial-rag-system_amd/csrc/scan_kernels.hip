@@ -1,5 +1,5 @@
 // scan_kernels.hip — the streaming pass of a search: every stored tile MFMA-scored against
-// the pass's queries, each wave keeping its own top-32 per query (included by index_capi.hip
+// the pass's queries, each wave keeping its own top-32 per query (included by index_search.hip
 // after prep_kernels.hip, which defines the tile16 layout).
 //
 // Three top-k structures and the kernel each serves: ScanTopK / scan_kernel (D = 384, query

@@ -1,4 +1,4 @@
-// seed_kernels.hip — the seed sample of a search pass (included by index_capi.hip after
+// seed_kernels.hip — the seed sample of a search pass (included by index_search.hip after
 // scan_kernels.hip): a few thousand tiles spread over the shard are scored with the scan's own
 // arithmetic (sample_kernel, the fused qprep_sample_kernel, sample_wide_kernel) and
 // thresh_kernel turns their per-query maxima into seed_thr, the lower bound of the 32nd-best
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void qprep_sample_kernel(
   sample_epilogue<FILTER>(sc, st, lane, tags, filt_l, n_rows, n_sample, smax);
 }
 
-constexpr int kSampleGroups = 4;   // query groups of 32 per wide pass (index_capi kMaxGroups)
+constexpr int kSampleGroups = 4;   // query groups of 32 per wide pass (index_host.hpp kMaxGroups)
 
 // D = 1024 with several query groups: one pass over each sample tile for ALL groups (the
 // grouped sample_kernel re-read every tile once per group: 4x the bytes at B = 128). Same MFMA

@@ -13,7 +13,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 # translation units of libragmi.so
-SOURCES = ["index_capi.hip", "bert_capi.hip", "wordpiece_capi.cpp"]
+SOURCES = ["index_search.hip", "index_store.hip", "index_shardset.hip", "bert_capi.hip",
+           "wordpiece_capi.cpp"]
 # what they include: every other .hip / .hpp of csrc/ (derived, so that a new header counts
 # for needs_build() without being listed)
 HEADERS = sorted(f for f in os.listdir(CSRC)

@@ -4,7 +4,10 @@
 Both inputs are assembly files of the same source at two commits, device side only:
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-strict-aliasing \\
-          --cuda-device-only -S index_capi.hip -o X.s
+          --cuda-device-only -S index_search.hip -o X.s
+
+A unit that was split (or several units: index_search.hip, index_store.hip,
+index_shardset.hip) is compared as the concatenation of its units' assembly files.
 
 For every kernel symbol the text between its label and its end label is taken, comment, debug
 and unwind lines are dropped and the local label numbers are renumbered in order of appearance,

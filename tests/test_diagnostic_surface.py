@@ -133,7 +133,8 @@ def _inside_diag(src, pos):
 
 def test_diagnostic_instances_are_gated_in_the_sources():
     """Every non-production scan / attention instantiation sits under RAGMI_DIAG_BUILD."""
-    idx = _src("index_capi.hip")
+    from _index_src import index_host_source
+    idx = index_host_source()
     for probe in ("scan_valu_kernel<D><<<", "launch_variant<D, 3>", "launch_variant<D, 9>",
                   "RAG_WIDE(4)"):
         assert _inside_diag(idx, idx.index(probe)), probe

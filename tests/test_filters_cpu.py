@@ -251,8 +251,8 @@ def test_abi_is_declared_and_bound():
         decl = re.search(rf"int {name}\(([^;]*)\);", hdr)
         assert decl, name
         assert len(decl.group(1).split(",")) == len(_lib.INDEX_API[name][1]), name
-    src = open(os.path.join(ROOT, "financial-rag-system_amd", "csrc", "index_capi.hip")).read()
-    assert '#include "filter_kernels.hip"' in src
+    from _index_src import index_host_source
+    assert '#include "filter_kernels.hip"' in index_host_source()
 
 
 # ------------------------------------------------------------------ 2. compile_filter
