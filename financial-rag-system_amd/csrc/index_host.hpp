@@ -195,6 +195,7 @@ struct rag_index {
   char* c8 = nullptr;
   float* meta8 = nullptr;
   int prescan = 1;        // rag_index_set_prescan: 0 off, 1 auto, 2 always
+  int64_t prescan_passes = 0;   // passes that streamed the int8 copy (rag_index_prescan_passes)
   int n_cu = 256;
   int max_wgs = 0;        // scan workgroups at full occupancy
   int scan_wgs = 0;       // D <= 384 scan grid cap: 3/4 of the CUs (scan_grid)

@@ -274,6 +274,7 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   // CU with scan workgroups, landed between a scan's workgroups and stretched the scan launch
   // (10M rows: scan 0.76 vs 0.83 of the roofline, same qps, profiles/r03i_headline_prep_ab.jsonl)
   if (i8) {
+    ++h->prescan_passes;   // rag_index_prescan_passes (the caller holds h->mu)
     // the seed is then a lower bound of the 32nd-best u, which the prescan's thresholds compare
     if constexpr (D == 384) launch_prep8<D>(h, w, a.q, Bq, filt, a.tags, st);
   } else if (D <= 384 && groups == 1 && fused_prep() && h->serial_scans == 0) {
@@ -1201,6 +1202,14 @@ int rag_index_set_prescan(rag_index_t* h, int mode) {
 }
 
 int rag_index_prescan(const rag_index_t* h) { return h ? h->prescan : -1; }
+
+int rag_index_prescan_passes(rag_index_t* h, int64_t* n) {
+  ragmi::clear_error();
+  if (!h || !n) return ragmi::fail(RAG_EINVAL, "bad args");
+  std::lock_guard<std::mutex> lk(h->mu);
+  *n = h->prescan_passes;
+  return RAG_OK;
+}
 
 int rag_index_prescan_bounds(rag_index_t* h, const float* q, int B, const int64_t* rows_dev,
                              int64_t n, float* out_u) {

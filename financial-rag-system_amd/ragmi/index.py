@@ -590,6 +590,14 @@ class FlatIndex(ListOps):
         """The prescan mode set (rag_index_prescan)."""
         return int(self._L.rag_index_prescan(self._h))
 
+    def prescan_passes(self) -> int:
+        """Search passes since creation that streamed the int8 copy
+        (rag_index_prescan_passes): ceil(B / 32) per k <= 32 search the prescan took, nothing
+        for any other. Host state; no synchronisation."""
+        n = ctypes.c_int64()
+        check(self._L.rag_index_prescan_passes(self._h, ctypes.byref(n)))
+        return int(n.value)
+
     def prescan_bounds(self, queries, rows) -> torch.Tensor:
         """[B, n] upper bounds u of the prescan for stored rows `rows` against `queries`
         (B <= 32), from the stored int8 copy (rag_index_prescan_bounds; diagnostic)."""

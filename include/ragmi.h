@@ -548,6 +548,11 @@ enum { RAG_PRESCAN_OFF = 0, RAG_PRESCAN_AUTO = 1, RAG_PRESCAN_ALWAYS = 2 };
 int rag_index_set_prescan(rag_index_t* index, int mode);
 /* The mode set (-1 for NULL). */
 int rag_index_prescan(const rag_index_t* index);
+/* *n = the search passes since creation that streamed the int8 copy (scan_kernel_i8): what
+ * tells a pass of the prescan from one of the fp16 scan, whose results are the same. A search
+ * of B queries with k <= RAG_MAX_K that routes to the prescan adds ceil(B / RAG_QUERY_TILE);
+ * every other pass adds nothing. Host state only, no device work. */
+int rag_index_prescan_passes(rag_index_t* index, int64_t* n);
 /* Diagnostic view of the certificate's premise: out_u_dev[b * n + i] = the prescan's upper
  * bound u of stored row rows_dev[i] against query b (q_dev: B <= 32 queries, as for a search),
  * computed from the stored copy by the device function the prescan itself uses; -inf for a

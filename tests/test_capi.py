@@ -53,6 +53,10 @@ def test_library_loads_and_binds_without_gpu(libpath):
     h = ctypes.c_void_p()
     rc = L.rag_index_create(100, 16, 0, ctypes.byref(h))
     assert rc == -1 and b"dim" in L.rag_last_error()
+    # the prescan pass counter: NULL handle or NULL result refused on the host
+    n = ctypes.c_int64(-5)
+    assert L.rag_index_prescan_passes(None, ctypes.byref(n)) == -1 and n.value == -5
+    assert b"bad args" in L.rag_last_error()
     # partition streams: argument errors before any HIP call
     st = ctypes.c_void_p()
     for part, parts in ((0, 0), (2, 2), (-1, 4)):
