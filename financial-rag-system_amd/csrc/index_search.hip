@@ -12,6 +12,7 @@
 #include "merge_kernels.hip"
 #include "largek_kernels.hip"
 #include "reselect_kernels.hip"
+#include "formula_kernels.hip"
 
 #include <hipcub/hipcub.hpp>
 
@@ -1071,6 +1072,44 @@ int rag_fuse_rrf(const int64_t* cand_r, const int32_t* ncand, int B, int L, int 
   ragmi::rrf_fuse_kernel<<<dim3((unsigned)B), dim3(ragmi::kRrfBlock), 0,
                            static_cast<hipStream_t>(stream)>>>(cand_r, ncand, L, C, k, rrf_k,
                                                                out_s, out_r, out_count);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// ---- formula queries: prefetched candidates re-scored by a program (formula_kernels.hip) ----
+
+int rag_formula_rescore(const float* cand_s, const int64_t* cand_r, const uint32_t* cand_t,
+                        const int64_t* const* cand_keys, const int32_t* ncand,
+                        const uint32_t* prog, int64_t words, int B, int L, int C, int k,
+                        float* out_s, int64_t* out_r, int32_t* out_count, uint32_t* out_status,
+                        void* stream) {
+  ragmi::clear_error();
+  static_assert(ragmi::kFmlBlock == ragmi::kRrfBlock && ragmi::kFmlPer <= 32 &&
+                    ragmi::kFmlMaxOps * ragmi::kFmlOp + ragmi::kFmlHdr +
+                            ragmi::kFmlMaxConds * RAG_FILTER_REC_WORDS < (1 << 20),
+                "formula_rescore_kernel's sort, its head mask and its staged records");
+  if (L < 1 || L > RAG_FUSION_MAX_LISTS)
+    return ragmi::fail(RAG_ERANGE, "formula_rescore: L must be in [1, RAG_FUSION_MAX_LISTS=16]");
+  if (C < 1) return ragmi::fail(RAG_ERANGE, "formula_rescore: C must be >= 1");
+  if ((int64_t)L * C > RAG_FUSION_MAX_ENTRIES)
+    return ragmi::fail(RAG_ERANGE,
+                       "formula_rescore: L * C must be <= RAG_FUSION_MAX_ENTRIES=4096");
+  if (k < 1) return ragmi::fail(RAG_EINVAL, "formula_rescore: k must be >= 1");
+  if (B < 0) return ragmi::fail(RAG_EINVAL, "formula_rescore: B must be >= 0");
+  if (B > 0 && (!cand_s || !cand_r || !prog || !out_s || !out_r || !out_status))
+    return ragmi::fail(RAG_EINVAL,
+                       "formula_rescore: a NULL candidate, program or output pointer");
+  if (B > 0 && words < RAG_FORMULA_HDR_WORDS)
+    return ragmi::fail(RAG_EINVAL, "formula_rescore: words must be >= RAG_FORMULA_HDR_WORDS=2");
+  if (B == 0) return RAG_OK;
+  ragmi::FormulaKeys keys;
+  for (int c = 0; c < RAG_KEYS_MAX_COLS; ++c) keys.col[c] = cand_keys ? cand_keys[c] : nullptr;
+  // a blob the kernel can index with 32 bits: nothing a program names lies past its records
+  const uint32_t w32 = (uint32_t)std::min<int64_t>(words, (int64_t)1 << 30);
+  ragmi::formula_rescore_kernel<<<dim3((unsigned)B), dim3(ragmi::kFmlBlock), 0,
+                                  static_cast<hipStream_t>(stream)>>>(
+      cand_s, cand_r, cand_t, keys, ncand, prog, w32, L, C, k, out_s, out_r, out_count,
+      out_status);
   RAG_HIP(hipGetLastError());
   return RAG_OK;
 }

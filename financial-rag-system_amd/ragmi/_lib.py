@@ -133,6 +133,10 @@ INDEX_API = {
                                         c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rag_fuse_rrf": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rag_formula_rescore": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp,
+                                           ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp]),
     "rag_merge_topk": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       c_vp, c_vp, c_vp]),
     "rag_merge_topk_packed": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

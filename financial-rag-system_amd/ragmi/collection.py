@@ -20,8 +20,9 @@ from .coalesce import Coalescer
 from .filters import (DEFAULT_TAG_FIELDS, MAX_PROGRAMS, FilterProgram, PayloadRanges,
                       PayloadTags, UnsupportedFilter, compile_filter, compile_legacy_only,
                       pack_view)
-from .index import (FUSION_MAX_ENTRIES, GROUPS_MAX, GROUPS_MAX_CELLS, FlatIndex, fuse_rrf,
-                    hits_of, host_or_tensor)
+from .formula import BAD, MISSING, NONFINITE, compile_formula
+from .index import (FUSION_MAX_ENTRIES, GROUPS_MAX, GROUPS_MAX_CELLS, FlatIndex,
+                    formula_rescore, fuse_rrf, hits_of, host_or_tensor)
 from .shardset import ShardSet, parse_devices
 
 
@@ -456,6 +457,94 @@ class Collection:
         under the same hold of the lock (_points)."""
         with self.lock:
             return self._points(self.search_fusion(requests), with_vectors)
+
+    def search_formula(self, requests: list):
+        """Formula queries. `requests`: per request (FormulaQuery, [(vector,
+        Filter or None, limit), ...], limit), as formula_params returns them. Every formula is
+        compiled over this collection's tag and range fields (ragmi.formula) with L = the
+        request's number of prefetches. Every prefetch of every request rides one batched
+        search at C = the largest prefetch limit (clamped to the collection's count), scores
+        kept; the lists are arranged [B, Lmax, C] on the device, each cut to its own limit by
+        ncand; the tags are gathered once when a formula has a condition, each key column once
+        when a formula names it; rag_formula_rescore runs in one launch per distinct compiled
+        formula. A prefetch whose filter can match nothing, or whose limit is < 1, is an empty
+        list and is not searched. A request whose status comes back non-zero (a variable
+        without value or default, a value that is not finite) raises ValueError for the call.
+        Returns per request [(row, value)], best first."""
+        with self.lock:
+            out = [[] for _ in requests]
+            count = self.index.count
+            # compiled first, so that a refusal does not depend on the limits
+            formulas = [compile_formula(q, None, len(pres), self.tags, self.ranges)
+                        for q, pres, _ in requests]
+            compiled = [[self.compile_filter(f) for _, f, _ in pres] for _, pres, _ in requests]
+            qs, filters, where = [], [], []          # the searched prefetches, flattened
+            for b, (_, pres, limit) in enumerate(requests):
+                if limit < 1 or count == 0:
+                    continue
+                for l, (vec, _, plim) in enumerate(pres):
+                    if compiled[b][l] is not None and plim >= 1:
+                        qs.append(vec)
+                        filters.append(compiled[b][l])
+                        where.append((b, l, min(plim, count)))
+            if not qs:
+                return out
+            live = sorted({b for b, _, _ in where})
+            slot = {b: j for j, b in enumerate(live)}
+            Lmax = max(len(requests[b][1]) for b in live)
+            C = max(n for _, _, n in where)
+            if Lmax * C > FUSION_MAX_ENTRIES:
+                raise ValueError(f"formula: {Lmax} prefetches of up to {C} hits are {Lmax * C} "
+                                 f"entries; at most {FUSION_MAX_ENTRIES} (prefetches x the "
+                                 "largest prefetch limit) are re-scored")
+            sc, ids = self._lists(stack_queries(qs, self.dim), filters, list(range(len(qs))), C)
+            dev = ids.device
+            rows = torch.full((len(live), Lmax, C), -1, dtype=torch.int64, device=dev)
+            scores = torch.full((len(live), Lmax, C), float("-inf"), dtype=torch.float32,
+                                device=dev)
+            at = np.asarray([(slot[b], l) for b, l, _ in where], dtype=np.int64)
+            a0, a1 = torch.from_numpy(at[:, 0]).to(dev), torch.from_numpy(at[:, 1]).to(dev)
+            rows[a0, a1] = ids
+            scores[a0, a1] = sc
+            ncand = np.zeros((len(live), Lmax), dtype=np.int32)
+            ncand[at[:, 0], at[:, 1]] = [n for _, _, n in where]
+            lim = [int(requests[b][2]) for b in live]
+            k = min(max(lim), Lmax * C)
+            by_blob: dict = {}
+            for j, b in enumerate(live):
+                by_blob.setdefault(formulas[b].blob().tobytes(), (formulas[b], []))[1].append(j)
+            tags = (self.index.gather_tags(rows)
+                    if any(f.has_cond for f, _ in by_blob.values()) else None)
+            keys = {c: self.index.gather_keys(c, rows)
+                    for c in sorted({c for f, _ in by_blob.values() for c in f.columns})}
+            for f, members in by_blob.values():
+                every = len(members) == len(live)
+                sel = None if every else torch.as_tensor(members, device=dev)
+                pick = lambda t: t if every or t is None else t[sel]
+                s, r, status = formula_rescore(
+                    pick(scores), pick(rows), f.blob(), k, ncand if every else ncand[members],
+                    pick(tags) if f.has_cond else None,
+                    {c: pick(keys[c]) for c in f.columns})
+                status = status.cpu().numpy()
+                if status.any():
+                    bits = int(np.bitwise_or.reduce(status))
+                    raise ValueError("formula: " + "; ".join(
+                        text for bit, text in (
+                            (MISSING, "a variable has no value for a candidate (a payload field "
+                                      "the point lacks, or a $score[i] of a point outside "
+                                      "prefetch i) and no entry in `defaults`"),
+                            (NONFINITE, "a candidate's value is not finite (a division by zero "
+                                        "without by_zero_default, or an overflow)"),
+                            (BAD, "the device refused the compiled program")) if bits & bit))
+                for j, h in zip(members, hits_of(s, r)):
+                    out[live[j]] = h[:lim[j]]
+            return out
+
+    def search_points_formula(self, requests: list, with_vectors=False):
+        """search_formula with every hit resolved to its ScoredPoint (score = the formula's
+        value) under the same hold of the lock (_points)."""
+        with self.lock:
+            return self._points(self.search_formula(requests), with_vectors)
 
     def search_groups(self, queries, group_by: str, limit: int, group_size: int, filters: list,
                       with_vectors=False, candidates: int | None = None,

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .filters import MAX_PROGRAMS, REC_WORDS, view_programs
+from .filters import KEYS_MAX_COLS, MAX_PROGRAMS, REC_WORDS, view_programs
 
 MAX_K = 32          # RAG_MAX_K in include/ragmi.h: the scan's certified top-k path
 MAX_K_LARGE = 4096  # RAG_MAX_K_LARGE: k in (32, 4096] takes the exact large-k pass; larger k
@@ -819,6 +819,82 @@ def fuse_rrf(cand_rows: torch.Tensor, k: int, rrf_k: int = 2, ncand=None,
             out_s.data_ptr(), out_r.data_ptr(),
             count.data_ptr() if count is not None else None, _stream_ptr(dev)))
     return (out_s, out_r, count) if with_count else (out_s, out_r)
+
+
+def formula_rescore(cand_scores: torch.Tensor, cand_rows: torch.Tensor, program, k: int,
+                    ncand=None, cand_tags=None, cand_keys=None, with_count: bool = False):
+    """rag_formula_rescore over candidate lists on one device (fp32 scores and int64 rows
+    [B, L, C], -1 = none): per request the distinct rows of its L lists re-scored by the formula
+    program `program` (ragmi.formula's blob: a uint32 host array, or an int32 tensor on the
+    lists' device) and ordered by (value desc, row asc), the first k of them — include/ragmi.h.
+    `ncand`: None, or int32 values [B, L]. `cand_tags`: the rows' int32 tag bits [B, L, C]
+    (gather_tags), needed when the program has a condition. `cand_keys`: a mapping or sequence
+    of key column -> int64 keys [B, L, C] (gather_keys), None entries = not supplied. Returns
+    (scores fp32 [B, k], rows int64 [B, k], status int32 [B]: bit 0 a missing variable, bit 1 a
+    non-finite value, bit 2 a bad program) with -inf / -1 padding, and the distinct-row counts
+    int32 [B] when `with_count`. Index-free; enqueued on the current stream."""
+    if not isinstance(cand_rows, torch.Tensor) or cand_rows.dim() != 3:
+        raise ValueError("cand_rows must be a [B, L, C] tensor")
+    if not isinstance(cand_scores, torch.Tensor) or cand_scores.shape != cand_rows.shape:
+        raise ValueError("cand_scores and cand_rows must both be [B, L, C] tensors")
+    if cand_rows.dtype != torch.int64 or cand_scores.dtype != torch.float32:
+        raise ValueError("candidates must be fp32 scores and int64 rows")
+    dev = cand_rows.device
+    r = cand_rows.contiguous()
+    s = cand_scores.to(dev).contiguous()
+    B, L, C = r.shape
+    k = int(k)
+    if not 1 <= L <= FUSION_MAX_LISTS:
+        raise ValueError(f"L must be in [1, {FUSION_MAX_LISTS}] lists")
+    if C < 1 or L * C > FUSION_MAX_ENTRIES:
+        raise ValueError(f"C must be >= 1 and L * C <= {FUSION_MAX_ENTRIES} entries")
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if isinstance(program, torch.Tensor):
+        prog = program.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+    else:
+        a = np.ascontiguousarray(np.asarray(program, dtype=np.uint32).reshape(-1))
+        prog = torch.from_numpy(a.view(np.int32)).to(dev)
+    if prog.numel() < 2:
+        raise ValueError("a formula blob holds at least its two header words")
+    n = None
+    if ncand is not None:
+        if isinstance(ncand, torch.Tensor):
+            n = ncand.to(device=dev, dtype=torch.int32).contiguous()
+        else:
+            n = torch.from_numpy(np.ascontiguousarray(np.asarray(ncand, dtype=np.int32))).to(dev)
+        if n.shape != (B, L):
+            raise ValueError("ncand must be [B, L]")
+    t = None
+    if cand_tags is not None:
+        t = cand_tags.to(dev).contiguous()
+        if t.shape != r.shape or t.dtype != torch.int32:
+            raise ValueError("cand_tags must be int32 tag bits [B, L, C]")
+    cols = [None] * KEYS_MAX_COLS
+    for c, x in (cand_keys.items() if hasattr(cand_keys, "items") else
+                 enumerate(cand_keys or ())):
+        if x is None:
+            continue
+        if not 0 <= int(c) < KEYS_MAX_COLS:
+            raise ValueError(f"key columns are 0..{KEYS_MAX_COLS - 1}")
+        x = x.to(dev).contiguous()
+        if x.shape != r.shape or x.dtype != torch.int64:
+            raise ValueError("cand_keys must be int64 keys [B, L, C]")
+        cols[int(c)] = x
+    ptrs = (ctypes.c_void_p * KEYS_MAX_COLS)(*[x.data_ptr() if x is not None and x.numel()
+                                               else None for x in cols])
+    out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out_r = torch.empty((B, k), dtype=torch.int64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev) if with_count else None
+    with torch.cuda.device(dev):      # index-free: the launch goes to the current device
+        check(_lib.load().rag_formula_rescore(
+            s.data_ptr(), r.data_ptr(), t.data_ptr() if t is not None else None, ptrs,
+            n.data_ptr() if n is not None else None, prog.data_ptr(), prog.numel(), B, L, C, k,
+            out_s.data_ptr(), out_r.data_ptr(),
+            count.data_ptr() if count is not None else None, status.data_ptr(),
+            _stream_ptr(dev)))
+    return (out_s, out_r, status, count) if with_count else (out_s, out_r, status)
 
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int):

@@ -8,6 +8,7 @@ Drop-in for the calls the reference makes on `qdrant_client.QdrantClient`:
   query_points(name, query, limit, query_filter) -> .points[i].{id,score,payload}
                                           main.py:232-237, main2.py:163
 plus query_batch_points (one GPU scan for a whole micro-batch; main2.py:281-295 stage 2),
+the prefetch routes of query_points (FusionQuery / RrfQuery, FormulaQuery),
 count (also filtered), retrieve, delete (by ids or by filter) and delete_collection.
 
 `url` is accepted and ignored: the collection lives in this process's GPU memory (the
@@ -125,12 +126,19 @@ def fusion_params(query, prefetch, limit, query_filter=None):
                          "each Prefetch(filter=...)")
     if not _is_int(limit):
         raise ValueError("a fusion query needs an int limit")
+    return int(rrf_k), prefetch_lists(prefetch, "fusion", "to fuse", "fuses")
+
+
+def prefetch_lists(prefetch, what: str, to: str, verb: str) -> list:
+    """[(vector, Filter or None, limit), ...] of the prefetches of a `what` query — a Prefetch or
+    a list of 1 to RAG_FUSION_MAX_LISTS of them, each a plain nearest query with an int limit —
+    or ValueError naming what is wrong or not built."""
     if isinstance(prefetch, models.Prefetch):
         prefetch = [prefetch]
     if prefetch is None or len(prefetch) == 0:
-        raise ValueError("a fusion query needs prefetches to fuse: prefetch=[Prefetch(...), ...]")
+        raise ValueError(f"a {what} query needs prefetches {to}: prefetch=[Prefetch(...), ...]")
     if len(prefetch) > FUSION_MAX_LISTS:
-        raise ValueError(f"a fusion query fuses at most {FUSION_MAX_LISTS} prefetches, "
+        raise ValueError(f"a {what} query {verb} at most {FUSION_MAX_LISTS} prefetches, "
                          f"got {len(prefetch)}")
     out = []
     for n, p in enumerate(prefetch):
@@ -139,7 +147,7 @@ def fusion_params(query, prefetch, limit, query_filter=None):
         if p.prefetch is not None:
             raise ValueError(f"prefetch[{n}]: a nested Prefetch.prefetch is not built")
         vec, mmr = nearest_of(p.query)
-        if vec is None or is_fusion(vec):
+        if vec is None or is_fusion(vec) or isinstance(vec, models.FormulaQuery):
             raise ValueError(f"prefetch[{n}] needs a query: a vector or a NearestQuery")
         if mmr is not None:
             raise ValueError(f"prefetch[{n}]: an MMR query (NearestQuery.mmr) inside a prefetch "
@@ -147,15 +155,33 @@ def fusion_params(query, prefetch, limit, query_filter=None):
         if not _is_int(p.limit):
             raise ValueError(f"prefetch[{n}] needs an int limit")
         out.append((vec, p.filter, int(p.limit)))
-    return int(rrf_k), out
+    return out
 
 
-FUSION, MMR, PLAIN = "fusion", "mmr", "plain"      # the routes of a request
+def formula_params(query, prefetch, limit, query_filter=None) -> list:
+    """[(vector, Filter or None, limit), ...], the prefetches of a formula request — query a
+    FormulaQuery, prefetch a Prefetch or a list of them, under the restrictions fusion places on
+    them — or ValueError: a top-level filter, a limit that is no int, no prefetches. The formula
+    itself is compiled by the collection (Collection.search_formula), which knows the fields."""
+    if not isinstance(query, models.FormulaQuery):
+        raise ValueError("formula_params: query must be a FormulaQuery")
+    if query_filter is not None:
+        raise ValueError("a formula query takes no top-level query_filter: the filter belongs on "
+                         "each Prefetch(filter=...)")
+    if not _is_int(limit):
+        raise ValueError("a formula query needs an int limit")
+    return prefetch_lists(prefetch, "formula", "to re-score", "re-scores")
+
+
+FUSION, FORMULA, MMR, PLAIN = "fusion", "formula", "mmr", "plain"   # the routes of a request
 
 
 def route_of(query, prefetch=None) -> str:
-    """The route of a request, decided once: FUSION (prefetched lists fused), MMR (a
-    NearestQuery with an Mmr) or PLAIN."""
+    """The route of a request, decided once: FORMULA (prefetched candidates re-scored by a
+    FormulaQuery), FUSION (prefetched lists fused; every other use of a prefetch goes there to
+    be refused), MMR (a NearestQuery with an Mmr) or PLAIN."""
+    if isinstance(query, models.FormulaQuery):
+        return FORMULA
     if prefetch is not None or isinstance(query, (models.FusionQuery, models.RrfQuery)):
         return FUSION
     return MMR if isinstance(query, models.NearestQuery) and query.mmr is not None else PLAIN
@@ -169,6 +195,10 @@ def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=Fals
         par = [fusion_params(r.query, r.prefetch, r.limit, r.filter) for r in reqs]
         return col.search_points_fusion(
             [(rrf_k, pres, int(r.limit)) for (rrf_k, pres), r in zip(par, reqs)], with_vectors)
+    if route == FORMULA:
+        return col.search_points_formula(
+            [(r.query, formula_params(r.query, r.prefetch, r.limit, r.filter), int(r.limit))
+             for r in reqs], with_vectors)
     qs, filters, limits, div, cand = [], [], [], [], []
     for r in reqs:
         q, mmr = nearest_of(r.query)
@@ -355,8 +385,8 @@ class QdrantClient:
                      query_filter: models.Filter | None = None, with_payload=True,
                      with_vectors=False, prefetch=None, **kwargs) -> models.QueryResponse:
         """One request on its route (route_of, answer). A plain request with a limit the scan
-        serves rides the coalescer; fusion and MMR requests never do: their prefetches, their
-        candidate search, are passes of their own."""
+        serves rides the coalescer; fusion, formula and MMR requests never do: their prefetches,
+        their candidate search, are passes of their own."""
         col = self._col(collection_name)
         route = route_of(query, prefetch)
         if route == PLAIN and self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
@@ -373,18 +403,19 @@ class QdrantClient:
                            **kwargs) -> list[models.QueryResponse]:
         """One GPU scan for the whole batch (per-query filters ride along in the kernel). The
         requests are partitioned by route once, each non-empty route is answered by one call
-        (answer), fusion first, and the results are scattered back in request order. With MMR
-        requests in the batch the plain requests ride with them, at diversity 0 with their own
+        (answer), fusion and formula first, and the results are scattered back in request order.
+        With MMR requests in the batch the plain requests ride with them, at diversity 0 with their own
         limit as candidate count: one search at the batch's largest candidate count and one
         MMR launch — unless a plain limit exceeds RAG_MMR_MAX_CANDIDATES, in which case the
         plain requests are searched on their own."""
         col = self._col(collection_name)
-        routes: dict = {FUSION: [], PLAIN: [], MMR: []}
+        routes: dict = {FUSION: [], FORMULA: [], PLAIN: [], MMR: []}
         for i, r in enumerate(requests):
             routes[route_of(r.query, getattr(r, "prefetch", None))].append(i)
         if routes[MMR] and all(int(requests[i].limit) <= MMR_MAX_CANDIDATES
                                for i in routes[PLAIN]):
-            routes = {FUSION: routes[FUSION], MMR: sorted(routes[MMR] + routes[PLAIN])}
+            routes = {FUSION: routes[FUSION], FORMULA: routes[FORMULA],
+                      MMR: sorted(routes[MMR] + routes[PLAIN])}
         out: list = [None] * len(requests)
         for route, members in routes.items():
             if members:
@@ -409,7 +440,8 @@ class QdrantClient:
             raise ValueError("query_points_groups needs group_by, a payload field")
         if kwargs.get("with_lookup") is not None:
             raise NotImplementedError("with_lookup (a join on another collection) is not supported")
-        if is_fusion(query) or kwargs.get("prefetch") is not None:
+        if is_fusion(query) or isinstance(query, models.FormulaQuery) or \
+                kwargs.get("prefetch") is not None:
             raise ValueError("a grouped query over prefetched candidates (prefetch, FusionQuery, "
                              "RrfQuery) is not built")
         query, mmr = nearest_of(query)

@@ -261,7 +261,7 @@ class RrfQuery:
 
 @dataclass
 class Prefetch:
-    """One candidate list of a fusion query: the `limit` nearest points to `query` (a vector,
+    """One candidate list of a fusion or formula query: the `limit` nearest points to `query` (a vector,
     or a NearestQuery without mmr) under `filter`. A nested `prefetch` is refused."""
     query: Any = None
     filter: Optional[Filter] = None
@@ -269,10 +269,137 @@ class Prefetch:
     prefetch: Any = None
 
 
+# ---- formula queries (score boosting): the expression tree of FormulaQuery.formula. An
+# expression is one of these, a number (a constant), a str (a variable: "$score", "$score[i]"
+# or the name of a number range field), or a condition (FieldCondition, IsEmptyCondition,
+# Filter: 1.0 when the candidate passes, else 0.0). ragmi.formula compiles it.
+@dataclass
+class SumExpression:
+    sum: list
+
+
+@dataclass
+class MultExpression:
+    mult: list
+
+
+@dataclass
+class NegExpression:
+    neg: Any
+
+
+@dataclass
+class AbsExpression:
+    abs: Any
+
+
+@dataclass
+class DivisionParams:
+    """left / right; `by_zero_default`: the value when right == 0.0 (None: the request fails)."""
+    left: Any
+    right: Any
+    by_zero_default: Optional[float] = None
+
+
+@dataclass
+class DivExpression:
+    div: DivisionParams
+
+
+@dataclass
+class DatetimeExpression:
+    """A constant point in time (an RFC 3339 string or a datetime / date object), as seconds
+    since the epoch."""
+    datetime: Any
+
+
+@dataclass
+class DatetimeKeyExpression:
+    """The value of a datetime range field, as seconds since the epoch."""
+    datetime_key: str
+
+
+@dataclass
+class DecayParamsExpression:
+    """Decay of |x - target|: `scale` is the distance at which the decay reaches `midpoint`.
+    None fields take the defaults: target 0.0, scale 1.0, midpoint 0.5."""
+    x: Any
+    target: Any = None
+    scale: Optional[float] = None
+    midpoint: Optional[float] = None
+
+
+@dataclass
+class LinDecayExpression:
+    lin_decay: DecayParamsExpression
+
+
+@dataclass
+class ExpDecayExpression:
+    exp_decay: DecayParamsExpression
+
+
+@dataclass
+class GaussDecayExpression:
+    gauss_decay: DecayParamsExpression
+
+
+@dataclass
+class SqrtExpression:
+    """Not built (refused by ragmi.formula, like the five below)."""
+    sqrt: Any
+
+
+@dataclass
+class PowParams:
+    base: Any
+    exponent: Any
+
+
+@dataclass
+class PowExpression:
+    pow: PowParams
+
+
+@dataclass
+class ExpExpression:
+    exp: Any
+
+
+@dataclass
+class Log10Expression:
+    log10: Any
+
+
+@dataclass
+class LnExpression:
+    ln: Any
+
+
+@dataclass
+class GeoDistanceParams:
+    origin: Any
+    to: str
+
+
+@dataclass
+class GeoDistance:
+    geo_distance: GeoDistanceParams
+
+
+@dataclass
+class FormulaQuery:
+    """query_points(prefetch=[Prefetch(...), ...], query=FormulaQuery(formula=<expression>,
+    defaults={...})): the prefetched candidates re-scored by the formula. `defaults`: the value
+    of a variable a candidate lacks, keyed by field name or "$score[i]"."""
+    formula: Any
+    defaults: dict = field(default_factory=dict)
+
+
 @dataclass
 class QueryRequest:
     """Batched query entry for query_batch_points (one per request of a micro-batch); `query`
-    is a vector or a NearestQuery, or with `prefetch` a FusionQuery / RrfQuery."""
+    is a vector or a NearestQuery, or with `prefetch` a FusionQuery / RrfQuery / FormulaQuery."""
     query: Any
     filter: Optional[Filter] = None
     limit: int = 10

@@ -157,9 +157,37 @@ def _fusion(vector, rewrites, flt, limit, rrf_k, diversity, candidates):
                    for v in [vector, *rewrites]]
 
 
+RECENCY_PREFETCH = 50        # a recency boost re-scores max(limit, this) hits
+RECENCY_FIELD = "ingested_at"
+RECENCY_DEFAULT = "1970-01-01T00:00:00Z"      # a chunk without a timestamp is as old as can be
+
+
+def _recency(vector, recency, recency_now, flt, limit, diversity, candidates, rewrites):
+    """(query, prefetch) of a recency-boosted retrieval, recency = (half_life_days, weight):
+    $score + weight * exp_decay(datetime_key "ingested_at", target = now, scale = half_life_days
+    * 86400 s, midpoint 0.5) over one prefetch of max(limit, 50) hits under the request's
+    filter; a chunk without a timestamp counts as from the epoch. recency_now None: the current
+    UTC time."""
+    if diversity is not None or candidates is not None or rewrites is not None:
+        raise ValueError("recency (a formula query) cannot be combined with rewrites (fusion) "
+                         "or diversity / candidates (MMR)")
+    half_life_days, weight = recency
+    now = datetime.now(timezone.utc) if recency_now is None else recency_now
+    decay = models.ExpDecayExpression(exp_decay=models.DecayParamsExpression(
+        x=models.DatetimeKeyExpression(datetime_key=RECENCY_FIELD),
+        target=models.DatetimeExpression(datetime=now),
+        scale=float(half_life_days) * 86400.0, midpoint=0.5))
+    query = models.FormulaQuery(
+        formula=models.SumExpression(sum=[
+            "$score", models.MultExpression(mult=[float(weight), decay])]),
+        defaults={RECENCY_FIELD: RECENCY_DEFAULT})
+    return query, [models.Prefetch(query=vector, filter=flt, limit=max(limit, RECENCY_PREFETCH))]
+
+
 def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEVE_LIMIT, *,
                          diversity=None, candidates=None, rewrites=None, rrf_k=None,
-                         ingested_since=None, ingested_until=None):
+                         ingested_since=None, ingested_until=None, recency=None,
+                         recency_now=None):
     """ingested_since / ingested_until (keyword-only, not in the reference): only chunks whose
     `ingested_at` timestamp lies in [since, until) — RFC 3339 strings or datetime / date objects,
     either may be None; a DatetimeRange on `ingested_at` joins the `must` list. The collection
@@ -172,9 +200,24 @@ def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEV
     rewrites (keyword-only): extra query vectors for the same question; the lists of the
     original and of each rewrite, max(limit, 50) hits under the same filter, are fused by
     reciprocal rank (constant rrf_k, None = 2) and cut to `limit`. None is today's call; with
-    diversity / candidates it is a ValueError."""
+    diversity / candidates it is a ValueError.
+    recency (keyword-only) = (half_life_days, weight): newer chunks are boosted; the max(limit,
+    50) nearest under the same filter are re-scored as $score + weight * 0.5 ** (age /
+    half_life_days), age measured from `recency_now` (a datetime or RFC 3339 string; None = the
+    current UTC time) to the chunk's `ingested_at`, and cut to `limit`. The collection needs
+    `ingested_at` declared a datetime range field, as for ingested_since. None is today's call;
+    with rewrites or diversity / candidates it is a ValueError."""
     if _testing():
         return type("obj", (object,), {"points": []})
+    if recency is not None:
+        query, prefetch = _recency(query_vector, recency, recency_now,
+                                   _filter(ticker, document_type, ingested_since, ingested_until),
+                                   limit, diversity, candidates, rewrites)
+        try:
+            return get_qdrant().query_points(collection_name=COLLECTION_NAME, query=query,
+                                             prefetch=prefetch, limit=limit)
+        except Exception:
+            return type("obj", (object,), {"points": []})
     if rewrites is not None:
         query, prefetch = _fusion(query_vector, rewrites,
                                   _filter(ticker, document_type, ingested_since, ingested_until),
@@ -198,14 +241,25 @@ def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEV
 
 
 def retrieve_batch(query_vectors, tickers, document_types=None, limit=RETRIEVE_LIMIT, *,
-                   diversity=None, candidates=None, rewrites=None, rrf_k=None):
+                   diversity=None, candidates=None, rewrites=None, rrf_k=None, recency=None,
+                   recency_now=None):
     """One GPU scan for a whole micro-batch (main2.py:281-295 + 228), per-request filters;
     diversity / candidates as in retrieve_from_qdrant, for every request of the batch.
     rewrites: per request a list of extra query vectors (as in retrieve_from_qdrant); every
-    prefetch of the batch rides one scan and one fusion launch."""
+    prefetch of the batch rides one scan and one fusion launch.
+    recency / recency_now: as in retrieve_from_qdrant, for every request of the batch (one
+    `now` for all of them); one scan, one gather and one formula launch."""
     if _testing():
         return [type("obj", (object,), {"points": []}) for _ in tickers]
     document_types = document_types or [None] * len(tickers)
+    if recency is not None:
+        now = datetime.now(timezone.utc) if recency_now is None else recency_now
+        reqs = []
+        for v, t, d in zip(query_vectors, tickers, document_types):
+            query, prefetch = _recency(v, recency, now, _filter(t, d), limit, diversity,
+                                       candidates, rewrites)
+            reqs.append(models.QueryRequest(query=query, prefetch=prefetch, limit=limit))
+        return get_qdrant().query_batch_points(COLLECTION_NAME, reqs)
     if rewrites is not None:
         reqs = []
         for v, t, d, rw in zip(query_vectors, tickers, document_types, rewrites):

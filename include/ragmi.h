@@ -323,6 +323,100 @@ int rag_fuse_rrf(const int64_t* cand_rows_dev, const int32_t* ncand_dev, int B, 
                  int k, int rrf_k, float* out_scores_dev, int64_t* out_rows_dev,
                  int32_t* out_count_dev, void* stream);
 
+/* Formula queries (Qdrant's query_points(prefetch = [Prefetch(...), ...], query =
+ * FormulaQuery(formula, defaults))): the candidates of a request's L exact lists re-scored by an
+ * arithmetic formula over their scores, their payload keys and filter conditions. Index-free like
+ * rag_fuse_rrf: it reads only its input arrays, runs on the calling thread's current device and
+ * is asynchronous on `stream`. The arithmetic is this project's definition, modelled on Qdrant's
+ * published formula expressions (sum, mult, div, neg, abs, lin / exp / gauss decay, conditions as
+ * 1.0 / 0.0); the reference never re-scores, and parity with a Qdrant server's own arithmetic is
+ * unpinned.
+ *
+ * Candidates. Lists and their ends are rag_fuse_rrf's: for request b and list l the entries are
+ * the first n_{b,l} positions, n_{b,l} = min(ncand_dev[b][l] clamped to [0, C], the number of
+ * leading entries with row >= 0). The candidates are the distinct rows of the live entries; rows
+ * are opaque int64 ids. A row that occurs several times within one list contributes its first
+ * occurrence; its tag and keys are read at the slot e = l * C + p of its first entry in (list,
+ * position) order.
+ *
+ * Formula programs. A formula is a postfix program of at most RAG_FORMULA_MAX_OPS ops over an
+ * evaluation stack of fp64 values, at most RAG_FORMULA_MAX_STACK deep, the same for every
+ * candidate of the launch. The device blob (uint32 words, `words` of them):
+ *   word 0    n, the op count;   word 1    U, the number of condition programs (<=
+ *             RAG_FORMULA_MAX_CONDS)
+ *   words [2 + 6 i, 8 + 6 i), i < n: op i = (kind, arg, flags, 0, imm low, imm high), imm one fp64
+ *   words [2 + 6 n, words): when U > 0, a "Filter programs" blob of U programs (their INSET /
+ *             RANGE offsets count from this blob's own first word)
+ * Op kinds (x, y popped: y the top of the stack; every arithmetic step one IEEE fp64 operation,
+ * never contracted into an fma):
+ *   RAG_FORMULA_CONST   push imm
+ *   RAG_FORMULA_SCORE   push (double)score of the candidate's entry in list arg; a candidate
+ *                       absent from that list: imm when flags & 1, else status bit 0 and 0.0
+ *   RAG_FORMULA_KEY     the key k of column arg (cand_keys[arg][b][e]): push the double whose
+ *                       key it is ("Key columns"), divided by 1e6 when flags & 2 (a datetime
+ *                       column: microseconds to seconds); k == RAG_KEY_ABSENT: imm when
+ *                       flags & 1, else status bit 0 and 0.0
+ *   RAG_FORMULA_COND    push 1.0 when (tag, keys) of the candidate passes condition program arg,
+ *                       else 0.0; a RANGE atom on a column that was not supplied is false
+ *   RAG_FORMULA_ADD     push x + y        RAG_FORMULA_MUL   push x * y
+ *   RAG_FORMULA_NEG     push -y           RAG_FORMULA_ABS   push |y|
+ *   RAG_FORMULA_DIV     push x / y; when y == 0.0: imm when flags & 1, else status bit 1
+ *   RAG_FORMULA_LIN     d = |x - y|; t = 1.0 - imm * d; push t when t > 0.0, else 0.0
+ *   RAG_FORMULA_EXP     d = |x - y|; push E(imm * d)
+ *   RAG_FORMULA_GAUSS   d = |x - y|; push E(imm * (d * d))
+ * (for the decays x is the variable, y the target and imm the coefficient lambda the host derives
+ * from scale and midpoint). E, the decay exponential, for a <= 0: 0.0 when a < -700; otherwise
+ * n = rint(a * 1.4426950408889634), r = (a - n * 6.93147180369123816490e-01) - n *
+ * 1.90821492927058770002e-10, p = the degree-13 Taylor polynomial of e^r by Horner (coefficients
+ * 1 / i! as correctly rounded doubles; each step one multiply, then one add), E = p * 2^n
+ * (exact). E(a) is NaN for a > 0 or a NaN. Relative error against a correctly rounded exp over
+ * [-700, 0]: at most 2.0 * 2^-53 (measured, 6M arguments).
+ *
+ * Value and result. After the last op the one value left is rounded once to fp32, -0.0 taken as
+ * +0.0. The distinct rows ordered by (value descending, row ascending); the first k go to
+ * out_scores_dev fp32 [B][k] and out_rows_dev int64 [B][k], -inf / -1 past the last distinct row;
+ * out_count_dev int32 [B] (may be NULL) is the number of distinct rows. out_status_dev uint32 [B]:
+ * bit 0 a variable without a value and without a default, bit 1 a division by zero without a
+ * default or a final fp32 value that is not finite, bit 2 a bad program. For a request whose
+ * status is non-zero the other outputs are written but unspecified. Every output element is
+ * written by the launch; no floating-point atomics, so the result is a pure function of the
+ * inputs, and the first k' outputs of a run at k are the run at k'.
+ *
+ * The blob is never trusted. It is bad (bit 2 for every request, no op evaluated) when words < 2,
+ * n > RAG_FORMULA_MAX_OPS, U > RAG_FORMULA_MAX_CONDS, the op records or the U program records end
+ * past `words`, a kind is unknown, the stack would drop below its operands or rise above
+ * RAG_FORMULA_MAX_STACK, it does not end at depth 1, a SCORE names a list >= L, a KEY names a
+ * column >= RAG_KEYS_MAX_COLS or one whose pointer is NULL, a COND names a program >= U or
+ * cand_tags_dev is NULL. A condition program reads the blob as filter_view_kernel does: a word
+ * only when its index is < words. So a malformed blob never reads or writes outside the blob,
+ * the inputs and the outputs.
+ *
+ * cand_keys: a HOST array of RAG_KEYS_MAX_COLS device pointers (int64 [B][L][C] each, the keys
+ * of the candidates' rows: rag_index_gather_keys), NULL = column not supplied; the array itself
+ * may be NULL (no column). cand_tags_dev: uint32 [B][L][C] (rag_index_gather_tags) or NULL.
+ * Limits and refusals are rag_fuse_rrf's, on the host before any HIP call: 1 <= L <=
+ * RAG_FUSION_MAX_LISTS, C >= 1, L * C <= RAG_FUSION_MAX_ENTRIES (RAG_ERANGE); k >= 1, B >= 0,
+ * words >= 2, non-NULL cand_scores_dev / cand_rows_dev / prog_dev / out_scores_dev /
+ * out_rows_dev / out_status_dev (RAG_EINVAL); B = 0 launches nothing. */
+#define RAG_FORMULA_MAX_OPS 64
+#define RAG_FORMULA_MAX_STACK 8
+#define RAG_FORMULA_MAX_CONDS 8
+#define RAG_FORMULA_HDR_WORDS 2
+#define RAG_FORMULA_OP_WORDS 6
+enum {
+  RAG_FORMULA_CONST = 0, RAG_FORMULA_SCORE = 1, RAG_FORMULA_KEY = 2, RAG_FORMULA_COND = 3,
+  RAG_FORMULA_ADD = 4, RAG_FORMULA_MUL = 5, RAG_FORMULA_NEG = 6, RAG_FORMULA_ABS = 7,
+  RAG_FORMULA_DIV = 8, RAG_FORMULA_LIN = 9, RAG_FORMULA_EXP = 10, RAG_FORMULA_GAUSS = 11,
+};
+#define RAG_FORMULA_MISSING 1u     /* status bit 0 */
+#define RAG_FORMULA_NONFINITE 2u   /* status bit 1 */
+#define RAG_FORMULA_BAD 4u         /* status bit 2 */
+int rag_formula_rescore(const float* cand_scores_dev, const int64_t* cand_rows_dev,
+                        const uint32_t* cand_tags_dev, const int64_t* const* cand_keys,
+                        const int32_t* ncand_dev, const uint32_t* prog_dev, int64_t words, int B,
+                        int L, int C, int k, float* out_scores_dev, int64_t* out_rows_dev,
+                        int32_t* out_count_dev, uint32_t* out_status_dev, void* stream);
+
 /* Merge n_lists per-shard result lists (each [B][k] sorted by (score desc, id asc), device;
  * laid out [n_lists][B][k]; padding: id -1) into the global top-k [B][k] (device) by (score
  * desc, id asc), padding -inf / -1 past the valid entries. Any k >= 1 (k > RAG_MAX_K_LARGE:
