@@ -7,6 +7,9 @@ namespace ragmi {
 
 constexpr int kCandCap = 256;   // select: compacted heads at/above the lane-max threshold
 constexpr int kBandLists = 32;  // select tier 1: lists gathered per chunk (8 per wave)
+// ... after the 6-bit prescan (select_kernel<D, FILTER, kBandLists6>): its band is ~200 rows in
+// as many lists per query, seven chunks of 32; 128 per chunk make that two gather round trips
+constexpr int kBandLists6 = 128;
 
 // Wave 0 merges the four waves' top-32 lists (best first, one row of ws / wi per wave) out of
 // LDS: lanes 0..31 end with the best 32 of the 128 entries, best first. `none` pads list 0 in
@@ -145,13 +148,13 @@ struct ExactStats {
 //       the rescan kernel launched after every select (its workgroups split the shard); here
 //       select only records L and e_k. Only inputs with more than 32 in-band rows inside one
 //       wave's share of the tiles (or a seed above L) get there. After an int8 prescan
-//       (scan_kernel_i8) the list scores are upper bounds u >= e: a row outside A has
+//       (scan_kernel_i8, scan_kernel_i6) the list scores are upper bounds u >= e: a row outside A has
 //       e <= u <= a_32, the same check with a := u and eps the prescan's slack; a true top-k
 //       row has u >= e >= e_k >= L, so tier 1 reads the same lists. (Round 2 ran this pass
 //       inside select, on the query's one workgroup: a single-CU pass over the whole shard,
 //       ~0.1 s at 10M rows — unbounded by the chip's bandwidth; VERDICT/ADVICE r2.)
 // ----------------------------------------------------------------------------------------
-template <int D, bool FILTER>
+template <int D, bool FILTER, int BL = kBandLists>
 __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ part_s,
                                                      const int* __restrict__ part_i,
                                                      const float* __restrict__ heads_s,
@@ -186,7 +189,7 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
   __shared__ int e_i[32];
   __shared__ int qlist[kMaxLists];   // tier 1: lists whose head is >= L
   __shared__ int n_q;
-  __shared__ int band[kBandLists * kKS];   // tier 1: a chunk's rows with a >= L outside A
+  __shared__ int band[BL * kKS];   // tier 1: a chunk's rows with a >= L outside A
   __shared__ int n_band;
   __shared__ float n_s[2][32];       // tier 1: a round's exact scores / rows (two rounds in
   __shared__ int n_i[2][32];         // flight: one barrier per round)
@@ -460,10 +463,10 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
   const int nql = seeded ? n_q : 0;
   const int a_row = e_i[lane & 31];   // A's rows, one per lane: their exact scores are known
   int rnd = 0;
-  for (int c0 = 0; c0 < nql; c0 += kBandLists) {
+  for (int c0 = 0; c0 < nql; c0 += BL) {
     // gather: a half-wave per list, a lane per entry; wave w takes the chunk's lists w, w + 4,
     // ... Every load is issued before the first use (clamped, selects afterwards: step 1).
-    constexpr int kG = kBandLists / 8;
+    constexpr int kG = BL / 8;
     const int pos = lane & (kKS - 1);
     float gs[kG];
     int gi[kG], gn[kG];
@@ -518,7 +521,7 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
         bitonic_sort64(rs, ri, lane);
       }
     }
-    if (c0 + kBandLists < nql) {   // the band buffer is reused by the next chunk
+    if (c0 + BL < nql) {   // the band buffer is reused by the next chunk
       __syncthreads();
       if (tid == 0) n_band = 0;
       __syncthreads();

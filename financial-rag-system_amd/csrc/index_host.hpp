@@ -194,8 +194,14 @@ struct rag_index {
   // pairs); rebuilt from the stored fp16 rows after every write of `corpus` (requant)
   char* c8 = nullptr;
   float* meta8 = nullptr;
-  int prescan = 1;        // rag_index_set_prescan: 0 off, 1 auto, 2 always
-  int64_t prescan_passes = 0;   // passes that streamed the int8 copy (rag_index_prescan_passes)
+  // 6-bit scan copy (prep_kernels.hip "pair6"), kept only where it is used: capacity at least
+  // RAG_PRESCAN6_MIN_ROWS, or mode RAG_PRESCAN_ALWAYS6 set (ensure_copy6). Whole pairs of
+  // tiles over cap_rows / 16 + 1 tiles, and its own (scale, error) meta; rebuilt with the int8 one
+  char* c6 = nullptr;
+  float* meta6 = nullptr;
+  int prescan = 1;        // rag_index_set_prescan: 0 off, 1 auto, 2 always (int8), 3 always 6-bit
+  int64_t prescan_passes = 0;   // passes that streamed a prescan copy (rag_index_prescan_passes)
+  int64_t prescan6_passes = 0;  // those over the 6-bit copy (rag_index_prescan6_passes)
   int n_cu = 256;
   int max_wgs = 0;        // scan workgroups at full occupancy
   int scan_wgs = 0;       // D <= 384 scan grid cap: 3/4 of the CUs (scan_grid)
@@ -262,6 +268,9 @@ int view_args(const uint32_t* progs, int64_t words, int n_programs);
 int acquire_view(rag_index* h, hipStream_t st, uint32_t** view);
 int launch_filter_view(rag_index* h, const uint32_t* progs, int64_t words, int n_programs,
                        uint32_t* view, hipStream_t st);
+// index_store.hip: the 6-bit scan copy of an index that can keep one (dim 384, fp16 storage) and
+// has none yet, allocated and built from the stored rows; synchronous (lock held)
+int ensure_copy6(rag_index* h);
 #pragma GCC visibility pop
 
 }  // namespace ragmi

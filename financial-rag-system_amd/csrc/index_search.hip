@@ -194,21 +194,33 @@ bool use_prescan(const rag_index* h, int k) {
   return h->c8 && RAG_PRESCAN_ROUTES(h->prescan, h->dim, h->storage, k, h->count);
 }
 
-// Query prep and seeds of an int8 prescan pass: qprep's outputs plus the int8 planes
-// (qprep8_kernel), then launch_seed's sample of the shard scored with the prescan's own upper
-// bound u (sample_kernel_i8) and thresh_kernel on it
+// ... and does it scan the 6-bit copy instead? Only where the index keeps one (capacity from
+// RAG_PRESCAN6_MIN_ROWS, or mode RAG_PRESCAN_ALWAYS6 set). Auto: from RAG_PRESCAN6_MIN_ROWS
+// rows
+bool use_prescan6(const rag_index* h, int k) {
+  return h->c6 && RAG_PRESCAN6_ROUTES(h->prescan, h->dim, h->storage, k, h->count);
+}
+
+// Query prep and seeds of a prescan pass (`six`: over the 6-bit copy): qprep's outputs plus the
+// int8 planes (qprep8_kernel), then launch_seed's sample of the shard scored with the prescan's
+// own upper bound u (sample_kernel_i8 / sample_kernel_i6) and thresh_kernel on it
 template <int D>
 void launch_prep8(rag_index* h, Workspace& w, const float* q, int Bq, const uint32_t* filt,
-                  const uint32_t* tags, hipStream_t st) {
+                  const uint32_t* tags, hipStream_t st, bool six = false) {
   qprep8_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(q, Bq, filt, w.qn, w.qfrag, w.filt, w.eps,
                                                   w.qfrag8, w.qp8, w.eps8);
   const int nt = (int)((h->count + 15) / 16);
   if (nt == 0) return;   // the scan visits no tile; seeds are never read
   const int n_sample = seed_sample(nt, kMaxSample);
   with_filter(filt, [&](auto f) {
-    sample_kernel_i8<D, decltype(f)::value><<<dim3((n_sample + 7) / 8), dim3(256), 0, st>>>(
-        h->c8, h->meta8, tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
-        (int)h->count, nt, n_sample, w.smax);
+    if (six)
+      sample_kernel_i6<D, decltype(f)::value><<<dim3((n_sample + 7) / 8), dim3(256), 0, st>>>(
+          h->c6, h->meta6, tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
+          (int)h->count, nt, n_sample, w.smax);
+    else
+      sample_kernel_i8<D, decltype(f)::value><<<dim3((n_sample + 7) / 8), dim3(256), 0, st>>>(
+          h->c8, h->meta8, tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
+          (int)h->count, nt, n_sample, w.smax);
   });
   thresh_kernel<kMaxSample><<<dim3(kQ, 1), dim3(256), 0, st>>>(w.smax, n_sample, w.eps8, w.seed);
 }
@@ -228,7 +240,7 @@ int max_wgs_on(const rag_index* h, int cus) { return partitioned(h, cus) ? 2 * c
 // list work is paid by 768 waves instead of 2048 (select merges that many fewer lists), and
 // the free CUs take the other streams' query prep, sampling and select beside the scan
 // instead of behind it. RAGMI_SCAN_WGS overrides the cap (diagnostic A/B).
-int scan_grid(const rag_index* h, int cus, bool filtered, bool i8) {
+int scan_grid(const rag_index* h, int cus, bool filtered, bool i8, bool i6 = false) {
   static ragmi::Knob k_wgs("RAGMI_SCAN_WGS");
   const int wg_env = k_wgs.get(0) > 0 ? std::max(8, k_wgs.get(0)) : 0;
   const bool part = partitioned(h, cus);
@@ -243,7 +255,14 @@ int scan_grid(const rag_index* h, int cus, bool filtered, bool i8) {
   // 222.7-223.3K vs 207.0-207.6K, profiles/r05d_partition_lines.jsonl)
   // the int8 prescan holds both query planes in VGPRs (one workgroup per CU at most), so its
   // filtered passes take the unfiltered grid
-  const int wg_cap = wg_env ? wg_env : (filtered && !i8) ? max_wgs : part ? cus : h->scan_wgs;
+  // the 6-bit prescan is bound by instruction issue where the int8 one is bound by HBM (its
+  // top-k and bound arithmetic no longer hide under the loads): one workgroup on EVERY CU,
+  // 10M rows 59.2K qps at 192 workgroups, 62.4K at 224, 63.6K at 256
+  const int wg_cap = wg_env ? wg_env
+                     : (filtered && !i8) ? max_wgs
+                     : part ? cus
+                     : i6 ? h->n_cu
+                          : h->scan_wgs;
   const int64_t n_tiles = (h->count + 15) / 16;
   const int grid = (int)std::min<int64_t>(std::min(max_wgs, wg_cap),
                                           std::max<int64_t>(1, (n_tiles + 3) / 4));
@@ -267,8 +286,11 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   const int Bq = a.Bq;
   // Bq <= 32 * h->groups queries: `groups` query groups of 32 (one for D <= 384)
   const int groups = (Bq + kQ - 1) / kQ;
-  bool i8 = false;
-  if constexpr (D == 384) i8 = use_prescan(h, a.k);
+  bool i8 = false, i6 = false;   // i8: a prescan copy is streamed; i6: the 6-bit one
+  if constexpr (D == 384) {
+    i8 = use_prescan(h, a.k);
+    i6 = i8 && use_prescan6(h, a.k);
+  }
   // fused qprep + sample only in free scan order (small shards, several scans overlapping):
   // there it is +1.1% (1.25M rows, 4 in flight, profiles/r03d_fused_prep_ab.jsonl); with the
   // scans chained (>= 4M rows) its 256-thread workgroups of ~180 registers, which cannot share a
@@ -276,8 +298,9 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   // (10M rows: scan 0.76 vs 0.83 of the roofline, same qps, profiles/r03i_headline_prep_ab.jsonl)
   if (i8) {
     ++h->prescan_passes;   // rag_index_prescan_passes (the caller holds h->mu)
+    if (i6) ++h->prescan6_passes;
     // the seed is then a lower bound of the 32nd-best u, which the prescan's thresholds compare
-    if constexpr (D == 384) launch_prep8<D>(h, w, a.q, Bq, filt, a.tags, st);
+    if constexpr (D == 384) launch_prep8<D>(h, w, a.q, Bq, filt, a.tags, st, i6);
   } else if (D <= 384 && groups == 1 && fused_prep() && h->serial_scans == 0) {
     with_filter(filt, [&](auto f) {
       launch_prep_seed<D, decltype(f)::value>(h, w, a.q, Bq, filt, a.tags, st);
@@ -302,7 +325,7 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
         per_group, ((n_tiles + kLdsWaves - 1) / kLdsWaves + 7) & ~int64_t(7));
     grid = std::max(8, std::min(need, kMaxLists / kLdsWaves));
   } else {
-    grid = scan_grid(h, w.cus, filt != nullptr, i8);
+    grid = scan_grid(h, w.cus, filt != nullptr, i8, i6);
   }
   const hipStream_t caller = st;
   if (h->serial_scans == 1) {
@@ -377,6 +400,11 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
     const int rc = with_filter(filt, [&](auto f) -> int {
       constexpr bool F = decltype(f)::value;
       if constexpr (D == 384) {
+        if (i6)
+          return RAG_SCAN_GO(scan_kernel_i6<D, F>)(
+              h->c6, h->meta6, a.tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
+              (int)h->count, (int)n_tiles, w.seed, w.part_s, w.part_i, w.heads_s,
+              w.heads_i, w.heads_n);
         if (i8)
           return RAG_SCAN_GO(scan_kernel_i8<D, F>)(
               h->c8, h->meta8, a.tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
@@ -404,11 +432,15 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   const ExactStats fb{w.fb_tier, w.fb_cnt, w.t2};
   // select certifies every query's top-k; its fallbacks (list re-scoring, a workgroup-local
   // second pass over the shard) run inside the same launch
+  // (after the 6-bit prescan with the wider gather chunk: its band spans ~200 lists a query)
   with_filter(filt, [&](auto f) {
-    select_kernel<D, decltype(f)::value><<<dim3(Bq), dim3(256), 0, st>>>(
-        w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, a.tags, w.filt,
-        w.qfrag, (int)h->count, w.qn, a.k, i8 ? w.eps8 : w.eps, w.seed, fb, a.id_offset, a.out_s,
-        a.out_i, a.out_packed, h->rows32, i8 ? w.eps : nullptr);
+    with_flag(i6, [&](auto six) {
+      constexpr int BL = (D == 384 && decltype(six)::value) ? kBandLists6 : kBandLists;
+      select_kernel<D, decltype(f)::value, BL><<<dim3(Bq), dim3(256), 0, st>>>(
+          w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, a.tags, w.filt,
+          w.qfrag, (int)h->count, w.qn, a.k, i8 ? w.eps8 : w.eps, w.seed, fb, a.id_offset,
+          a.out_s, a.out_i, a.out_packed, h->rows32, i8 ? w.eps : nullptr);
+    });
   });
   // tier 2 of the certificate (rescan_kernel): returns at once unless select marked a query
   // of the pass; otherwise its R workgroups stream the shard once per 16 marked queries.
@@ -732,6 +764,33 @@ int bench_scan(rag_index* h, const float* q, int B, int variant, int reps, doubl
     rows64_kernel<D><<<grid1d(h->count * (D / 8), 256), dim3(256), 0, nullptr>>>(
         h->corpus, h->count, rows64.p);
     qchunk_kernel<D><<<dim3(kQ), dim3(64), 0, nullptr>>>(w.qn, qc.p);
+  }
+  // variants 20 / 21 / 22 / 23 / 24: the 6-bit prescan (scan_kernel_i6) at its production grid
+  // — production, MFMA + bound only (no top-k), loads only, loads + unpack, production with
+  // every seed at +inf (the top-k's fixed cost: no candidate is ever taken)
+  if (variant >= 20) {
+    if constexpr (D == 384) {
+      if (!h->c6) return ragmi::fail(RAG_EINVAL, "variants 20-24: index keeps no 6-bit copy");
+      launch_prep8<D>(h, w, q, std::min(B, kQ), nullptr, h->tags, nullptr, true);
+      if (variant == 24)
+        RAG_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(w.seed), 0x7f800000, kQ));
+      const int grid = scan_grid(h, 0, false, true, true);
+      const auto go = [&](auto mode) {
+        launch_fixed<kScanBlock>(scan_kernel_i6<D, false, decltype(mode)::value>, dim3(grid), 0,
+                                 nullptr, h->c6, h->meta6, h->tags, w.filt,
+                                 reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
+                                 (int)h->count, (int)n_tiles, w.seed, w.part_s, w.part_i,
+                                 w.heads_s, w.heads_i, w.heads_n);
+      };
+      return time_launches(reps, [&]() {
+        if (variant == 20 || variant == 24) go(std::integral_constant<int, 0>{});
+        else if (variant == 21) go(std::integral_constant<int, 1>{});
+        else if (variant == 22) go(std::integral_constant<int, 2>{});
+        else go(std::integral_constant<int, 3>{});
+      }, avg_ms);
+    } else {
+      return ragmi::fail(RAG_EINVAL, "variants 20-24: dim 384 only");
+    }
   }
   // variants 17 / 18 / 19: the int8 prescan (scan_kernel_i8) at the production grid —
   // production, MFMA + bound only (no top-k), loads only
@@ -1170,7 +1229,7 @@ int rag_bench_scan(rag_index_t* h, const float* queries_dev, int B, int variant,
     return ragmi::fail(RAG_EINVAL, "variant: 0 (production) or 7 (dim 384: seeds at +inf); the "
                                    "scan's timing probes are in the diagnostic build only");
 #endif
-  if (!h || !queries_dev || B < 1 || reps < 1 || !avg_ms || variant < 0 || variant > 19)
+  if (!h || !queries_dev || B < 1 || reps < 1 || !avg_ms || variant < 0 || variant > 24)
     return ragmi::fail(RAG_EINVAL, "bad bench args");
   std::lock_guard<std::mutex> lk(h->mu);
   RAG_HIP(hipSetDevice(h->device));
@@ -1233,9 +1292,14 @@ int rag_index_set_scan_order(rag_index_t* h, int serial) {
 int rag_index_set_prescan(rag_index_t* h, int mode) {
   ragmi::clear_error();
   if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
-  if (mode < RAG_PRESCAN_OFF || mode > RAG_PRESCAN_ALWAYS)
-    return ragmi::fail(RAG_EINVAL, "prescan mode must be 0 (off), 1 (auto) or 2 (always)");
+  if (mode < RAG_PRESCAN_OFF || mode > RAG_PRESCAN_ALWAYS6)
+    return ragmi::fail(RAG_EINVAL,
+                       "prescan mode must be 0 (off), 1 (auto), 2 (always) or 3 (always 6-bit)");
   std::lock_guard<std::mutex> lk(h->mu);
+  if (mode == RAG_PRESCAN_ALWAYS6) {   // an index below the threshold builds its 6-bit copy now
+    const int rc = ragmi::ensure_copy6(h);
+    if (rc) return rc;
+  }
   h->prescan = mode;
   return RAG_OK;
 }
@@ -1247,6 +1311,14 @@ int rag_index_prescan_passes(rag_index_t* h, int64_t* n) {
   if (!h || !n) return ragmi::fail(RAG_EINVAL, "bad args");
   std::lock_guard<std::mutex> lk(h->mu);
   *n = h->prescan_passes;
+  return RAG_OK;
+}
+
+int rag_index_prescan6_passes(rag_index_t* h, int64_t* n) {
+  ragmi::clear_error();
+  if (!h || !n) return ragmi::fail(RAG_EINVAL, "bad args");
+  std::lock_guard<std::mutex> lk(h->mu);
+  *n = h->prescan6_passes;
   return RAG_OK;
 }
 
@@ -1266,9 +1338,15 @@ int rag_index_prescan_bounds(rag_index_t* h, const float* q, int B, const int64_
   Workspace& w = h->ws[0];
   qprep8_kernel<384><<<dim3(kQ), dim3(64), 0, nullptr>>>(q, B, nullptr, w.qn, w.qfrag, w.filt,
                                                          w.eps, w.qfrag8, w.qp8, w.eps8);
-  prescan_bounds_kernel<384><<<dim3((unsigned)n), dim3(64), 0, nullptr>>>(
-      h->c8, h->meta8, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, rows_dev, n, h->count, B,
-      out_u);
+  // the bound of the copy a k = 1 pass streams in the current mode (the int8 one where none)
+  if (use_prescan6(h, 1))
+    prescan6_bounds_kernel<384><<<dim3((unsigned)n), dim3(64), 0, nullptr>>>(
+        h->c6, h->meta6, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, rows_dev, n,
+        h->count, B, out_u);
+  else
+    prescan_bounds_kernel<384><<<dim3((unsigned)n), dim3(64), 0, nullptr>>>(
+        h->c8, h->meta8, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, rows_dev, n, h->count,
+        B, out_u);
   RAG_HIP(hipGetLastError());
   RAG_HIP(hipDeviceSynchronize());
   return RAG_OK;

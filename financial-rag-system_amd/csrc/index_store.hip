@@ -29,13 +29,40 @@ int alloc_copy8(const rag_index* h, int64_t cap_rows, DeviceBuf<char>& c8, Devic
   return RAG_OK;
 }
 
-// The int8 copy of rows[i] (device list) or row0 + i, i < n, rebuilt from the stored fp16 rows:
-// enqueued on `st` right after the kernel that wrote them
+// the 6-bit copy: whole pairs of tiles over the int8 copy's cap_rows / 16 + 1 tiles
+size_t copy6_bytes(int64_t cap_rows) {
+  return (size_t)((cap_rows / 16 + 2) / 2) * ragmi::kPair6Bytes;
+}
+
+int alloc_copy6(int64_t cap_rows, DeviceBuf<char>& c6, DeviceBuf<float>& m6) {
+  if (c6.alloc(copy6_bytes(cap_rows)) != hipSuccess ||
+      m6.alloc(meta8_bytes(cap_rows)) != hipSuccess)
+    return ragmi::fail(RAG_ENOMEM, "hipMalloc(6-bit scan copy) failed");
+  RAG_HIP(hipMemset(c6.p, 0, copy6_bytes(cap_rows)));
+  RAG_HIP(hipMemset(m6.p, 0, meta8_bytes(cap_rows)));
+  return RAG_OK;
+}
+
+// The scan copies of rows[i] (device list) or row0 + i, i < n, rebuilt from the stored fp16
+// rows: enqueued on `st` right after the kernel that wrote them
 int requant(rag_index* h, const int64_t* rows, int64_t row0, int64_t n, hipStream_t st) {
   if (!h->c8 || n <= 0) return RAG_OK;
   ragmi::requant_kernel<384><<<dim3((unsigned)n), dim3(64), 0, st>>>(
       h->corpus, rows, row0, n, h->cap_rows, h->c8, h->meta8);
+  if (h->c6)
+    ragmi::requant6_kernel<384><<<dim3((unsigned)n), dim3(64), 0, st>>>(
+        h->corpus, rows, row0, n, h->cap_rows, h->c6, h->meta6);
   RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// the whole 6-bit copy from the stored rows (a copy that starts late: reserve, ensure_copy6)
+int requant6_all(rag_index* h) {
+  if (h->count > 0)
+    ragmi::requant6_kernel<384><<<dim3((unsigned)h->count), dim3(64), 0, nullptr>>>(
+        h->corpus, nullptr, 0, h->count, h->cap_rows, h->c6, h->meta6);
+  RAG_HIP(hipGetLastError());
+  RAG_HIP(hipDeviceSynchronize());
   return RAG_OK;
 }
 
@@ -340,6 +367,19 @@ int ragmi::acquire_view(rag_index* h, hipStream_t st, uint32_t** view) {
   return RAG_OK;
 }
 
+int ragmi::ensure_copy6(rag_index* h) {
+  if (h->c6 || !keeps_copy8(h)) return RAG_OK;
+  RAG_HIP(hipSetDevice(h->device));
+  DeviceBuf<char> c6;
+  DeviceBuf<float> m6;
+  const int rc = alloc_copy6(h->cap_rows, c6, m6);
+  if (rc) return rc;
+  RAG_HIP(hipDeviceSynchronize());   // no writer of the rows in flight
+  h->c6 = c6.release();
+  h->meta6 = m6.release();
+  return requant6_all(h);
+}
+
 extern "C" {
 
 const char* rag_last_error(void) { return ragmi::last_error().c_str(); }
@@ -382,6 +422,17 @@ int rag_index_create_ex(int dim, int64_t capacity_rows, int device, int storage,
     }
     h->c8 = c8.release();
     h->meta8 = m8.release();
+    if (h->cap_rows >= RAG_PRESCAN6_MIN_ROWS) {
+      DeviceBuf<char> c6;
+      DeviceBuf<float> m6;
+      rc = alloc_copy6(h->cap_rows, c6, m6);
+      if (rc) {
+        rag_index_destroy(h);
+        return rc;
+      }
+      h->c6 = c6.release();
+      h->meta6 = m6.release();
+    }
   }
   if (storage == RAG_STORE_FP32) {
     const size_t b32 = (size_t)h->cap_rows * dim * 4;
@@ -443,6 +494,8 @@ int rag_index_destroy(rag_index_t* h) {
   if (h->rows32) (void)hipFree(h->rows32);
   if (h->c8) (void)hipFree(h->c8);
   if (h->meta8) (void)hipFree(h->meta8);
+  if (h->c6) (void)hipFree(h->c6);
+  if (h->meta6) (void)hipFree(h->meta6);
   if (h->stage) (void)hipFree(h->stage);
   for (auto& v : h->views)
     if (v.p) (void)hipFree(v.p);
@@ -476,6 +529,14 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
     rc = alloc_copy8(h, cap, n8, nm8);
     if (rc) return rc;
   }
+  // the 6-bit copy grows with the rest, and starts here when the capacity reaches its threshold
+  DeviceBuf<char> n6;
+  DeviceBuf<float> nm6;
+  const bool start6 = !h->c6 && keeps_copy8(h) && cap >= RAG_PRESCAN6_MIN_ROWS;
+  if (h->c6 || start6) {
+    rc = alloc_copy6(cap, n6, nm6);
+    if (rc) return rc;
+  }
   RAG_HIP(hipDeviceSynchronize());
   // the key columns regrow with the tags: old rows keep their keys, new rows hold ABSENT
   DeviceBuf<int64_t> nk[RAG_KEYS_MAX_COLS];
@@ -498,6 +559,19 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
     h->c8 = n8.release();
     h->meta8 = nm8.release();
   }
+  if (h->c6) {
+    // whole pairs of the old capacity; an odd last tile's pair is copied with its spare half
+    RAG_HIP(hipMemcpy(n6.p, h->c6, (size_t)((h->cap_rows / 16 + 1) / 2) * ragmi::kPair6Bytes,
+                      hipMemcpyDeviceToDevice));
+    RAG_HIP(hipMemcpy(nm6.p, h->meta6, (size_t)(h->cap_rows / 16) * 32 * 4,
+                      hipMemcpyDeviceToDevice));
+    (void)hipFree(h->c6);
+    (void)hipFree(h->meta6);
+  }
+  if (n6.p) {
+    h->c6 = n6.release();
+    h->meta6 = nm6.release();
+  }
   (void)hipFree(h->corpus);
   (void)hipFree(h->tags);
   if (h->rows32) (void)hipFree(h->rows32);
@@ -509,6 +583,7 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
     h->keys[c] = nk[c].release();
   }
   h->cap_rows = cap;
+  if (start6) return requant6_all(h);   // built from the rows just moved
   return RAG_OK;
 }
 

@@ -232,6 +232,105 @@ __global__ __launch_bounds__(64) void requant_kernel(const half8* __restrict__ c
 }
 
 // ----------------------------------------------------------------------------------------
+// 6-bit scan copy (D = 384, fp16 storage, the largest shards). A third image of
+// the corpus: per row and dimension one integer v in [-31, 31] (six bits, two's complement),
+// with the row's own scale s_r = max|c| / 31 and measured error E_r = ||c - s_r v||_2. The scan
+// reads each value as the int8 4 v (its six bits are the byte's top six: no sign extension, no
+// bias), so `meta6` (meta_slot, as the int8 copy's) holds s_r / 4, exact, and E_r.
+// Layout "pair6": the unit is a PAIR of tiles (32 rows, 9216 B, nine 1-KiB wave loads). Lane
+// l = h*16 + r of the wave owns row r and k-group h of both tiles: 36 dwords, dword g of lane l
+// at byte
+//     pair * 9216 + (g / 4) * 1024 + l * 16 + (g % 4) * 4,
+// g = 18 u + 3 s + c for tile u of the pair, k-step s and part c < 3. The three dwords of
+// (u, s) hold the lane's sixteen values of dims 64 s + 16 h .. + 15 — the k-map of the int8
+// copy, so the int8 query fragments serve unchanged —: byte b of part c carries in its top six
+// bits v of dim 4 c + b, and in its low two bits the bits 2c, 2c + 1 of v of dim 12 + b.
+// unpack6 rebuilds the four A-fragment dwords (bytes 4 v) in nine bitwise ops.
+// ----------------------------------------------------------------------------------------
+constexpr int kPair6Bytes = 9216;
+constexpr int kQ6Max = 31;     // |v| <= 31
+
+// dword index, within the lane's 36, of part c of k-step s of tile u of a pair
+__host__ __device__ constexpr int pair6_dword(int u, int s, int c) { return 18 * u + 3 * s + c; }
+
+// byte offset of dword g of fragment lane l of pair `pair`
+__device__ __forceinline__ int64_t pair6_byte(int64_t pair, int g, int l) {
+  return pair * kPair6Bytes + (g >> 2) * 1024 + l * 16 + (g & 3) * 4;
+}
+
+// the int8 A-fragment (sixteen values 4 v, one per byte) of three packed dwords
+__device__ __forceinline__ intx4 unpack6(uint32_t p0, uint32_t p1, uint32_t p2) {
+  const uint32_t x = ((p0 << 2) & 0x0c0c0c0cu) | ((p1 << 4) & 0x30303030u) |
+                     ((p2 << 6) & 0xc0c0c0c0u);
+  return intx4{(int)(p0 & 0xfcfcfcfcu), (int)(p1 & 0xfcfcfcfcu), (int)(p2 & 0xfcfcfcfcu), (int)x};
+}
+
+// The one 6-bit quantiser of a stored row, by one wave, as quantise_row: lane c < D/8 passes
+// piece c. Scale s = max|x| / 31, v = rint(x / s) in [-31, 31]; returns the eight values as
+// six-bit two's complement fields, one per byte; err = ||x - s v||_2 measured in fp64 and
+// rounded up. The zero row gives scale 0, v = 0, error 0.
+__device__ __forceinline__ uint2 quantise_row6(const float (&x)[8], float& s, float& err) {
+  float m = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[j]));
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+  s = m / (float)kQ6Max;
+  uint32_t w[2] = {0u, 0u};
+  double e2 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float v = s > 0.f ? rintf(x[j] / s) : 0.f;
+    v = fminf(fmaxf(v, -(float)kQ6Max), (float)kQ6Max);
+    const double dd = (double)x[j] - (double)s * (double)v;
+    e2 = fma(dd, dd, e2);
+    w[j >> 2] |= ((uint32_t)(int)v & 0x3fu) << (8 * (j & 3));
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) e2 += __shfl_xor(e2, d, 64);
+  err = e2 > 0.0 ? (float)(sqrt(e2) * (1.0 + 0x1p-20)) : 0.f;
+  return uint2{w[0], w[1]};
+}
+
+// requant_kernel's twin for the 6-bit copy: rows[i] or row0 + i, one wave per row
+template <int D>
+__global__ __launch_bounds__(64) void requant6_kernel(const half8* __restrict__ corpus,
+                                                      const int64_t* __restrict__ rows,
+                                                      int64_t row0, int64_t n, int64_t cap_rows,
+                                                      char* __restrict__ c6,
+                                                      float* __restrict__ meta) {
+  static_assert(D / 8 <= 64, "one piece per lane");
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  const int lane = threadIdx.x;
+  const int64_t row = rows ? rows[i] : row0 + i;
+  if (row < 0 || row >= cap_rows) return;   // never read or write out of bounds
+  float x[8];
+  const bool has = lane < D / 8;
+  half8 h = {};
+  if (has) h = corpus[tile_slot<D>(row, lane)];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = has ? (float)h[j] : 0.f;
+  float s, err;
+  const uint2 b = quantise_row6(x, s, err);
+  // pieces 2m, 2m + 1 are the sixteen dims of one (k-step, k-group): the even lane packs both
+  const uint32_t o0 = __shfl_xor(b.x, 1, 64), o1 = __shfl_xor(b.y, 1, 64);
+  if (has && (lane & 1) == 0) {
+    const int ks = lane >> 3, kg = (lane >> 1) & 3;
+    const int l = kg * 16 + (int)(row & 15), u = (int)(row >> 4) & 1;
+    const uint32_t p[3] = {(b.x << 2) | (o1 & 0x03030303u), (b.y << 2) | ((o1 >> 2) & 0x03030303u),
+                           (o0 << 2) | ((o1 >> 4) & 0x03030303u)};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *reinterpret_cast<uint32_t*>(c6 + pair6_byte(row >> 5, pair6_dword(u, ks, c), l)) = p[c];
+  }
+  if (lane == 0) {
+    meta[meta_slot(row)] = 0.25f * s;   // the scale of the bytes 4 v
+    meta[meta_slot(row) + 16] = err;
+  }
+}
+
+// ----------------------------------------------------------------------------------------
 // int8 query prep, one wave per query slot, after qprep_slot: the normalised query y as two
 // int8 planes, y ~ qh = sq * (254 hi + lo) with s1 = max|y| / 127, hi = rint(y / s1),
 // sq = s1 / 254 and lo = rint((y - s1 hi) / sq) (|y - s1 hi| <= s1 / 2, so |lo| <= 127).
@@ -256,6 +355,17 @@ __global__ __launch_bounds__(64) void requant_kernel(const half8* __restrict__ c
 // (||c|| + E_r)(||y|| + F) < 1.1 in magnitude, so the four roundings stay below 4 * 1.1 * 2^-24
 // < 2^-21.7, and e's own fp32 rounding below 2^-24 * 1.01. The slack 2^-20 in C covers both
 // (A and C themselves are rounded up from fp64).
+//
+// The 6-bit copy (c8 := v in [-31, 31], s_r = max|c| / 31, its own measured E_r) goes through
+// the same inequality. Its scan multiplies the bytes 4 v and reads the scale s_r / 4: both
+// factors of 4 are exact, so u is the u of (v, s_r) bit for bit. I6 = sum 4 v (254 hi + lo) is
+// exact in int32 (|I6| <= 4 D 31 (254 127 + 127) = 1.55e9 < 2^31); both plane dots are at most
+// 4 D 31 127 = 6.05e6 < 2^23, so u_bound6 forms 254 hi + lo with one 24-bit integer
+// multiply-add and converts once: the same single rounding of the same exact integer as
+// u_bound's fma of two exact conversions. E_r <= (s_r / 2) sqrt(D) = 0.317 max|c| <= 0.317
+// ||c||, so every term is at most (||c|| + E_r)(||y|| + F) < 1.33 * 1.01 in magnitude: four
+// roundings stay below 4 * 1.35 * 2^-24 < 2^-21.5, and with e's own 2^-24 * 1.01 below
+// 2^-21.2. The slack 2^-20 covers it unchanged.
 // ----------------------------------------------------------------------------------------
 constexpr float kU8Slack = 0x1p-20f;
 
@@ -263,6 +373,13 @@ __device__ __forceinline__ float u_bound(int hi, int lo, float s_r, float e_r, f
                                          float C) {
   // fma_scalar: same values as fmaf, never paired into packed fp32 ops beside the MFMAs
   const float If = fma_scalar((float)hi, 254.0f, (float)lo);
+  return fma_scalar(If, s_r * sq, fma_scalar(e_r, A, C));
+}
+
+// the 6-bit scan's form (hi, lo: the plane dots of the bytes 4 v; s_r: the stored s_r / 4)
+__device__ __forceinline__ float u_bound6(int hi, int lo, float s_r, float e_r, float sq, float A,
+                                          float C) {
+  const float If = (float)(__mul24(hi, 254) + lo);
   return fma_scalar(If, s_r * sq, fma_scalar(e_r, A, C));
 }
 

@@ -744,6 +744,276 @@ __global__ __launch_bounds__(64) void prescan_bounds_kernel(
   }
 }
 
+// ----------------------------------------------------------------------------------------
+// 6-bit prescan (D = 384, fp16 storage, the largest shards): the scan over the 6-bit copy
+// (prep_kernels.hip "6-bit scan copy"), 0.755 of the int8 scan's bytes. Same bound, same query
+// planes, same lists; the A-fragments (bytes 4 v) are unpacked from the packed dwords
+// (unpack6) and the stored scale is s_r / 4.
+// ----------------------------------------------------------------------------------------
+// The integer dots I of one 6-bit tile (w: the lane's eighteen packed dwords of it,
+// pair6_dword(u, s, c) - 18 u) against both planes of the 32 queries, in the accumulator
+// layout of tile_mfma
+struct Dots6 {
+  intx4 h0, l0, h1, l1;
+};
+
+template <int D>
+__device__ __forceinline__ void tile_dots6(const uint32_t (&w)[3 * steps8<D>()],
+                                           const Query8<D>& q, Dots6& d) {
+  d.h0 = d.l0 = d.h1 = d.l1 = intx4{0, 0, 0, 0};
+#pragma unroll
+  for (int s = 0; s < steps8<D>(); ++s) {
+    const intx4 a = unpack6(w[3 * s], w[3 * s + 1], w[3 * s + 2]);
+    d.h0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, q.h0[s], d.h0, 0, 0, 0);
+    d.h1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, q.h1[s], d.h1, 0, 0, 0);
+    d.l0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, q.l0[s], d.l0, 0, 0, 0);
+    d.l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, q.l1[s], d.l1, 0, 0, 0);
+  }
+}
+
+// ... and their upper bounds u (sc / er: scales and errors of the lane's four C/D rows), as
+// tile_u8's second half. The one place the 6-bit u is evaluated: the scan, the seed sample and
+// rag_index_prescan_bounds all come here.
+template <int D>
+__device__ __forceinline__ void dots6_u(const Dots6& d, const Query8<D>& q, const float4& sc,
+                                        const float4& er, floatx4& u0, floatx4& u1) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float s_r = r == 0 ? sc.x : r == 1 ? sc.y : r == 2 ? sc.z : sc.w;
+    const float e_r = r == 0 ? er.x : r == 1 ? er.y : r == 2 ? er.z : er.w;
+    u0[r] = u_bound6(d.h0[r], d.l0[r], s_r, e_r, q.sq0, q.A0, q.C0);
+    u1[r] = u_bound6(d.h1[r], d.l1[r], s_r, e_r, q.sq1, q.A1, q.C1);
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void tile_u6(const uint32_t (&w)[3 * steps8<D>()], const Query8<D>& q,
+                                        const float4& sc, const float4& er, floatx4& u0,
+                                        floatx4& u1) {
+  Dots6 d;
+  tile_dots6<D>(w, q, d);
+  dots6_u<D>(d, q, sc, er, u0, u1);
+}
+
+// the lane's 36 dwords of pair `pair` by plain loads (seed sample, diagnostic bounds)
+__device__ __forceinline__ void pair6_load(uint32_t (&w)[36], const char* __restrict__ c6,
+                                           int64_t pair, int lane) {
+  const intx4* pp = reinterpret_cast<const intx4*>(c6 + pair * kPair6Bytes) + lane;
+#pragma unroll
+  for (int L = 0; L < 9; ++L) {
+    const intx4 x = __builtin_nontemporal_load(pp + L * 64);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[4 * L + j] = (uint32_t)x[j];
+  }
+}
+
+// tile t of the copy against the 32 queries, by one wave (pair6_load, then tile_u6 on its half)
+template <int D>
+__device__ __forceinline__ void tile_u6_at(const char* __restrict__ c6,
+                                           const float* __restrict__ meta, int64_t t,
+                                           const Query8<D>& q, int lane, floatx4& u0,
+                                           floatx4& u1) {
+  static_assert(D == 384, "pair6 layout");
+  uint32_t w[36], wt[18];
+  pair6_load(w, c6, t >> 1, lane);
+#pragma unroll
+  for (int g = 0; g < 18; ++g) wt[g] = (t & 1) ? w[18 + g] : w[g];
+  const float4 sc = *reinterpret_cast<const float4*>(meta + t * 32 + 4 * (lane >> 4));
+  const float4 er = *reinterpret_cast<const float4*>(meta + t * 32 + 16 + 4 * (lane >> 4));
+  tile_u6<D>(wt, q, sc, er, u0, u1);
+}
+
+// As scan_kernel_i8: strided pairs of tiles, one buffer descriptor per pair, the pair's meta
+// and tags in the same load batch. A pair is 9 KiB (nine loads) + 256 B of meta; THREE batches
+// are in flight per wave (27.8 KiB against the int8 scan's 24.5), the registers the narrower
+// unit frees. c6 / meta hold whole pairs; the tag descriptor is clipped at n_tiles * 16 rows
+// and the rows of a spare tile fail topk_tile_tg's bound check.
+// The bound and the top-k check of a tile run ONE TILE LATE, in the basic block that issues the
+// next tile's MFMAs: with one wave per SIMD nothing else hides them, and checked right behind
+// its own MFMA chain a tile's ~90 bound / compare instructions and the ballot's branch ran
+// with the matrix pipe idle (production 0.57 ms against 0.445 for MFMA + bound).
+// MODE: 0 production, 1 MFMA + bound only (no top-k), 2 loads only, 3 loads + unpack.
+template <int D, bool FILTER, int MODE = 0>
+__global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
+    const char* __restrict__ c6, const float* __restrict__ meta,
+    const uint32_t* __restrict__ tags, const uint32_t* __restrict__ filt,
+    const intx4* __restrict__ qfrag8, const float* __restrict__ qp8, int n_rows, int n_tiles,
+    const float* __restrict__ seed_thr, float* __restrict__ part_s, int* __restrict__ part_i,
+    float* __restrict__ heads_s, int* __restrict__ heads_i, int* __restrict__ heads_n) {
+  static_assert(D == 384, "pair6 layout");
+  __shared__ int lds[kWavesPerWG * kLdsPerWave];
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  ScanTopK st;
+  topk_init<FILTER>(st, lds, wid, lane, seed_thr, filt);
+
+  const int gw = blockIdx.x * kWavesPerWG + __builtin_amdgcn_readfirstlane(wid);
+  const int nw = gridDim.x * kWavesPerWG;
+  const int n_pairs = (n_tiles + 1) / 2;
+  int p_first, p_step, n_mine;
+  tile_sequence<true>(gw, nw, n_pairs, p_first, p_step, n_mine);
+
+  Query8<D> q;
+  query8_load<D>(q, qfrag8, qp8, lane);
+  // The lo planes live in accumulation registers, which the MFMAs read as they read vector
+  // registers: three batches in flight and both planes do not fit the 256 vector registers, and
+  // left to itself the allocator parks fragments there and copies each back before its use
+  // (27 copies per tile)
+#pragma unroll
+  for (int s = 0; s < steps8<D>(); ++s) {
+    asm volatile("" : "+a"(q.l0[s]));
+    asm volatile("" : "+a"(q.l1[s]));
+  }
+
+  struct Batch {
+    intx4 x[9];
+    float4 sc[2], er[2];
+    uint4 tg[2];
+  };
+  const int voff = lane * 16, goff = (lane >> 4) * 16;
+  auto load = [&](Batch& b, int j) __attribute__((always_inline)) {
+    const int p = __builtin_amdgcn_readfirstlane(p_first + j * p_step);
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(c6 + (int64_t)p * kPair6Bytes, kPair6Bytes);
+#pragma unroll
+    for (int L = 0; L < 9; ++L)
+      b.x[L] = __builtin_bit_cast(intx4,
+                                  __builtin_amdgcn_raw_buffer_load_b128(rs, voff, L * 1024, 2));
+    const __amdgpu_buffer_rsrc_t rm = tile_rsrc(meta + (int64_t)p * 64, 256);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      b.sc[u] = __builtin_bit_cast(float4,
+                                   __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128, 0));
+      b.er[u] = __builtin_bit_cast(
+          float4, __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128 + 64, 0));
+    }
+    if constexpr (FILTER) {
+      const int left = min(2, n_tiles - 2 * p);   // tiles of this pair the tag column holds
+      const __amdgpu_buffer_rsrc_t rt =
+          tile_rsrc(tags + (int64_t)p * (2 * kTileRows), left * kTileRows * 4);
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        b.tg[u] = __builtin_bit_cast(
+            uint4, __builtin_amdgcn_raw_buffer_load_b128(rt, goff, u * (kTileRows * 4), 0));
+    } else {
+      b.tg[0] = b.tg[1] = uint4{0u, 0u, 0u, 0u};
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  float vmax = kNegInf;   // MODE 1/2/3: keeps the work alive
+  // the tile whose dots await their bound and check. Before the first: the spare tile n_tiles
+  // with zero scales, whose rows all fail topk_tile_tg's bound check
+  // (two sets of dots, one per tile of a pair, written in turn: no copy between them)
+  struct Held {
+    float4 sc, er;
+    uint4 tg;
+    int t;
+  } held;
+  Dots6 dots[2];
+  dots[1].h0 = dots[1].l0 = dots[1].h1 = dots[1].l1 = intx4{0, 0, 0, 0};
+  held.sc = held.er = float4{0.f, 0.f, 0.f, 0.f};
+  held.tg = uint4{0u, 0u, 0u, 0u};
+  held.t = n_tiles;
+  auto check_held = [&](const Dots6& d) __attribute__((always_inline)) {
+    floatx4 u0, u1;
+    dots6_u<D>(d, q, held.sc, held.er, u0, u1);
+    if constexpr (MODE == 0) {
+      // a full tile (wave-uniform; every tile but the shard's last) skips the per-row checks
+      const int t = __builtin_amdgcn_readfirstlane(held.t);
+      if ((t + 1) * kTileRows <= n_rows)
+        topk_tile_tg<FILTER>(st, u0, u1, t, 0x7fffffff, held.tg, lane);
+      else
+        topk_tile_tg<FILTER>(st, u0, u1, t, n_rows, held.tg, lane);
+    } else {
+      vmax = fmaxf(vmax, fmaxf(fmaxf(fmaxf(u0[0], u0[1]), fmaxf(u0[2], u0[3])),
+                               fmaxf(fmaxf(u1[0], u1[1]), fmaxf(u1[2], u1[3]))));
+    }
+  };
+  auto process = [&](const Batch& b, int j) __attribute__((always_inline)) {
+    const int p = p_first + j * p_step;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if constexpr (MODE == 2) {
+        intx4 x = b.x[0];
+#pragma unroll
+        for (int L = 1; L < 9; ++L) x += b.x[L];
+        if (u == 0) vmax = fmaxf(vmax, (float)(x[0] + x[1] + x[2] + x[3]));
+        vmax = fmaxf(vmax, b.sc[u].x + b.er[u].x);
+      } else {
+        uint32_t w[18];
+#pragma unroll
+        for (int g = 0; g < 18; ++g) w[g] = (uint32_t)b.x[(18 * u + g) >> 2][(18 * u + g) & 3];
+        if constexpr (MODE == 3) {
+          intx4 x = {0, 0, 0, 0};
+#pragma unroll
+          for (int s = 0; s < steps8<D>(); ++s) x += unpack6(w[3 * s], w[3 * s + 1], w[3 * s + 2]);
+          vmax = fmaxf(vmax, (float)(x[0] + x[1] + x[2] + x[3]) + b.sc[u].x + b.er[u].x);
+        } else {
+          tile_dots6<D>(w, q, dots[u]);   // issued first; the held tile's check beside them
+          check_held(dots[u ^ 1]);
+          held.sc = b.sc[u];
+          held.er = b.er[u];
+          held.tg = b.tg[u];
+          held.t = 2 * p + u;
+        }
+      }
+    }
+  };
+  if (n_mine > 0) {
+    Batch b0, b1, b2;
+    const auto at = [&](int j) { return min(j, n_mine - 1); };
+    load(b0, 0);
+    load(b1, at(1));
+    int j = 0;
+    while (true) {
+      load(b2, at(j + 2));
+      process(b0, j);
+      if (++j >= n_mine) break;
+      load(b0, at(j + 2));
+      process(b1, j);
+      if (++j >= n_mine) break;
+      load(b1, at(j + 2));
+      process(b2, j);
+      if (++j >= n_mine) break;
+    }
+    if constexpr (MODE == 0 || MODE == 1) check_held(dots[1]);   // the last tile
+  }
+  if constexpr (MODE != 0) {
+    if (vmax == 12345.0f) part_s[gw] = vmax;   // never true in practice; defeats DCE
+    return;
+  }
+  topk_finish<2>(st, lane, gw, nw, part_s, part_i, heads_s, heads_i, heads_n);
+}
+
+// prescan_bounds_kernel for the 6-bit copy: one wave per requested row, through tile_u6
+template <int D>
+__global__ __launch_bounds__(64) void prescan6_bounds_kernel(
+    const char* __restrict__ c6, const float* __restrict__ meta,
+    const intx4* __restrict__ qfrag8, const float* __restrict__ qp8,
+    const int64_t* __restrict__ rows, int64_t n, int64_t n_rows, int B,
+    float* __restrict__ out) {
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  const int lane = threadIdx.x;
+  const int64_t row = rows[i];
+  if (row < 0 || row >= n_rows) {   // not a stored row: never dereferenced
+    if (lane < B) out[(int64_t)lane * n + i] = kNegInf;
+    return;
+  }
+  Query8<D> q;
+  query8_load<D>(q, qfrag8, qp8, lane);
+  floatx4 u0, u1;
+  tile_u6_at<D>(c6, meta, row >> 4, q, lane, u0, u1);
+  // lane holds rows 4(lane >> 4) + r of queries (lane & 15), 16 + (lane & 15)
+  const int r = (int)(row & 15) - 4 * (lane >> 4);
+  if (r >= 0 && r < 4) {
+    const int qa = lane & 15, qb = 16 + (lane & 15);
+    const float va = r == 0 ? u0[0] : r == 1 ? u0[1] : r == 2 ? u0[2] : u0[3];
+    const float vb = r == 0 ? u1[0] : r == 1 ? u1[1] : r == 2 ? u1[2] : u1[3];
+    if (qa < B) out[(int64_t)qa * n + i] = va;
+    if (qb < B) out[(int64_t)qb * n + i] = vb;
+  }
+}
+
 // ---- register-pending top-k (LDS-query scan): the pending candidates of a lane live in
 // VGPRs (8 slots per query tile, pushed by shifting: static register indices), so a wave's
 // LDS is only its keep lists (8 KB) plus a 512-B gather scratch — which lets 8 waves share one

@@ -188,6 +188,27 @@ __global__ __launch_bounds__(256) void sample_kernel_i8(
   sample_epilogue<FILTER>(sc, st, lane, tags, filt, n_rows, n_sample, smax);
 }
 
+// sample for a pass that scans the 6-bit copy (scan_kernel_i6): the same sample tiles, scored
+// with that scan's own u (tile_u6)
+template <int D, bool FILTER>
+__global__ __launch_bounds__(256) void sample_kernel_i6(
+    const char* __restrict__ c6, const float* __restrict__ meta,
+    const uint32_t* __restrict__ tags, const uint32_t* __restrict__ filt,
+    const intx4* __restrict__ qfrag8, const float* __restrict__ qp8, int n_rows, int n_tiles,
+    int n_sample, float* __restrict__ smax) {
+  const int lane = threadIdx.x & 63;
+  SampleTiles st;
+  // only the tile numbers are used: the copy is addressed by pair (tile_u6_at)
+  if (!sample_tiles<1>(st, reinterpret_cast<const half8*>(c6), n_tiles, n_sample, lane)) return;
+  Query8<D> q;
+  query8_load<D>(q, qfrag8, qp8, lane);
+  floatx4 sc[2][2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    tile_u6_at<D>(c6, meta, u == 0 ? st.t0 : st.t1, q, lane, sc[u][0], sc[u][1]);
+  sample_epilogue<FILTER>(sc, st, lane, tags, filt, n_rows, n_sample, smax);
+}
+
 // qprep + sample in ONE launch (D <= 384, one query group; round 3): every workgroup builds the
 // 32 queries' B-fragments itself (qprep_slot, 8 slots per wave, into an LDS image of qfrag's
 // layout) and samples its tiles against them; workgroup 0 also publishes qn / qfrag / filt / eps

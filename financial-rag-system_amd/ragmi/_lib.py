@@ -165,6 +165,7 @@ INDEX_API = {
     "rag_index_set_prescan": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "rag_index_prescan": (ctypes.c_int, [c_vp]),
     "rag_index_prescan_passes": (ctypes.c_int, [c_vp, c_i64p]),
+    "rag_index_prescan6_passes": (ctypes.c_int, [c_vp, c_i64p]),
     "rag_index_prescan_bounds": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int64,
                                                 c_vp]),
     "rag_stream_create_cu_partition": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,

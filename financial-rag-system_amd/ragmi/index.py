@@ -32,7 +32,9 @@ FUSION_MAX_ENTRIES = 4096      # RAG_FUSION_MAX_ENTRIES: lists x entries per lis
 SEARCH_FULL = 1     # RAG_SEARCH_FULL (rag_index_search_view)
 STORAGE = {"fp16": 0, "fp32": 1}   # RAG_STORE_FP16 / RAG_STORE_FP32
 PRESCAN_OFF, PRESCAN_AUTO, PRESCAN_ALWAYS = 0, 1, 2   # RAG_PRESCAN_*: FlatIndex.set_prescan
+PRESCAN_ALWAYS6 = 3            # RAG_PRESCAN_ALWAYS6: every k <= 32 pass over the 6-bit copy
 PRESCAN_MIN_ROWS = 500000      # RAG_PRESCAN_MIN_ROWS: auto mode's smallest shard
+PRESCAN6_MIN_ROWS = 4000000    # RAG_PRESCAN6_MIN_ROWS: auto mode's smallest 6-bit shard
 CREATE_DIAGNOSTIC = 0x100          # RAG_CREATE_DIAGNOSTIC: honour the RAGMI_* A/B knobs
 
 
@@ -581,9 +583,10 @@ class FlatIndex(ListOps):
         check(self._L.rag_index_set_scan_order(self._h, mode))
 
     def set_prescan(self, mode: int) -> None:
-        """0 off / 1 auto (default) / 2 always: whether k <= 32 passes stream the int8 copy of
-        the rows (dim 384, fp16 storage) and certify the exact top-k from the fp16 rows;
-        results are the same in every mode (rag_index_set_prescan)."""
+        """0 off / 1 auto (default) / 2 always / 3 always 6-bit: whether k <= 32 passes stream
+        the int8 (or 6-bit) copy of the rows (dim 384, fp16 storage) and certify the exact top-k
+        from the fp16 rows; results are the same in every mode. Mode 3 builds the 6-bit copy of
+        an index that has none (rag_index_set_prescan)."""
         check(self._L.rag_index_set_prescan(self._h, int(mode)))
 
     def prescan(self) -> int:
@@ -591,16 +594,23 @@ class FlatIndex(ListOps):
         return int(self._L.rag_index_prescan(self._h))
 
     def prescan_passes(self) -> int:
-        """Search passes since creation that streamed the int8 copy
+        """Search passes since creation that streamed a prescan copy, int8 or 6-bit
         (rag_index_prescan_passes): ceil(B / 32) per k <= 32 search the prescan took, nothing
         for any other. Host state; no synchronisation."""
         n = ctypes.c_int64()
         check(self._L.rag_index_prescan_passes(self._h, ctypes.byref(n)))
         return int(n.value)
 
+    def prescan6_passes(self) -> int:
+        """Those of prescan_passes() that streamed the 6-bit copy (rag_index_prescan6_passes)."""
+        n = ctypes.c_int64()
+        check(self._L.rag_index_prescan6_passes(self._h, ctypes.byref(n)))
+        return int(n.value)
+
     def prescan_bounds(self, queries, rows) -> torch.Tensor:
         """[B, n] upper bounds u of the prescan for stored rows `rows` against `queries`
-        (B <= 32), from the stored int8 copy (rag_index_prescan_bounds; diagnostic)."""
+        (B <= 32), from the stored copy the current mode streams (rag_index_prescan_bounds;
+        diagnostic)."""
         q = _as_dev(queries, torch.float32, self.device)
         r = _as_dev(rows, torch.int64, self.device)
         out = torch.empty((q.shape[0], r.shape[0]), dtype=torch.float32, device=self.device)

@@ -624,32 +624,60 @@ int rag_index_set_scan_order(rag_index_t* index, int serial);
  * top-k as it does after the fp16 scan: returned ids and scores are the same in every mode,
  * bit for bit. The wider error band makes the list re-scoring fallback (tier 1 of
  * rag_index_exactness_stats) common, which is why the default is by size:
- *   RAG_PRESCAN_OFF     always the fp16 scan
- *   RAG_PRESCAN_AUTO    (default) the int8 prescan for passes (filtered ones included) over
- *                       at least RAG_PRESCAN_MIN_ROWS rows, else the fp16 scan
- *   RAG_PRESCAN_ALWAYS  the int8 prescan for every k <= RAG_MAX_K pass
+ *   RAG_PRESCAN_OFF      always the fp16 scan
+ *   RAG_PRESCAN_AUTO     (default) the int8 prescan for passes (filtered ones included) over
+ *                        at least RAG_PRESCAN_MIN_ROWS rows, else the fp16 scan; the 6-bit
+ *                        prescan (below) from RAG_PRESCAN6_MIN_ROWS rows
+ *   RAG_PRESCAN_ALWAYS   the int8 prescan for every k <= RAG_MAX_K pass
+ *   RAG_PRESCAN_ALWAYS6  the 6-bit prescan for every k <= RAG_MAX_K pass
  * Indexes without the copy (dim 1024, fp32 storage) accept any mode and stay on the fp16 scan.
  * No reference counterpart (Qdrant's scalar quantisation with rescoring is approximate; this
- * one is certified exact). */
-enum { RAG_PRESCAN_OFF = 0, RAG_PRESCAN_AUTO = 1, RAG_PRESCAN_ALWAYS = 2 };
+ * one is certified exact).
+ *
+ * 6-bit prescan. The largest shards keep a third image: one integer in [-31, 31] per element
+ * (six bits, 288 B per row) with its own scale and measured error per row, +296 B per row
+ * (+38 % of the fp16 rows: 2.96 GB more at 10M x 384). A pass over it reads 0.755x the int8
+ * pass's bytes and ranks by the same kind of upper bound; the certificate band is about four
+ * times wider, so every query of such a pass takes tier 1 (about 200 rescored rows at 10M
+ * rows). The copy exists only where it is used: in an index whose capacity is at least
+ * RAG_PRESCAN6_MIN_ROWS (at creation or after rag_index_reserve), or once
+ * RAG_PRESCAN_ALWAYS6 is set, which builds it from the stored rows. It is rebuilt with the
+ * int8 copy by every call that writes rows, and on import. */
+enum {
+  RAG_PRESCAN_OFF = 0,
+  RAG_PRESCAN_AUTO = 1,
+  RAG_PRESCAN_ALWAYS = 2,
+  RAG_PRESCAN_ALWAYS6 = 3
+};
 #define RAG_PRESCAN_MIN_ROWS 500000
+#define RAG_PRESCAN6_MIN_ROWS 4000000
 /* The routing rule itself (the library calls this; no device involved): 1 when a pass of `k`
- * over `count` rows of a (dim, storage) index in `mode` streams the int8 copy. */
+ * over `count` rows of a (dim, storage) index in `mode` streams a prescan copy (either). */
 #define RAG_PRESCAN_ROUTES(mode, dim, storage, k, count)                                   \
   ((dim) == 384 && (storage) == RAG_STORE_FP16 && (k) >= 1 && (k) <= RAG_MAX_K &&          \
-   ((mode) == RAG_PRESCAN_ALWAYS ||                                                        \
+   ((mode) == RAG_PRESCAN_ALWAYS || (mode) == RAG_PRESCAN_ALWAYS6 ||                       \
     ((mode) == RAG_PRESCAN_AUTO && (count) >= RAG_PRESCAN_MIN_ROWS)))
+/* 1 when that pass streams the 6-bit copy, given that the index keeps one (else the int8 copy
+ * serves it): RAG_PRESCAN_ALWAYS6, or auto from RAG_PRESCAN6_MIN_ROWS rows.
+ * RAG_PRESCAN_ALWAYS stays the int8 prescan. */
+#define RAG_PRESCAN6_ROUTES(mode, dim, storage, k, count)                                  \
+  ((dim) == 384 && (storage) == RAG_STORE_FP16 && (k) >= 1 && (k) <= RAG_MAX_K &&          \
+   ((mode) == RAG_PRESCAN_ALWAYS6 ||                                                       \
+    ((mode) == RAG_PRESCAN_AUTO && (count) >= RAG_PRESCAN6_MIN_ROWS)))
 int rag_index_set_prescan(rag_index_t* index, int mode);
 /* The mode set (-1 for NULL). */
 int rag_index_prescan(const rag_index_t* index);
-/* *n = the search passes since creation that streamed the int8 copy (scan_kernel_i8): what
- * tells a pass of the prescan from one of the fp16 scan, whose results are the same. A search
- * of B queries with k <= RAG_MAX_K that routes to the prescan adds ceil(B / RAG_QUERY_TILE);
- * every other pass adds nothing. Host state only, no device work. */
+/* *n = the search passes since creation that streamed a prescan copy (scan_kernel_i8 or
+ * scan_kernel_i6): what tells a pass of the prescan from one of the fp16 scan, whose results
+ * are the same. A search of B queries with k <= RAG_MAX_K that routes to the prescan adds
+ * ceil(B / RAG_QUERY_TILE); every other pass adds nothing. Host state only, no device work. */
 int rag_index_prescan_passes(rag_index_t* index, int64_t* n);
+/* *n = those of them that streamed the 6-bit copy (scan_kernel_i6). */
+int rag_index_prescan6_passes(rag_index_t* index, int64_t* n);
 /* Diagnostic view of the certificate's premise: out_u_dev[b * n + i] = the prescan's upper
  * bound u of stored row rows_dev[i] against query b (q_dev: B <= 32 queries, as for a search),
- * computed from the stored copy by the device function the prescan itself uses; -inf for a
+ * computed from the stored copy by the device function the prescan itself uses (of the copy
+ * a k = 1 pass of the index streams in its current mode; the int8 one where none); -inf for a
  * row outside [0, count). u >= the exact score of every pair is what the certificate rests
  * on. RAG_EINVAL for an index without the copy. Synchronous. */
 int rag_index_prescan_bounds(rag_index_t* index, const float* q_dev, int B,

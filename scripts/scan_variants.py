@@ -24,7 +24,12 @@ NAMES = {0: "prod (seeded, interleaved, nt, sched-barrier)", 1: "unseeded", 2: "
          12: "dynamic (2), loads only (timed per launch)",
          13: "static prod (timed per launch)", 14: "static loads only (timed per launch)",
          15: "prod without the end-of-scan pending sort (probe)",
-         16: "prod with the round-1 pending sort (32 lanes x 2 queries)"}
+         16: "prod with the round-1 pending sort (32 lanes x 2 queries)",
+         17: "int8 prescan: production", 18: "int8 prescan: MFMA + bound, no top-k",
+         19: "int8 prescan: loads only",
+         20: "6-bit prescan: production", 21: "6-bit prescan: MFMA + bound, no top-k",
+         22: "6-bit prescan: loads only", 23: "6-bit prescan: loads + unpack",
+         24: "6-bit prescan: production, seeds at +inf (top-k never taken)"}
 
 
 def main():
@@ -34,6 +39,8 @@ def main():
     dev = torch.device("cuda", 0)
     idx = FlatIndex(bench.D, rows, dev, diagnostic=True)
     bench.build_shard(idx, 0, rows, rows, dev)
+    if any(v >= 20 for v in variants):
+        idx.set_prescan(3)          # the 6-bit copy, whatever the shard's size
     qs, _ = bench.make_queries(1, rows, dev)
     res = {v: [] for v in variants}
     for _ in range(rounds):
