@@ -1,10 +1,11 @@
 // index_store.hip — the storage side of the flat index's extern "C" boundary (declared in
 // include/ragmi.h): handle lifetime and capacity growth, upsert / import / export, row movement
-// (select, move, gather, scatter), key columns and filter views.
+// (select, move, gather, scatter), key columns and filter views, order_rows and facet_counts.
 #include "index_host.hpp"
 // prep_kernels.hip for upsert_kernel / requant_kernel: all templates or inlined, so two units
 #include "prep_kernels.hip"
 #include "rows_kernels.hip"
+#include "order_kernels.hip"
 #include "filter_kernels.hip"
 
 using namespace ragmi;
@@ -234,11 +235,14 @@ int negative_count(const rag_index* h) {
   return ragmi::fail(h ? RAG_ERANGE : RAG_EINVAL, h ? "new_count is negative" : "index is NULL");
 }
 
-// the ordered select (count / prefix sum / emit) over tag column `tags` of h->count rows
+// the ordered select (count / prefix sum / emit) over tag column `tags` of the rows
+// [row0, h->count): the chunks from row0's on
 int select_locked(rag_index* h, const uint32_t* tags, uint32_t tag_mask, uint32_t tag_value,
-                  int64_t* out_rows, int64_t cap, int64_t* out_n, hipStream_t st) {
+                  int64_t row0, int64_t* out_rows, int64_t cap, int64_t* out_n, hipStream_t st) {
   const int64_t count = h->count;
-  const int nb = (int)((count + ragmi::kSelChunk - 1) / ragmi::kSelChunk);
+  const int nb = row0 >= count ? 0
+                               : (int)((count + ragmi::kSelChunk - 1) / ragmi::kSelChunk -
+                                       row0 / ragmi::kSelChunk);
   if (nb == 0) {
     RAG_HIP(hipMemsetAsync(out_n, 0, sizeof(int64_t), st));
     return RAG_OK;
@@ -247,22 +251,25 @@ int select_locked(rag_index* h, const uint32_t* tags, uint32_t tag_mask, uint32_
   RAG_HIP(offsets.alloc((size_t)nb * sizeof(int64_t)));
   int64_t* const off = reinterpret_cast<int64_t*>(offsets.p);
   ragmi::select_count_kernel<<<dim3((unsigned)nb), dim3(ragmi::kSelBlock), 0, st>>>(
-      tags, count, tag_mask, tag_value, off);
+      tags, row0, count, tag_mask, tag_value, off);
   ragmi::select_scan_kernel<<<dim3(1), dim3(ragmi::kSelScanBlock), 0, st>>>(off, nb, out_n);
   if (cap > 0)
     ragmi::select_emit_kernel<<<dim3((unsigned)nb), dim3(ragmi::kSelBlock), 0, st>>>(
-        tags, count, tag_mask, tag_value, off, out_rows, cap);
+        tags, row0, count, tag_mask, tag_value, off, out_rows, cap);
   RAG_HIP(hipGetLastError());
   return RAG_OK;
 }
 
-// rag_index_select_rows, and (view) rag_index_select_rows_view over a one-program filter view
+// rag_index_select_rows, and (view) rag_index_select_rows_view / rag_index_select_rows_from over
+// a one-program filter view, from row `row0` on
 int select_rows(rag_index* h, const uint32_t* progs, int64_t words, bool view, uint32_t tag_mask,
-                uint32_t tag_value, int64_t* out_rows, int64_t cap, int64_t* out_n, void* stream) {
+                uint32_t tag_value, int64_t row0, int64_t* out_rows, int64_t cap, int64_t* out_n,
+                void* stream) {
   ragmi::clear_error();
   if (!h) return ragmi::fail(RAG_EINVAL, "index is NULL");
   if (view)
     if (const int rc = view_args(progs, words, 1)) return rc;
+  if (row0 < 0) return ragmi::fail(RAG_EINVAL, "select: row0 is negative");
   if (!out_n || cap < 0 || (cap > 0 && !out_rows))
     return ragmi::fail(RAG_EINVAL, "bad select args (out_n NULL, or cap > 0 without out_rows)");
   const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -273,7 +280,7 @@ int select_rows(rag_index* h, const uint32_t* progs, int64_t words, bool view, u
     if (const int rc = acquire_view(h, st, &v)) return rc;
     if (const int rc = launch_filter_view(h, progs, words, 1, v, st)) return rc;
   }
-  return select_locked(h, v, tag_mask, tag_value, out_rows, cap, out_n, st);
+  return select_locked(h, v, tag_mask, tag_value, row0, out_rows, cap, out_n, st);
 }
 
 // rag_index_write_keys / rag_index_gather_keys: the shared argument checks, the column check
@@ -679,7 +686,7 @@ int rag_index_export_tags(rag_index_t* h, int64_t row0, int64_t n, uint32_t* out
 
 int rag_index_select_rows(rag_index_t* h, uint32_t tag_mask, uint32_t tag_value,
                           int64_t* out_rows, int64_t cap, int64_t* out_n, void* stream) {
-  return select_rows(h, nullptr, 0, false, tag_mask, tag_value, out_rows, cap, out_n, stream);
+  return select_rows(h, nullptr, 0, false, tag_mask, tag_value, 0, out_rows, cap, out_n, stream);
 }
 
 int rag_index_filter_view(rag_index_t* h, const uint32_t* progs, int64_t words, int n_programs,
@@ -697,7 +704,14 @@ int rag_index_filter_view(rag_index_t* h, const uint32_t* progs, int64_t words, 
 
 int rag_index_select_rows_view(rag_index_t* h, const uint32_t* progs, int64_t words,
                                int64_t* out_rows, int64_t cap, int64_t* out_n, void* stream) {
-  return select_rows(h, progs, words, true, 1u, 1u, out_rows, cap, out_n, stream);
+  return select_rows(h, progs, words, true, 1u, 1u, 0, out_rows, cap, out_n, stream);
+}
+
+int rag_index_select_rows_from(rag_index_t* h, const uint32_t* progs, int64_t words, int64_t row0,
+                               int64_t* out_rows, int64_t cap, int64_t* out_n, void* stream) {
+  if (!progs)   // every row: the (0, 0) select over the stored tags
+    return select_rows(h, nullptr, 0, false, 0u, 0u, row0, out_rows, cap, out_n, stream);
+  return select_rows(h, progs, words, true, 1u, 1u, row0, out_rows, cap, out_n, stream);
 }
 
 int rag_index_move_rows(rag_index_t* h, const int64_t* src_rows, const int64_t* dst_rows,
@@ -778,6 +792,106 @@ int rag_index_gather_keys(rag_index_t* h, int col, const int64_t* rows, int64_t 
     ragmi::gather_keys_kernel<<<grid, dim3(ragmi::kKeyBlock), 0, st>>>(column, rows, n,
                                                                         h->cap_rows, out_keys);
   });
+}
+
+// ---- order_by and facet (order_kernels.hip) ----
+
+int rag_index_order_rows(rag_index_t* h, const uint32_t* progs, int64_t words, int col, int flags,
+                         int64_t lo, int64_t hi, int limit, int64_t* out_keys, int64_t* out_rows,
+                         int64_t* out_n, void* stream) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "order_rows: index is NULL");
+  if (!out_keys || !out_rows || !out_n)
+    return ragmi::fail(RAG_EINVAL, "order_rows: a NULL output pointer");
+  if (limit < 1 || limit > RAG_ORDER_MAX)
+    return ragmi::fail(RAG_ERANGE, "order_rows: limit must be in [1, RAG_ORDER_MAX=4096]");
+  if (progs)
+    if (const int rc = view_args(progs, words, 1)) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (col < 0 || col >= h->n_keys)
+    return ragmi::fail(RAG_ERANGE, "order_rows: no such column (call rag_index_keys_create)");
+  RAG_HIP(hipSetDevice(h->device));
+  uint32_t* view = nullptr;
+  if (progs) {
+    if (const int rc = acquire_view(h, st, &view)) return rc;
+    if (const int rc = launch_filter_view(h, progs, words, 1, view, st)) return rc;
+  }
+  int n2 = 1;
+  while (n2 < limit) n2 <<= 1;
+  const uint32_t desc = (flags & RAG_ORDER_DESC) ? 1u : 0u;
+  const int64_t count = h->count;
+  const int nb = (int)((count + kSelChunk - 1) / kSelChunk);
+  if (nb == 0) {   // nothing to rank: the sort pads the whole list
+    RAG_HIP(hipMemsetAsync(out_n, 0, 2 * sizeof(int64_t), st));
+  } else {
+    // scratch: the passes' counters, the states, the total below the threshold, then per chunk
+    // the rows below the threshold and the rows of its rank
+    constexpr size_t kHist = (size_t)kOrdPasses * 256 * sizeof(u64);
+    constexpr size_t kState = (size_t)(kOrdPasses + 1) * sizeof(OrderState);
+    constexpr size_t kHead = kHist + kState + 2 * sizeof(int64_t);
+    StreamScratch scratch(st);
+    RAG_HIP(scratch.alloc(kHead + 2 * (size_t)nb * sizeof(int64_t)));
+    RAG_HIP(hipMemsetAsync(scratch.p, 0, kHead, st));
+    u64* const hist = reinterpret_cast<u64*>(scratch.p);
+    OrderState* const state = reinterpret_cast<OrderState*>(scratch.p + kHist);
+    int64_t* const tot = reinterpret_cast<int64_t*>(scratch.p + kHist + kState);
+    int64_t* const less = tot + 2;
+    int64_t* const eq = less + nb;
+    const OrderArgs a{view, h->keys[col], count, lo, hi, desc};
+    const int64_t steps = (count + kOrdRows - 1) / kOrdRows;
+    const dim3 grid((unsigned)std::min<int64_t>(steps, (int64_t)kOrdWgPerCu * h->n_cu));
+    for (int p = 0; p < kOrdPasses; ++p)
+      order_hist_kernel<<<grid, dim3(kOrdBlock), 0, st>>>(a, p, limit, hist, state);
+    order_count_kernel<<<dim3((unsigned)nb), dim3(kOrdBlock), 0, st>>>(a, limit, hist, state, less,
+                                                                      eq);
+    order_scan_kernel<<<dim3(1), dim3(kSelScanBlock), 0, st>>>(less, eq, nb, hist, state, tot,
+                                                               out_n);
+    order_emit_kernel<<<dim3((unsigned)nb), dim3(kOrdBlock), 0, st>>>(a, limit, state, less, eq,
+                                                                     tot, out_keys, out_rows);
+    RAG_HIP(hipGetLastError());
+  }
+  order_sort_kernel<<<dim3(1), dim3(kOrdSortBlock), (size_t)n2 * 16, st>>>(out_keys, out_rows,
+                                                                         out_n, limit, n2, desc);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+int rag_index_facet_counts(rag_index_t* h, const uint32_t* progs, int64_t words, int field,
+                           int n_codes, int64_t* out_counts, void* stream) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "facet_counts: index is NULL");
+  if (!out_counts) return ragmi::fail(RAG_EINVAL, "facet_counts: the output pointer is NULL");
+  if (field < 0 || field > 1)
+    return ragmi::fail(RAG_ERANGE, "facet_counts: field must be 0 or 1");
+  if (n_codes < 0 || n_codes > 65535)
+    return ragmi::fail(RAG_ERANGE, "facet_counts: n_codes must be in [0, 65535]");
+  if (progs)
+    if (const int rc = view_args(progs, words, 1)) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  uint32_t* view = nullptr;
+  if (progs) {
+    if (const int rc = acquire_view(h, st, &view)) return rc;
+    if (const int rc = launch_filter_view(h, progs, words, 1, view, st)) return rc;
+  }
+  const size_t bins = (size_t)n_codes + 1;
+  RAG_HIP(hipMemsetAsync(out_counts, 0, bins * sizeof(int64_t), st));
+  const int64_t count = h->count;
+  if (count == 0) return RAG_OK;
+  const int64_t steps = (count + kFacetChunk - 1) / kFacetChunk;
+  const dim3 grid((unsigned)std::min<int64_t>(steps, (int64_t)kFacetWgPerCu * h->n_cu));
+  u64* const out = reinterpret_cast<u64*>(out_counts);
+  const uint32_t shift = 16u * (uint32_t)field;
+  if (bins <= (size_t)kFacetLdsBins)
+    facet_kernel<true><<<grid, dim3(kFacetBlock), bins * 4, st>>>(h->tags, view, count, shift,
+                                                                  (uint32_t)n_codes, out);
+  else
+    facet_kernel<false><<<grid, dim3(kFacetBlock), 0, st>>>(h->tags, view, count, shift,
+                                                            (uint32_t)n_codes, out);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
 }
 
 }  // extern "C"

@@ -14,8 +14,9 @@
 namespace ragmi {
 
 // ----------------------------------------------------------------------------------------
-// select: rows r < count with (tag[r] & mask) == value, ascending — an ordered stream
-// compaction over the tag array in three launches:
+// select: rows row0 <= r < count with (tag[r] & mask) == value, ascending — an ordered stream
+// compaction over the tag array in three launches (the chunks from row0's on: workgroup b takes
+// chunk chunk0 + b, chunk0 = row0 / kSelChunk; rag_index_select_rows_from; row0 = 0 otherwise):
 //   select_count_kernel   matches per chunk of kSelChunk rows (one workgroup per chunk)
 //   select_scan_kernel    exclusive prefix sum over the chunks (one workgroup), total -> *out_n
 //   select_emit_kernel    each chunk re-reads its tags (L2 / Infinity Cache warm) and writes
@@ -31,28 +32,29 @@ constexpr int kSelScanBlock = 1024;
 // f[j] = row r + j matches; r is a multiple of 4 and the tag array holds a multiple of 16
 // rows, so the 16-byte load stays inside it whenever r < count
 __device__ __forceinline__ void select_flags(const uint32_t* __restrict__ tags, int64_t r,
-                                             int64_t count, uint32_t mask, uint32_t value,
-                                             bool (&f)[4]) {
+                                             int64_t row0, int64_t count, uint32_t mask,
+                                             uint32_t value, bool (&f)[4]) {
   f[0] = f[1] = f[2] = f[3] = false;
   if (r < count) {
     const uint4 t = *reinterpret_cast<const uint4*>(tags + r);
-    f[0] = (t.x & mask) == value;
-    f[1] = r + 1 < count && (t.y & mask) == value;
-    f[2] = r + 2 < count && (t.z & mask) == value;
-    f[3] = r + 3 < count && (t.w & mask) == value;
+    f[0] = r >= row0 && (t.x & mask) == value;
+    f[1] = r + 1 >= row0 && r + 1 < count && (t.y & mask) == value;
+    f[2] = r + 2 >= row0 && r + 2 < count && (t.z & mask) == value;
+    f[3] = r + 3 >= row0 && r + 3 < count && (t.w & mask) == value;
   }
 }
 
 __global__ __launch_bounds__(kSelBlock) void select_count_kernel(
-    const uint32_t* __restrict__ tags, int64_t count, uint32_t mask, uint32_t value,
+    const uint32_t* __restrict__ tags, int64_t row0, int64_t count, uint32_t mask, uint32_t value,
     int64_t* __restrict__ counts) {
   __shared__ int wsum[kSelBlock / 64];
   const int tid = threadIdx.x;
   int c = 0;   // wave-uniform
   for (int it = 0; it < kSelIters; ++it) {
-    const int64_t r = (int64_t)blockIdx.x * kSelChunk + it * (kSelBlock * 4) + tid * 4;
+    const int64_t r =
+        (row0 / kSelChunk + blockIdx.x) * kSelChunk + it * (kSelBlock * 4) + tid * 4;
     bool f[4];
-    select_flags(tags, r, count, mask, value, f);
+    select_flags(tags, r, row0, count, mask, value, f);
 #pragma unroll
     for (int j = 0; j < 4; ++j) c += __popcll(__ballot(f[j]));
   }
@@ -65,10 +67,9 @@ __global__ __launch_bounds__(kSelBlock) void select_count_kernel(
   }
 }
 
-// counts[0..nb) -> exclusive prefix sums in place; *out_n = the total
-__global__ __launch_bounds__(kSelScanBlock) void select_scan_kernel(int64_t* __restrict__ counts,
-                                                                    int nb,
-                                                                    int64_t* __restrict__ out_n) {
+// counts[0..nb) -> exclusive prefix sums in place, by one workgroup of kSelScanBlock threads;
+// returns the total to every thread
+__device__ int64_t scan_chunks(int64_t* __restrict__ counts, int nb) {
   constexpr int kWaves = kSelScanBlock / 64;
   __shared__ int wtot[kWaves];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -93,11 +94,19 @@ __global__ __launch_bounds__(kSelScanBlock) void select_scan_kernel(int64_t* __r
     carry += tot;
     __syncthreads();
   }
-  if (tid == 0) *out_n = carry;
+  return carry;
+}
+
+// counts[0..nb) -> exclusive prefix sums in place; *out_n = the total
+__global__ __launch_bounds__(kSelScanBlock) void select_scan_kernel(int64_t* __restrict__ counts,
+                                                                    int nb,
+                                                                    int64_t* __restrict__ out_n) {
+  const int64_t total = scan_chunks(counts, nb);
+  if (threadIdx.x == 0) *out_n = total;
 }
 
 __global__ __launch_bounds__(kSelBlock) void select_emit_kernel(
-    const uint32_t* __restrict__ tags, int64_t count, uint32_t mask, uint32_t value,
+    const uint32_t* __restrict__ tags, int64_t row0, int64_t count, uint32_t mask, uint32_t value,
     const int64_t* __restrict__ offsets, int64_t* __restrict__ out, int64_t cap) {
   __shared__ int wcnt[kSelBlock / 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -105,9 +114,10 @@ __global__ __launch_bounds__(kSelBlock) void select_emit_kernel(
   if (base >= cap) return;   // the whole chunk lies past the output (uniform)
   const unsigned long long below = (1ull << lane) - 1ull;
   for (int it = 0; it < kSelIters; ++it) {
-    const int64_t r = (int64_t)blockIdx.x * kSelChunk + it * (kSelBlock * 4) + tid * 4;
+    const int64_t r =
+        (row0 / kSelChunk + blockIdx.x) * kSelChunk + it * (kSelBlock * 4) + tid * 4;
     bool f[4];
-    select_flags(tags, r, count, mask, value, f);
+    select_flags(tags, r, row0, count, mask, value, f);
     int pre = 0, wc = 0;   // matches in lower lanes / in the wave: lanes own rows in order
 #pragma unroll
     for (int j = 0; j < 4; ++j) {

@@ -128,6 +128,13 @@ INDEX_API = {
                                             c_vp]),
     "rag_index_gather_keys": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int64, c_vp,
                                              c_vp]),
+    "rag_index_order_rows": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rag_index_facet_counts": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int,
+                                              ctypes.c_int, c_vp, c_vp]),
+    "rag_index_select_rows_from": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64,
+                                                  c_vp, ctypes.c_int64, c_vp, c_vp]),
     "rag_group_select": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                         c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -17,11 +17,11 @@ import torch
 from . import groups
 from . import qdrant_models as models
 from .coalesce import Coalescer
-from .filters import (DEFAULT_TAG_FIELDS, MAX_PROGRAMS, FilterProgram, PayloadRanges,
-                      PayloadTags, UnsupportedFilter, compile_filter, compile_legacy_only,
-                      pack_view)
+from .filters import (DEFAULT_TAG_FIELDS, KEY_ABSENT, MAX_PROGRAMS, FilterProgram,
+                      PayloadRanges, PayloadTags, UnsupportedFilter, compile_filter,
+                      compile_legacy_only, pack_view)
 from .formula import BAD, MISSING, NONFINITE, compile_formula
-from .index import (FUSION_MAX_ENTRIES, GROUPS_MAX, GROUPS_MAX_CELLS, FlatIndex,
+from .index import (FUSION_MAX_ENTRIES, GROUPS_MAX, GROUPS_MAX_CELLS, ORDER_MAX, FlatIndex,
                     formula_rescore, fuse_rrf, hits_of, host_or_tensor)
 from .shardset import ShardSet, parse_devices
 
@@ -593,6 +593,135 @@ class Collection:
                 out[i] = [models.PointGroup(hits=pts, id=self.tags.value_of(f, key >> shift))
                           for (key, _), pts in zip(found, points)]
             return out
+
+    # ---------------------------------------------------------------- payload queries
+    @staticmethod
+    def _program_of(c):
+        """A compiled filter (not None) as the index's payload queries take it: None for the
+        (0, 0) everything filter, else the packed blob of its one program, a legacy (mask,
+        value) pair as its one-atom program."""
+        if c == (0, 0):
+            return None
+        return pack_view([c if isinstance(c, FilterProgram) else FilterProgram.maskeq(*c)])
+
+    def order_spec(self, order_by):
+        """(field, column, desc, lo, hi) of an order_by argument, a field name or an OrderBy:
+        the field must be a declared range field; start_from becomes the inclusive bound on its
+        side of the direction. ValueError names what is wrong."""
+        ob = order_by if isinstance(order_by, models.OrderBy) else models.OrderBy(key=order_by)
+        if not isinstance(ob.key, str) or ob.key not in self.ranges.fields:
+            raise ValueError(
+                f"order_by {ob.key!r} is not a declared range field (have {self.ranges.fields}): "
+                "declare it with create_payload_index (integer, float or datetime); ordering by "
+                "a keyword field is not built")
+        col = self.ranges.fields.index(ob.key)
+        direction = getattr(ob.direction, "value", ob.direction)
+        if direction not in (None, models.Direction.ASC.value, models.Direction.DESC.value):
+            raise ValueError(f"order_by direction {ob.direction!r}: Direction.ASC or Direction.DESC")
+        desc = direction == models.Direction.DESC.value
+        lo = hi = None
+        if ob.start_from is not None:
+            key = self.ranges.key_of(ob.key, ob.start_from)
+            if key == KEY_ABSENT:
+                kind = self.ranges.kinds[col]
+                raise ValueError(
+                    f"order_by start_from={ob.start_from!r} is not a value of {kind} field "
+                    f"{ob.key!r} (" + ("a datetime or an RFC 3339 string" if kind == "datetime"
+                                       else "a number") + ")")
+            lo, hi = (None, key) if desc else (key, None)
+        return ob.key, col, desc, lo, hi
+
+    def _ordered_rows(self, order_by, limit, c):
+        """(field, rows) of an ordered query under compiled filter `c`: the `limit` first rows
+        by the field's value (index.order_rows; points without the field are left out). The
+        refusals come first; nothing is launched for a filter nothing can match or a limit
+        below 1. Called under the lock."""
+        field, col, desc, lo, hi = self.order_spec(order_by)
+        limit = int(limit)
+        if limit > ORDER_MAX:
+            raise ValueError(f"an ordered query returns at most {ORDER_MAX} points "
+                             f"(RAG_ORDER_MAX), got limit={limit}")
+        if c is None or limit < 1 or not self.row_ids:
+            return field, []
+        rows = self.index.order_rows(col, limit, desc, lo, hi, self._program_of(c))[1]
+        return field, rows.cpu().tolist()
+
+    def record(self, row: int, with_payload=True, with_vectors=False, order_field=None):
+        """Row `row` as a Record; `order_field`: the payload field whose stored value becomes
+        order_value. Called under the lock."""
+        p = self.point(row, 0.0, with_payload, with_vectors)
+        value = (self.payloads[row] or {}).get(order_field) if order_field is not None else None
+        return models.Record(id=p.id, payload=p.payload, vector=p.vector, order_value=value)
+
+    def scroll(self, flt, limit: int = 10, offset=None, with_payload=True, with_vectors=False,
+               order_by=None):
+        """The engine of QdrantClient.scroll: (records, next_page_offset). Without order_by the
+        page holds the first `limit` matching points in storage (row) order from the row of
+        point `offset` on — one select_rows_from of limit + 1 rows, the extra row's id being
+        the next offset — and storage order is stable between writes (a delete moves tail rows
+        into the holes). With order_by: the `limit` first points by that range field's value,
+        no paging. The rows become Records under the same hold of the lock as the select."""
+        if order_by is not None and offset is not None:
+            raise ValueError("scroll: offset cannot be used together with order_by; continue an "
+                             "ordered scroll with OrderBy(start_from=...)")
+        limit = int(limit)
+        with self.lock:
+            c = self.compile_filter(flt)
+            if order_by is not None:
+                field, rows = self._ordered_rows(order_by, limit, c)
+                return [self.record(r, with_payload, with_vectors, field) for r in rows], None
+            row0 = 0
+            if offset is not None:
+                row0 = self.id_to_row.get(_norm_id(offset))
+                if row0 is None:
+                    raise ValueError(f"scroll: offset {offset!r} is not the id of a point of "
+                                     f"collection {self.name!r}")
+            if c is None or limit < 1 or not self.row_ids:
+                return [], None
+            rows = self.index.select_rows_from(row0, self._program_of(c), cap=limit + 1)[0]
+            rows = rows.cpu().tolist()
+            nxt = self.row_ids[rows[limit]] if len(rows) > limit else None
+            return [self.record(r, with_payload, with_vectors) for r in rows[:limit]], nxt
+
+    def search_points_order(self, requests: list, with_vectors=False) -> list:
+        """The ORDER route: per request (order_by, compiled filter, limit) its `limit` first
+        points by the field's value as ScoredPoints, score 0.0 and order_value set; one
+        order_rows per request, resolved under the same hold of the lock."""
+        out = []
+        with self.lock:
+            for order_by, c, limit in requests:
+                field, rows = self._ordered_rows(order_by, limit, c)
+                pts = []
+                for r in rows:
+                    p = self.point(r, 0.0, True, with_vectors)
+                    p.order_value = (self.payloads[r] or {}).get(field)
+                    pts.append(p)
+                out.append(pts)
+        return out
+
+    def facet(self, key: str, flt, limit: int = 10) -> list:
+        """[(value, count)] of tag field `key` over the points a Filter matches: one
+        facet_counts call with n_codes = the codebook's size, code 0 (field absent) and zero
+        counts dropped, ordered by (count desc, value asc; values that do not compare with each
+        other by their str), the first `limit`. Exact."""
+        if key not in self.tags.fields:
+            raise NotImplementedError(
+                f"facet on {key!r}: facets count the keyword fields fixed when the collection is "
+                f"created (payload_tag_fields={self.tags.fields}); a facet on a range field is "
+                "not built")
+        f = self.tags.fields.index(key)
+        with self.lock:
+            c = self.compile_filter(flt)
+            values = list(self.tags.codes[f])          # code i + 1 -> values[i]
+            if c is None or int(limit) < 1 or not values or not self.row_ids:
+                return []
+            counts = self.index.facet_counts(f, len(values), self._program_of(c)).cpu().tolist()
+        hits = [(v, n) for v, n in zip(values, counts[1:]) if n > 0]
+        try:
+            hits.sort(key=lambda h: (-h[1], h[0]))
+        except TypeError:
+            hits.sort(key=lambda h: (-h[1], str(h[0])))
+        return hits[:int(limit)]
 
     def point(self, row: int, score: float, with_payload=True, with_vectors=False):
         payload = self.payloads[row] if with_payload else None

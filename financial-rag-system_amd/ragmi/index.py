@@ -17,7 +17,8 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .filters import KEYS_MAX_COLS, MAX_PROGRAMS, REC_WORDS, view_programs
+from .filters import (KEY_ABSENT, KEY_MAX, KEY_MIN, KEYS_MAX_COLS, MAX_PROGRAMS, REC_WORDS,
+                      view_programs)
 
 MAX_K = 32          # RAG_MAX_K in include/ragmi.h: the scan's certified top-k path
 MAX_K_LARGE = 4096  # RAG_MAX_K_LARGE: k in (32, 4096] takes the exact large-k pass; larger k
@@ -29,6 +30,8 @@ GROUPS_MAX = 1024              # RAG_GROUPS_MAX: groups per query
 GROUPS_MAX_CELLS = 4096        # RAG_GROUPS_MAX_CELLS: groups x hits per group
 FUSION_MAX_LISTS = 16          # RAG_FUSION_MAX_LISTS: lists per request rag_fuse_rrf fuses
 FUSION_MAX_ENTRIES = 4096      # RAG_FUSION_MAX_ENTRIES: lists x entries per list
+ORDER_MAX = 4096               # RAG_ORDER_MAX: the longest list rag_index_order_rows returns
+ORDER_DESC = 1                 # RAG_ORDER_DESC
 SEARCH_FULL = 1     # RAG_SEARCH_FULL (rag_index_search_view)
 STORAGE = {"fp16": 0, "fp32": 1}   # RAG_STORE_FP16 / RAG_STORE_FP32
 PRESCAN_OFF, PRESCAN_AUTO, PRESCAN_ALWAYS = 0, 1, 2   # RAG_PRESCAN_*: FlatIndex.set_prescan
@@ -115,6 +118,40 @@ def plan_removal(count: int, rows):
     stays[d[d >= n1] - n1] = False
     src = n1 + np.nonzero(stays)[0].astype(np.int64)
     return src, dst, n1
+
+
+def order_bounds(lo, hi) -> tuple[int, int]:
+    """The key bounds of order_rows with None filled in: the full interval of present keys."""
+    return (KEY_MIN if lo is None else int(lo)), (KEY_MAX if hi is None else int(hi))
+
+
+def order_rows_np(keys, limit: int, desc: bool = False, lo=None, hi=None, passing=None):
+    """numpy restatement of rag_index_order_rows over one key column of `count` rows (`keys`
+    int64 [count]; `passing`: bool [count], the rows the filter lets through, None = all):
+    (keys, rows, eligible) of the `limit` best eligible rows by (key asc, row asc), or with
+    `desc` (key desc, row asc). Eligible: passing, key != KEY_ABSENT, lo <= key <= hi."""
+    k = np.asarray(keys, np.int64).reshape(-1)
+    lo, hi = order_bounds(lo, hi)
+    ok = (k != KEY_ABSENT) & (k >= lo) & (k <= hi)
+    if passing is not None:
+        ok &= np.asarray(passing, bool).reshape(-1)
+    rows = np.nonzero(ok)[0].astype(np.int64)
+    kk = k[rows]
+    # a descending key order as an ascending one: ~k reverses int64 without overflow
+    order = np.lexsort((rows, ~kk if desc else kk))[:int(limit)]
+    return kk[order], rows[order], int(rows.size)
+
+
+def facet_counts_np(tags, field: int, n_codes: int, passing=None) -> np.ndarray:
+    """numpy restatement of rag_index_facet_counts over the tags of `count` rows: int64
+    [n_codes + 1], the passing rows per code of tag field `field`; codes above n_codes are not
+    counted."""
+    t = np.asarray(tags, np.uint32).reshape(-1)
+    c = ((t >> np.uint32(16 * int(field))) & np.uint32(0xFFFF)).astype(np.int64)
+    ok = c <= int(n_codes)
+    if passing is not None:
+        ok &= np.asarray(passing, bool).reshape(-1)
+    return np.bincount(c[ok], minlength=int(n_codes) + 1).astype(np.int64)
 
 
 def rescue_unanswered(index, s, ids, again) -> None:
@@ -465,6 +502,65 @@ class FlatIndex(ListOps):
         return self._selected(self.count if cap is None else cap, None,
                               lambda rows, cap, n, st: self._L.rag_index_select_rows_view(
                                   self._h, p.data_ptr(), words, rows, cap, n, st))
+
+    # ---------------------------------------------------------------- payload queries
+    def _program(self, programs):
+        """(blob tensor, its pointer, words) of the ONE filter program of a payload query;
+        (None, None, 0) for programs = None, every row. The caller holds the tensor until its
+        launch is enqueued."""
+        if programs is None:
+            return None, None, 0
+        p, words, _ = view_blob(programs, 1, self.device)
+        return p, p.data_ptr(), words
+
+    def select_rows_from(self, row0: int, programs=None, cap: int | None = None):
+        """select_rows_view restricted to rows >= row0 (rag_index_select_rows_from; programs
+        None = every row): (rows int64 cuda tensor, total at or after row0). Synchronises the
+        current stream (the total is read back)."""
+        row0 = int(row0)
+        if row0 < 0:
+            raise ValueError("row0 must be >= 0")
+        p, ptr, words = self._program(programs)
+        if cap is None:
+            cap = max(self.count - row0, 0)
+        return self._selected(cap, None,
+                              lambda rows, cap, n, st: self._L.rag_index_select_rows_from(
+                                  self._h, ptr, words, row0, rows, cap, n, st))
+
+    def order_rows(self, col: int, limit: int, desc: bool = False, lo=None, hi=None,
+                   programs=None):
+        """The `limit` best eligible rows of key column `col` (rag_index_order_rows): (keys
+        int64 [n], rows int64 [n], eligible), n = min(limit, eligible), ordered by (key asc, row
+        asc) or with `desc` (key desc, row asc). Eligible: below the count, passing the ONE
+        program of `programs` (None = every row), key present and lo <= key <= hi (None = no
+        bound). 1 <= limit <= ORDER_MAX. Synchronises the current stream (n is read back)."""
+        limit = int(limit)
+        if not 1 <= limit <= ORDER_MAX:
+            raise ValueError(f"order_rows: limit must lie in [1, {ORDER_MAX}]")
+        lo, hi = order_bounds(lo, hi)
+        p, ptr, words = self._program(programs)
+        keys = torch.empty((limit,), dtype=torch.int64, device=self.device)
+        rows = torch.empty((limit,), dtype=torch.int64, device=self.device)
+        n = torch.empty((2,), dtype=torch.int64, device=self.device)
+        check(self._L.rag_index_order_rows(
+            self._h, ptr, words, int(col), ORDER_DESC if desc else 0, lo, hi, limit,
+            keys.data_ptr(), rows.data_ptr(), n.data_ptr(), _stream_ptr(self.device)))
+        written, eligible = n.tolist()
+        return keys[:written], rows[:written], int(eligible)
+
+    def facet_counts(self, field: int, n_codes: int, programs=None) -> torch.Tensor:
+        """Rows per code of tag field `field` (0 or 1; rag_index_facet_counts): an int64 cuda
+        tensor [n_codes + 1], entry c the rows below the count that pass the ONE program of
+        `programs` (None = every row) and whose code is c; codes above n_codes are not counted.
+        Enqueued on the current stream."""
+        n_codes = int(n_codes)
+        if not 0 <= n_codes <= 0xFFFF:
+            raise ValueError("facet_counts: n_codes must lie in [0, 65535]")
+        p, ptr, words = self._program(programs)
+        out = torch.empty((n_codes + 1,), dtype=torch.int64, device=self.device)
+        check(self._L.rag_index_facet_counts(self._h, ptr, words, int(field), n_codes,
+                                             out.data_ptr(), _stream_ptr(self.device)))
+        return out
 
     def move_rows(self, src, dst, new_count: int) -> None:
         """Copy every stored form of row src[i] into slot dst[i], bit for bit, then set the

@@ -8,7 +8,8 @@ Drop-in for the calls the reference makes on `qdrant_client.QdrantClient`:
   query_points(name, query, limit, query_filter) -> .points[i].{id,score,payload}
                                           main.py:232-237, main2.py:163
 plus query_batch_points (one GPU scan for a whole micro-batch; main2.py:281-295 stage 2),
-the prefetch routes of query_points (FusionQuery / RrfQuery, FormulaQuery),
+the prefetch routes of query_points (FusionQuery / RrfQuery, FormulaQuery), its OrderByQuery
+route, scroll (in storage order, or order_by a range field), facet,
 count (also filtered), retrieve, delete (by ids or by filter) and delete_collection.
 
 `url` is accepted and ignored: the collection lives in this process's GPU memory (the
@@ -147,6 +148,8 @@ def prefetch_lists(prefetch, what: str, to: str, verb: str) -> list:
         if p.prefetch is not None:
             raise ValueError(f"prefetch[{n}]: a nested Prefetch.prefetch is not built")
         vec, mmr = nearest_of(p.query)
+        if isinstance(vec, models.OrderByQuery):
+            raise ValueError(f"prefetch[{n}]: an OrderByQuery inside a Prefetch is not built")
         if vec is None or is_fusion(vec) or isinstance(vec, models.FormulaQuery):
             raise ValueError(f"prefetch[{n}] needs a query: a vector or a NearestQuery")
         if mmr is not None:
@@ -174,23 +177,39 @@ def formula_params(query, prefetch, limit, query_filter=None) -> list:
 
 
 FUSION, FORMULA, MMR, PLAIN = "fusion", "formula", "mmr", "plain"   # the routes of a request
+ORDER = "order"
 
 
 def route_of(query, prefetch=None) -> str:
     """The route of a request, decided once: FORMULA (prefetched candidates re-scored by a
     FormulaQuery), FUSION (prefetched lists fused; every other use of a prefetch goes there to
-    be refused), MMR (a NearestQuery with an Mmr) or PLAIN."""
+    be refused), ORDER (an OrderByQuery: no vector, the points by a range field's value), MMR (a
+    NearestQuery with an Mmr) or PLAIN."""
     if isinstance(query, models.FormulaQuery):
         return FORMULA
+    if isinstance(query, models.OrderByQuery):
+        return ORDER
     if prefetch is not None or isinstance(query, (models.FusionQuery, models.RrfQuery)):
         return FUSION
     return MMR if isinstance(query, models.NearestQuery) and query.mmr is not None else PLAIN
 
 
+def order_params(col: Collection, req) -> tuple:
+    """(order_by, compiled filter, limit) of an ORDER request, or ValueError: prefetched
+    candidates cannot be ordered by a field, the limit must be an int."""
+    if getattr(req, "prefetch", None) is not None:
+        raise ValueError("an OrderByQuery over prefetched candidates (prefetch=...) is not built: "
+                         "it orders the points a query_filter matches")
+    if not _is_int(req.limit):
+        raise ValueError("an order_by query needs an int limit")
+    return req.query.order_by, col.compile_filter(req.filter), int(req.limit)
+
+
 def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=False) -> list:
     """The requests of one route (QueryRequests, in order) answered by one call on the
-    collection: per request its resolved points. On the MMR route a request without an Mmr
-    rides at diversity 0 with its own limit as candidate count."""
+    collection: per request its resolved points (the ORDER route: one order_rows per request
+    inside that call). On the MMR route a request without an Mmr rides at diversity 0 with its
+    own limit as candidate count."""
     if route == FUSION:
         par = [fusion_params(r.query, r.prefetch, r.limit, r.filter) for r in reqs]
         return col.search_points_fusion(
@@ -199,6 +218,8 @@ def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=Fals
         return col.search_points_formula(
             [(r.query, formula_params(r.query, r.prefetch, r.limit, r.filter), int(r.limit))
              for r in reqs], with_vectors)
+    if route == ORDER:
+        return col.search_points_order([order_params(col, r) for r in reqs], with_vectors)
     qs, filters, limits, div, cand = [], [], [], [], []
     for r in reqs:
         q, mmr = nearest_of(r.query)
@@ -381,12 +402,38 @@ class QdrantClient:
                     out.append(models.Record(id=p.id, payload=p.payload, vector=p.vector))
         return out
 
+    def scroll(self, collection_name: str, scroll_filter: models.Filter | None = None,
+               limit: int = 10, offset=None, with_payload=True, with_vectors=False,
+               order_by=None, **kwargs):
+        """Qdrant's scroll: (records, next_page_offset), the points `scroll_filter` matches, page
+        by page. Without `order_by` the pages are in storage (row) order — Qdrant pages by point
+        id; a documented deviation — which is stable between writes; `offset` is the id the page
+        starts at (an unknown id is a ValueError) and next_page_offset the id to pass for the
+        next page, None at the end. With `order_by` (a range field's name or an OrderBy): the
+        `limit` (<= RAG_ORDER_MAX) first points by that field's value, each Record's order_value
+        being its stored payload value, points without the field left out; `offset` is then
+        refused and next_page_offset is None (continue with OrderBy.start_from). The rows are
+        selected or ranked on the GPU (Collection.scroll)."""
+        return self._col(collection_name).scroll(scroll_filter, limit, offset, with_payload,
+                                                 with_vectors, order_by)
+
+    def facet(self, collection_name: str, key: str, facet_filter: models.Filter | None = None,
+              limit: int = 10, exact: bool = True, **kwargs) -> models.FacetResponse:
+        """Qdrant's facet: how many points hold each value of keyword field `key` (one of the
+        collection's payload_tag_fields, else NotImplementedError) under `facet_filter`, the
+        `limit` most frequent values first, ties by value ascending. Counted on the GPU and
+        always exact, whatever `exact` says (Collection.facet)."""
+        hits = self._col(collection_name).facet(key, facet_filter, limit)
+        return models.FacetResponse(hits=[models.FacetValueHit(value=v, count=n)
+                                          for v, n in hits])
+
     def query_points(self, collection_name: str, query=None, limit: int = 10,
                      query_filter: models.Filter | None = None, with_payload=True,
                      with_vectors=False, prefetch=None, **kwargs) -> models.QueryResponse:
         """One request on its route (route_of, answer). A plain request with a limit the scan
-        serves rides the coalescer; fusion, formula and MMR requests never do: their prefetches,
-        their candidate search, are passes of their own."""
+        serves rides the coalescer; fusion, formula, MMR and order_by requests never do: their
+        prefetches, their candidate search, their ranking of a key column are passes of their
+        own."""
         col = self._col(collection_name)
         route = route_of(query, prefetch)
         if route == PLAIN and self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
@@ -403,18 +450,19 @@ class QdrantClient:
                            **kwargs) -> list[models.QueryResponse]:
         """One GPU scan for the whole batch (per-query filters ride along in the kernel). The
         requests are partitioned by route once, each non-empty route is answered by one call
-        (answer), fusion and formula first, and the results are scattered back in request order.
+        (answer), fusion and formula first, then the order_by requests (a route of their own,
+        answered one request at a time), and the results are scattered back in request order.
         With MMR requests in the batch the plain requests ride with them, at diversity 0 with their own
         limit as candidate count: one search at the batch's largest candidate count and one
         MMR launch — unless a plain limit exceeds RAG_MMR_MAX_CANDIDATES, in which case the
         plain requests are searched on their own."""
         col = self._col(collection_name)
-        routes: dict = {FUSION: [], FORMULA: [], PLAIN: [], MMR: []}
+        routes: dict = {FUSION: [], FORMULA: [], ORDER: [], PLAIN: [], MMR: []}
         for i, r in enumerate(requests):
             routes[route_of(r.query, getattr(r, "prefetch", None))].append(i)
         if routes[MMR] and all(int(requests[i].limit) <= MMR_MAX_CANDIDATES
                                for i in routes[PLAIN]):
-            routes = {FUSION: routes[FUSION], FORMULA: routes[FORMULA],
+            routes = {FUSION: routes[FUSION], FORMULA: routes[FORMULA], ORDER: routes[ORDER],
                       MMR: sorted(routes[MMR] + routes[PLAIN])}
         out: list = [None] * len(requests)
         for route, members in routes.items():

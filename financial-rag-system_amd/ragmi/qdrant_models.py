@@ -396,6 +396,40 @@ class FormulaQuery:
     defaults: dict = field(default_factory=dict)
 
 
+class Direction(str, enum.Enum):
+    ASC = "asc"
+    DESC = "desc"
+
+
+@dataclass
+class OrderBy:
+    """Order of scroll(order_by=...) and OrderByQuery: by the value of range field `key`,
+    ascending unless `direction` says Direction.DESC; `start_from`: the first value to return
+    (inclusive: the smallest when ascending, the largest when descending), a number for a
+    number field, a datetime or RFC 3339 string for a datetime field."""
+    key: str
+    direction: Optional[Direction] = None
+    start_from: Any = None
+
+
+@dataclass
+class OrderByQuery:
+    """query_points(query=OrderByQuery(order_by=...)): the `limit` first points by the value of
+    a range field (a field name or an OrderBy); every score is 0.0 and order_value is set."""
+    order_by: Any
+
+
+@dataclass
+class FacetValueHit:
+    value: Any
+    count: int
+
+
+@dataclass
+class FacetResponse:
+    hits: list = field(default_factory=list)
+
+
 @dataclass
 class QueryRequest:
     """Batched query entry for query_batch_points (one per request of a micro-batch); `query`

@@ -368,6 +368,44 @@ class ShardSet(ListOps):
         """FlatIndex.select_rows_view over the set (_select)."""
         return self._select(cap, lambda shard: shard.select_rows_view(programs, cap))
 
+    # ---------------------------------------------------------------- payload queries
+    def select_rows_from(self, row0: int, programs=None, cap: int | None = None):
+        """FlatIndex.select_rows_from over the set: global row0 is, on shard s, its first local
+        row at or after it, ceil((row0 - s) / n); then _select."""
+        row0 = int(row0)
+        if row0 < 0:
+            raise ValueError("row0 must be >= 0")
+        first = {id(shard): max(0, -((s - row0) // self.n)) for s, shard in enumerate(self.shards)}
+        return self._select(cap, lambda shard: shard.select_rows_from(first[id(shard)], programs,
+                                                                      cap))
+
+    @_keeps_device
+    def order_rows(self, col: int, limit: int, desc: bool = False, lo=None, hi=None,
+                   programs=None):
+        """FlatIndex.order_rows over the set, in global rows: every shard's own list (its local
+        order is the global order of its rows) mapped to global rows, the lists merged on the
+        merge device by (key, global row) and cut to `limit`; the eligible counts add up."""
+        ks, rs, eligible = [], [], 0
+        for s, shard in enumerate(self.shards):
+            k, r, e = shard.order_rows(col, limit, desc, lo, hi, programs)
+            eligible += e
+            ks.append(k.to(self.device))
+            rs.append((r * self.n + s).to(self.device))
+        k, r = torch.cat(ks), torch.cat(rs)
+        by_row = torch.sort(r).indices                  # then a stable sort by key: ties stay
+        k, r = k[by_row], r[by_row]                     # in row order in both directions
+        by_key = torch.sort(k, stable=True, descending=bool(desc)).indices[:int(limit)]
+        return k[by_key], r[by_key], eligible
+
+    @_keeps_device
+    def facet_counts(self, field: int, n_codes: int, programs=None) -> torch.Tensor:
+        """FlatIndex.facet_counts summed over the shards, on the merge device."""
+        parts = [shard.facet_counts(field, n_codes, programs) for shard in self.shards]
+        out = parts[0].to(self.device)
+        for p in parts[1:]:
+            out = out + p.to(self.device)
+        return out
+
     # ---------------------------------------------------------------- search
     def _search_args(self, queries, k, filters):
         return self.shards[0]._search_args(queries, k, filters)     # on the merge device

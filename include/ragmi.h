@@ -581,6 +581,49 @@ int rag_index_write_keys(rag_index_t* index, int col, const int64_t* rows_dev,
 int rag_index_gather_keys(rag_index_t* index, int col, const int64_t* rows_dev, int64_t n,
                           int64_t* out_keys_dev, void* stream);
 
+/* Payload queries (QdrantClient.scroll, order_by, facet): ranking and counting over the tag and
+ * key columns, with no vector in play. All three take a filter the way
+ * rag_index_select_rows_view does: progs_dev == NULL means every row < count; otherwise ONE
+ * program (the blob's first record, the blob checked as every *_view call checks it) is
+ * evaluated into the view column the handle keeps for `stream`, and bit 0 of it is read. Rows at
+ * or past the count are never eligible, whatever their (unspecified) keys and tags hold, and no
+ * row outside [0, capacity) is dereferenced. Every argument is checked on the host before any
+ * HIP call; all three are asynchronous on `stream`.
+ *
+ * rag_index_order_rows: the `limit` best eligible rows of key column `col`. A row is eligible
+ * when it is < count, passes the program, its key is not RAG_KEY_ABSENT and lo <= key <= hi
+ * (signed 64-bit, both inclusive). The order is (key ascending, row ascending), or with
+ * RAG_ORDER_DESC in `flags` (key descending, row ascending). out_keys_dev / out_rows_dev (int64
+ * [limit], device) receive the list; out_n_dev (int64 [2], device): [0] the entries written,
+ * min(limit, eligible), [1] the eligible rows. Entries past the written ones hold row -1 and key
+ * RAG_KEY_ABSENT; nothing past entry limit - 1 is written. 1 <= limit <= RAG_ORDER_MAX and
+ * 0 <= col < columns, else RAG_ERANGE; a NULL output is RAG_EINVAL. The result is a pure
+ * function of the columns: the same bits on every run (a radix select of the limit-th key whose
+ * atomics add integer counts only, an ordered emit, a sort of the list in LDS). Each of its 10
+ * streaming passes reads 8 B per row of keys, and 4 B per row of view under a program.
+ *
+ * rag_index_facet_counts: out_counts_dev (int64 [n_codes + 1], device; zeroed by the call)
+ * [c] = the eligible rows whose code of tag field `field`, (tag >> 16 field) & 0xFFFF, equals c,
+ * 0 <= c <= n_codes. A stored code above n_codes is not counted and indexes nothing. field is 0
+ * or 1 and 0 <= n_codes <= 65535, else RAG_ERANGE. Exact for every n_codes (bins in LDS up to
+ * 8192 of them, in global memory above). One streaming pass: 4 B per row of tags, and 4 B per
+ * row of view under a program.
+ *
+ * rag_index_select_rows_from: rag_index_select_rows_view restricted to rows >= row0 (with
+ * progs_dev == NULL: every such row), *out_n_dev counting the matches at or after row0.
+ * row0 < 0 is RAG_EINVAL; row0 >= count selects nothing. Reads only the chunks from row0's on.
+ * No reference counterpart: the reference never scrolls, orders or facets. */
+#define RAG_ORDER_MAX 4096
+#define RAG_ORDER_DESC 1
+int rag_index_order_rows(rag_index_t* index, const uint32_t* progs_dev, int64_t words, int col,
+                         int flags, int64_t lo, int64_t hi, int limit, int64_t* out_keys_dev,
+                         int64_t* out_rows_dev, int64_t* out_n_dev, void* stream);
+int rag_index_facet_counts(rag_index_t* index, const uint32_t* progs_dev, int64_t words, int field,
+                           int n_codes, int64_t* out_counts_dev, void* stream);
+int rag_index_select_rows_from(rag_index_t* index, const uint32_t* progs_dev, int64_t words,
+                               int64_t row0, int64_t* out_rows_dev, int64_t cap,
+                               int64_t* out_n_dev, void* stream);
+
 /* Exactness bookkeeping (tests, bench): tier1 / tier2 = number of queries, since the index
  * was created, whose top-k was certified by the list re-scoring fallback / needed the second
  * pass over the shard (all other queries passed the error-bound check directly).
