@@ -121,6 +121,31 @@ int with_dim(int dim, F&& f) {
   return fail(RAG_EINVAL, "unsupported dim (built: 384, 1024)");
 }
 
+// The scan copies an index may keep beside its fp16 rows (dim 384, fp16 storage; prep_kernels.hip
+// "int8 scan copy", "6-bit scan copy"), and the copy a search pass streams (kNoCopy: the fp16
+// rows themselves). A copy is its image and its per-row (scale, error) meta, both over
+// cap_rows / 16 + 1 tiles (the prescans walk tile pairs; the 6-bit image holds whole pairs)
+enum CopyKind : int { kNoCopy = -1, kCopy8 = 0, kCopy6 = 1 };
+constexpr int kCopies = 2;
+struct ScanCopy {
+  char* data = nullptr;
+  float* meta = nullptr;
+};
+
+// ... and a copy kind as its device format (prep_kernels.hip Copy8 / Copy6), read by the lambda
+// as typename decltype(c)::type
+struct Copy8;
+struct Copy6;
+template <typename T>
+struct type_tag {
+  using type = T;
+};
+template <typename F>
+auto with_copy(CopyKind kind, F&& f) {
+  if (kind == kCopy6) return f(type_tag<Copy6>{});
+  return f(type_tag<Copy8>{});
+}
+
 // The slot (Workspace, ViewSlot, SetSlot) a call on stream `st` takes: the one bound to `st`,
 // else the first unused one. Neither: nullptr, every slot being bound to another stream whose
 // last call may still be running; `lru` is the least recently used one, for the caller to wait
@@ -189,19 +214,14 @@ struct rag_index {
   // rescoring reads — Qdrant's default Float32 datatype
   int storage = RAG_STORE_FP16;
   float* rows32 = nullptr;
-  // int8 scan copy (dim 384, fp16 storage; prep_kernels.hip): the tile16x64 image and the
-  // per-row (scale, error) meta, both over cap_rows / 16 + 1 tiles (the prescan walks tile
-  // pairs); rebuilt from the stored fp16 rows after every write of `corpus` (requant)
-  char* c8 = nullptr;
-  float* meta8 = nullptr;
-  // 6-bit scan copy (prep_kernels.hip "pair6"), kept only where it is used: capacity at least
-  // RAG_PRESCAN6_MIN_ROWS, or mode RAG_PRESCAN_ALWAYS6 set (ensure_copy6). Whole pairs of
-  // tiles over cap_rows / 16 + 1 tiles, and its own (scale, error) meta; rebuilt with the int8 one
-  char* c6 = nullptr;
-  float* meta6 = nullptr;
+  // scan copies, by CopyKind: the int8 one wherever the index can keep one (dim 384, fp16
+  // storage), the 6-bit one only where it is used: capacity at least RAG_PRESCAN6_MIN_ROWS, or
+  // mode RAG_PRESCAN_ALWAYS6 set (ensure_copy6). Every copy kept is rebuilt from the stored fp16
+  // rows after every write of `corpus` (requant)
+  ragmi::ScanCopy copy[ragmi::kCopies];
   int prescan = 1;        // rag_index_set_prescan: 0 off, 1 auto, 2 always (int8), 3 always 6-bit
-  int64_t prescan_passes = 0;   // passes that streamed a prescan copy (rag_index_prescan_passes)
-  int64_t prescan6_passes = 0;  // those over the 6-bit copy (rag_index_prescan6_passes)
+  // passes that streamed each copy (rag_index_prescan_passes: their sum; _prescan6_passes)
+  int64_t copy_passes[ragmi::kCopies] = {};
   int n_cu = 256;
   int max_wgs = 0;        // scan workgroups at full occupancy
   int scan_wgs = 0;       // D <= 384 scan grid cap: 3/4 of the CUs (scan_grid)
@@ -257,7 +277,7 @@ inline int ensure_stage(rag_index* h, size_t bytes) {
 
 // ---- functions that cross a unit boundary (not in the library's dynamic symbols) ----
 #pragma GCC visibility push(hidden)
-// index_search.hip: a new handle's workspaces (dim, groups, max_wgs, c8 set), one hipMalloc per
+// index_search.hip: a new handle's workspaces (dim, groups, max_wgs, copies set), one hipMalloc per
 // buffer in the tables' order; their release; the shard set's id remap (remap_ids_kernel)
 hipError_t alloc_workspaces(rag_index* h);
 void free_workspaces(rag_index* h);

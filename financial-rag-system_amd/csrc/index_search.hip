@@ -78,9 +78,9 @@ std::array<WsBuf, 22> ws_buffers(const rag_index* h, Workspace& w) {
           ws_buf(w.t2_s, G * Q * kRescanMaxWG * 32 * 4),
           ws_buf(w.t2_i, G * Q * kRescanMaxWG * 32 * 4),
           ws_buf(w.t2_tk, 64, true),
-          ws_buf(w.qfrag8, h->c8 ? 4 * (dim / 64) * 64 * 16 : 0),
-          ws_buf(w.qp8, h->c8 ? Q * 4 * 4 : 0),
-          ws_buf(w.eps8, h->c8 ? Q * 4 : 0)};
+          ws_buf(w.qfrag8, h->copy[kCopy8].data ? 4 * (dim / 64) * 64 * 16 : 0),
+          ws_buf(w.qp8, h->copy[kCopy8].data ? Q * 4 * 4 : 0),
+          ws_buf(w.eps8, h->copy[kCopy8].data ? Q * 4 : 0)};
 }
 
 // qprep's extra error-bound term for fp32 storage (prep_kernels.hip qprep_kernel): the exact
@@ -191,36 +191,41 @@ void launch_prep_seed(rag_index* h, Workspace& w, const float* q, int Bq, const 
 // 1.03x; DESIGN.md "int8 prescan"); below that a step is launch-bound and the wider
 // certificate band (tier 1 for a sixth to a third of the queries) buys nothing.
 bool use_prescan(const rag_index* h, int k) {
-  return h->c8 && RAG_PRESCAN_ROUTES(h->prescan, h->dim, h->storage, k, h->count);
+  return h->copy[kCopy8].data && RAG_PRESCAN_ROUTES(h->prescan, h->dim, h->storage, k, h->count);
 }
 
 // ... and does it scan the 6-bit copy instead? Only where the index keeps one (capacity from
 // RAG_PRESCAN6_MIN_ROWS, or mode RAG_PRESCAN_ALWAYS6 set). Auto: from RAG_PRESCAN6_MIN_ROWS
 // rows
 bool use_prescan6(const rag_index* h, int k) {
-  return h->c6 && RAG_PRESCAN6_ROUTES(h->prescan, h->dim, h->storage, k, h->count);
+  return h->copy[kCopy6].data && RAG_PRESCAN6_ROUTES(h->prescan, h->dim, h->storage, k, h->count);
 }
 
-// Query prep and seeds of a prescan pass (`six`: over the 6-bit copy): qprep's outputs plus the
-// int8 planes (qprep8_kernel), then launch_seed's sample of the shard scored with the prescan's
-// own upper bound u (sample_kernel_i8 / sample_kernel_i6) and thresh_kernel on it
+// The copy a k <= RAG_MAX_K pass of `h` streams: none (the fp16 rows), the int8 or the 6-bit one
+CopyKind pass_copy(const rag_index* h, int k) {
+  if (!use_prescan(h, k)) return kNoCopy;
+  return use_prescan6(h, k) ? kCopy6 : kCopy8;
+}
+
+// Query prep and seeds of a prescan pass over copy `kind`: qprep's outputs plus the int8 planes
+// (qprep8_kernel), then launch_seed's sample of the shard scored with that copy's own upper
+// bound u (sample_kernel_q) and thresh_kernel on it
 template <int D>
 void launch_prep8(rag_index* h, Workspace& w, const float* q, int Bq, const uint32_t* filt,
-                  const uint32_t* tags, hipStream_t st, bool six = false) {
+                  const uint32_t* tags, hipStream_t st, CopyKind kind) {
   qprep8_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(q, Bq, filt, w.qn, w.qfrag, w.filt, w.eps,
                                                   w.qfrag8, w.qp8, w.eps8);
   const int nt = (int)((h->count + 15) / 16);
   if (nt == 0) return;   // the scan visits no tile; seeds are never read
   const int n_sample = seed_sample(nt, kMaxSample);
   with_filter(filt, [&](auto f) {
-    if (six)
-      sample_kernel_i6<D, decltype(f)::value><<<dim3((n_sample + 7) / 8), dim3(256), 0, st>>>(
-          h->c6, h->meta6, tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
-          (int)h->count, nt, n_sample, w.smax);
-    else
-      sample_kernel_i8<D, decltype(f)::value><<<dim3((n_sample + 7) / 8), dim3(256), 0, st>>>(
-          h->c8, h->meta8, tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
-          (int)h->count, nt, n_sample, w.smax);
+    with_copy(kind, [&](auto c) {
+      sample_kernel_q<D, decltype(f)::value, typename decltype(c)::type>
+          <<<dim3((n_sample + 7) / 8), dim3(256), 0, st>>>(
+              h->copy[kind].data, h->copy[kind].meta, tags, w.filt,
+              reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, (int)h->count, nt, n_sample,
+              w.smax);
+    });
   });
   thresh_kernel<kMaxSample><<<dim3(kQ, 1), dim3(256), 0, st>>>(w.smax, n_sample, w.eps8, w.seed);
 }
@@ -240,7 +245,7 @@ int max_wgs_on(const rag_index* h, int cus) { return partitioned(h, cus) ? 2 * c
 // list work is paid by 768 waves instead of 2048 (select merges that many fewer lists), and
 // the free CUs take the other streams' query prep, sampling and select beside the scan
 // instead of behind it. RAGMI_SCAN_WGS overrides the cap (diagnostic A/B).
-int scan_grid(const rag_index* h, int cus, bool filtered, bool i8, bool i6 = false) {
+int scan_grid(const rag_index* h, int cus, bool filtered, CopyKind copy) {
   static ragmi::Knob k_wgs("RAGMI_SCAN_WGS");
   const int wg_env = k_wgs.get(0) > 0 ? std::max(8, k_wgs.get(0)) : 0;
   const bool part = partitioned(h, cus);
@@ -259,10 +264,10 @@ int scan_grid(const rag_index* h, int cus, bool filtered, bool i8, bool i6 = fal
   // top-k and bound arithmetic no longer hide under the loads): one workgroup on EVERY CU,
   // 10M rows 59.2K qps at 192 workgroups, 62.4K at 224, 63.6K at 256
   const int wg_cap = wg_env ? wg_env
-                     : (filtered && !i8) ? max_wgs
+                     : (filtered && copy == kNoCopy) ? max_wgs
                      : part ? cus
-                     : i6 ? h->n_cu
-                          : h->scan_wgs;
+                     : copy == kCopy6 ? h->n_cu
+                                      : h->scan_wgs;
   const int64_t n_tiles = (h->count + 15) / 16;
   const int grid = (int)std::min<int64_t>(std::min(max_wgs, wg_cap),
                                           std::max<int64_t>(1, (n_tiles + 3) / 4));
@@ -286,21 +291,17 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   const int Bq = a.Bq;
   // Bq <= 32 * h->groups queries: `groups` query groups of 32 (one for D <= 384)
   const int groups = (Bq + kQ - 1) / kQ;
-  bool i8 = false, i6 = false;   // i8: a prescan copy is streamed; i6: the 6-bit one
-  if constexpr (D == 384) {
-    i8 = use_prescan(h, a.k);
-    i6 = i8 && use_prescan6(h, a.k);
-  }
+  CopyKind copy = kNoCopy;   // the scan copy this pass streams
+  if constexpr (D == 384) copy = pass_copy(h, a.k);
   // fused qprep + sample only in free scan order (small shards, several scans overlapping):
   // there it is +1.1% (1.25M rows, 4 in flight, profiles/r03d_fused_prep_ab.jsonl); with the
   // scans chained (>= 4M rows) its 256-thread workgroups of ~180 registers, which cannot share a
   // CU with scan workgroups, landed between a scan's workgroups and stretched the scan launch
   // (10M rows: scan 0.76 vs 0.83 of the roofline, same qps, profiles/r03i_headline_prep_ab.jsonl)
-  if (i8) {
-    ++h->prescan_passes;   // rag_index_prescan_passes (the caller holds h->mu)
-    if (i6) ++h->prescan6_passes;
+  if (copy != kNoCopy) {
+    ++h->copy_passes[copy];   // rag_index_prescan_passes (the caller holds h->mu)
     // the seed is then a lower bound of the 32nd-best u, which the prescan's thresholds compare
-    if constexpr (D == 384) launch_prep8<D>(h, w, a.q, Bq, filt, a.tags, st, i6);
+    if constexpr (D == 384) launch_prep8<D>(h, w, a.q, Bq, filt, a.tags, st, copy);
   } else if (D <= 384 && groups == 1 && fused_prep() && h->serial_scans == 0) {
     with_filter(filt, [&](auto f) {
       launch_prep_seed<D, decltype(f)::value>(h, w, a.q, Bq, filt, a.tags, st);
@@ -325,7 +326,7 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
         per_group, ((n_tiles + kLdsWaves - 1) / kLdsWaves + 7) & ~int64_t(7));
     grid = std::max(8, std::min(need, kMaxLists / kLdsWaves));
   } else {
-    grid = scan_grid(h, w.cus, filt != nullptr, i8, i6);
+    grid = scan_grid(h, w.cus, filt != nullptr, copy);
   }
   const hipStream_t caller = st;
   if (h->serial_scans == 1) {
@@ -400,16 +401,14 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
     const int rc = with_filter(filt, [&](auto f) -> int {
       constexpr bool F = decltype(f)::value;
       if constexpr (D == 384) {
-        if (i6)
-          return RAG_SCAN_GO(scan_kernel_i6<D, F>)(
-              h->c6, h->meta6, a.tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
-              (int)h->count, (int)n_tiles, w.seed, w.part_s, w.part_i, w.heads_s,
-              w.heads_i, w.heads_n);
-        if (i8)
-          return RAG_SCAN_GO(scan_kernel_i8<D, F>)(
-              h->c8, h->meta8, a.tags, w.filt, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
-              (int)h->count, (int)n_tiles, w.seed, w.part_s, w.part_i, w.heads_s, w.heads_i,
-              w.heads_n);
+        // go(the arguments the two prescan kernels share)
+        const auto with_copy_args = [&](auto&& go) {
+          return go(h->copy[copy].data, h->copy[copy].meta, a.tags, w.filt,
+                    reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, (int)h->count, (int)n_tiles,
+                    w.seed, w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n);
+        };
+        if (copy == kCopy6) return with_copy_args(RAG_SCAN_GO(scan_kernel_i6<D, F>));
+        if (copy == kCopy8) return with_copy_args(RAG_SCAN_GO(scan_kernel_i8<D, F>));
       }
       return with_scan_args(RAG_SCAN_GO(scan_kernel<D, F>), nullptr);
     });
@@ -434,12 +433,13 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   // second pass over the shard) run inside the same launch
   // (after the 6-bit prescan with the wider gather chunk: its band spans ~200 lists a query)
   with_filter(filt, [&](auto f) {
-    with_flag(i6, [&](auto six) {
+    with_flag(copy == kCopy6, [&](auto six) {
       constexpr int BL = (D == 384 && decltype(six)::value) ? kBandLists6 : kBandLists;
       select_kernel<D, decltype(f)::value, BL><<<dim3(Bq), dim3(256), 0, st>>>(
           w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, a.tags, w.filt,
-          w.qfrag, (int)h->count, w.qn, a.k, i8 ? w.eps8 : w.eps, w.seed, fb, a.id_offset,
-          a.out_s, a.out_i, a.out_packed, h->rows32, i8 ? w.eps : nullptr);
+          w.qfrag, (int)h->count, w.qn, a.k, copy != kNoCopy ? w.eps8 : w.eps, w.seed, fb,
+          a.id_offset, a.out_s, a.out_i, a.out_packed, h->rows32,
+          copy != kNoCopy ? w.eps : nullptr);
     });
   });
   // tier 2 of the certificate (rescan_kernel): returns at once unless select marked a query
@@ -750,7 +750,7 @@ int bench_scan(rag_index* h, const float* q, int B, int variant, int reps, doubl
   if (variant == 7)
     RAG_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(w.seed), 0x7f800000, kQ));
   // the production grid of an unfiltered fp16 pass on an unpartitioned stream
-  const int grid = scan_grid(h, 0, false, false);
+  const int grid = scan_grid(h, 0, false, kNoCopy);
 #ifdef RAGMI_DIAG_BUILD
   const int64_t n_tiles = (h->count + 15) / 16;
   // variant 8: the v_dot2 VALU ablation over a row-group-major copy of the corpus
@@ -765,53 +765,43 @@ int bench_scan(rag_index* h, const float* q, int B, int variant, int reps, doubl
         h->corpus, h->count, rows64.p);
     qchunk_kernel<D><<<dim3(kQ), dim3(64), 0, nullptr>>>(w.qn, qc.p);
   }
-  // variants 20 / 21 / 22 / 23 / 24: the 6-bit prescan (scan_kernel_i6) at its production grid
-  // — production, MFMA + bound only (no top-k), loads only, loads + unpack, production with
+  // variants 17 / 18 / 19: the int8 prescan (scan_kernel_i8) at its production grid —
+  // production, MFMA + bound only (no top-k), loads only. Variants 20 / 21 / 22 / 23 / 24: the
+  // 6-bit prescan (scan_kernel_i6) at its own — the same three, loads + unpack, production with
   // every seed at +inf (the top-k's fixed cost: no candidate is ever taken)
-  if (variant >= 20) {
+  if (variant >= 17) {
+    const CopyKind kind = variant >= 20 ? kCopy6 : kCopy8;
     if constexpr (D == 384) {
-      if (!h->c6) return ragmi::fail(RAG_EINVAL, "variants 20-24: index keeps no 6-bit copy");
-      launch_prep8<D>(h, w, q, std::min(B, kQ), nullptr, h->tags, nullptr, true);
+      if (!h->copy[kind].data)
+        return ragmi::fail(RAG_EINVAL, kind == kCopy6 ? "variants 20-24: index keeps no 6-bit copy"
+                                                      : "variants 17-19: index keeps no int8 copy");
+      launch_prep8<D>(h, w, q, std::min(B, kQ), nullptr, h->tags, nullptr, kind);
       if (variant == 24)
         RAG_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(w.seed), 0x7f800000, kQ));
-      const int grid = scan_grid(h, 0, false, true, true);
-      const auto go = [&](auto mode) {
-        launch_fixed<kScanBlock>(scan_kernel_i6<D, false, decltype(mode)::value>, dim3(grid), 0,
-                                 nullptr, h->c6, h->meta6, h->tags, w.filt,
-                                 reinterpret_cast<const intx4*>(w.qfrag8), w.qp8,
-                                 (int)h->count, (int)n_tiles, w.seed, w.part_s, w.part_i,
-                                 w.heads_s, w.heads_i, w.heads_n);
-      };
-      return time_launches(reps, [&]() {
-        if (variant == 20 || variant == 24) go(std::integral_constant<int, 0>{});
-        else if (variant == 21) go(std::integral_constant<int, 1>{});
-        else if (variant == 22) go(std::integral_constant<int, 2>{});
-        else go(std::integral_constant<int, 3>{});
-      }, avg_ms);
-    } else {
-      return ragmi::fail(RAG_EINVAL, "variants 20-24: dim 384 only");
-    }
-  }
-  // variants 17 / 18 / 19: the int8 prescan (scan_kernel_i8) at the production grid —
-  // production, MFMA + bound only (no top-k), loads only
-  if (variant >= 17) {
-    if constexpr (D == 384) {
-      if (!h->c8) return ragmi::fail(RAG_EINVAL, "variants 17-19: index keeps no int8 copy");
-      launch_prep8<D>(h, w, q, std::min(B, kQ), nullptr, h->tags, nullptr);
-      const auto go = [&](auto mode) {
-        launch_fixed<kScanBlock>(scan_kernel_i8<D, false, decltype(mode)::value>, dim3(grid), 0,
-                                 nullptr, h->c8, h->meta8, h->tags, w.filt,
+      const int grid = scan_grid(h, 0, false, kind);
+      const int mode = variant == 24 ? 0 : variant - (kind == kCopy6 ? 20 : 17);
+      const auto go = [&](auto kernel) {
+        launch_fixed<kScanBlock>(kernel, dim3(grid), 0, nullptr, h->copy[kind].data,
+                                 h->copy[kind].meta, h->tags, w.filt,
                                  reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, (int)h->count,
                                  (int)n_tiles, w.seed, w.part_s, w.part_i, w.heads_s, w.heads_i,
                                  w.heads_n);
       };
       return time_launches(reps, [&]() {
-        if (variant == 17) go(std::integral_constant<int, 0>{});
-        else if (variant == 18) go(std::integral_constant<int, 1>{});
-        else go(std::integral_constant<int, 2>{});
+        if (kind == kCopy8) {
+          if (mode == 0) go(scan_kernel_i8<D, false, 0>);
+          else if (mode == 1) go(scan_kernel_i8<D, false, 1>);
+          else go(scan_kernel_i8<D, false, 2>);
+        } else {
+          if (mode == 0) go(scan_kernel_i6<D, false, 0>);
+          else if (mode == 1) go(scan_kernel_i6<D, false, 1>);
+          else if (mode == 2) go(scan_kernel_i6<D, false, 2>);
+          else go(scan_kernel_i6<D, false, 3>);
+        }
       }, avg_ms);
     } else {
-      return ragmi::fail(RAG_EINVAL, "variants 17-19: dim 384 only");
+      return ragmi::fail(RAG_EINVAL, kind == kCopy6 ? "variants 20-24: dim 384 only"
+                                                    : "variants 17-19: dim 384 only");
     }
   }
 #endif
@@ -1310,7 +1300,7 @@ int rag_index_prescan_passes(rag_index_t* h, int64_t* n) {
   ragmi::clear_error();
   if (!h || !n) return ragmi::fail(RAG_EINVAL, "bad args");
   std::lock_guard<std::mutex> lk(h->mu);
-  *n = h->prescan_passes;
+  *n = h->copy_passes[ragmi::kCopy8] + h->copy_passes[ragmi::kCopy6];
   return RAG_OK;
 }
 
@@ -1318,7 +1308,7 @@ int rag_index_prescan6_passes(rag_index_t* h, int64_t* n) {
   ragmi::clear_error();
   if (!h || !n) return ragmi::fail(RAG_EINVAL, "bad args");
   std::lock_guard<std::mutex> lk(h->mu);
-  *n = h->prescan6_passes;
+  *n = h->copy_passes[ragmi::kCopy6];
   return RAG_OK;
 }
 
@@ -1330,7 +1320,7 @@ int rag_index_prescan_bounds(rag_index_t* h, const float* q, int B, const int64_
     return ragmi::fail(RAG_EINVAL, "bad prescan_bounds args (1 <= B <= 32)");
   if (n > 0x7fffffff) return ragmi::fail(RAG_ERANGE, "n too large for one call");
   std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->c8)
+  if (!h->copy[ragmi::kCopy8].data)
     return ragmi::fail(RAG_EINVAL, "index keeps no int8 scan copy (dim 384, fp16 storage only)");
   if (n == 0) return RAG_OK;
   RAG_HIP(hipSetDevice(h->device));
@@ -1339,14 +1329,13 @@ int rag_index_prescan_bounds(rag_index_t* h, const float* q, int B, const int64_
   qprep8_kernel<384><<<dim3(kQ), dim3(64), 0, nullptr>>>(q, B, nullptr, w.qn, w.qfrag, w.filt,
                                                          w.eps, w.qfrag8, w.qp8, w.eps8);
   // the bound of the copy a k = 1 pass streams in the current mode (the int8 one where none)
-  if (use_prescan6(h, 1))
-    prescan6_bounds_kernel<384><<<dim3((unsigned)n), dim3(64), 0, nullptr>>>(
-        h->c6, h->meta6, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, rows_dev, n,
-        h->count, B, out_u);
-  else
-    prescan_bounds_kernel<384><<<dim3((unsigned)n), dim3(64), 0, nullptr>>>(
-        h->c8, h->meta8, reinterpret_cast<const intx4*>(w.qfrag8), w.qp8, rows_dev, n, h->count,
-        B, out_u);
+  const ragmi::CopyKind kind = use_prescan6(h, 1) ? ragmi::kCopy6 : ragmi::kCopy8;
+  ragmi::with_copy(kind, [&](auto c) {
+    prescan_bounds_kernel<384, typename decltype(c)::type>
+        <<<dim3((unsigned)n), dim3(64), 0, nullptr>>>(
+            h->copy[kind].data, h->copy[kind].meta, reinterpret_cast<const intx4*>(w.qfrag8),
+            w.qp8, rows_dev, n, h->count, B, out_u);
+  });
   RAG_HIP(hipGetLastError());
   RAG_HIP(hipDeviceSynchronize());
   return RAG_OK;

@@ -12,56 +12,86 @@ using namespace ragmi;
 
 namespace {
 
-// Which indexes keep the int8 scan copy
+// Which indexes keep scan copies: the int8 one always, the 6-bit one from its threshold
 bool keeps_copy8(const rag_index* h) { return h->dim == 384 && h->storage == RAG_STORE_FP16; }
 
-size_t copy8_bytes(const rag_index* h, int64_t cap_rows) {
-  return (size_t)(cap_rows / 16 + 1) * (h->dim / 64) * 1024;
+// Image bytes of `tiles` tiles of a copy: dim / 64 KiB a tile for the int8 one; whole pairs of
+// tiles for the 6-bit one (an odd last tile's pair counts with its spare half)
+size_t tiles_bytes(CopyKind kind, int dim, int64_t tiles) {
+  return kind == kCopy6 ? (size_t)((tiles + 1) / 2) * ragmi::kPair6Bytes
+                        : (size_t)tiles * (dim / 64) * 1024;
 }
-size_t meta8_bytes(int64_t cap_rows) { return (size_t)(cap_rows / 16 + 1) * 32 * 4; }
+// a copy's image over cap_rows / 16 + 1 tiles (one spare: the prescans walk tile pairs), its meta
+size_t copy_bytes(CopyKind kind, int dim, int64_t cap_rows) {
+  return tiles_bytes(kind, dim, cap_rows / 16 + 1);
+}
+size_t meta_bytes(int64_t cap_rows) { return (size_t)(cap_rows / 16 + 1) * 32 * 4; }
 
-// the copy's two buffers for `cap_rows` rows, zeroed (freed by the caller's DeviceBufs on error)
-int alloc_copy8(const rag_index* h, int64_t cap_rows, DeviceBuf<char>& c8, DeviceBuf<float>& m8) {
-  if (c8.alloc(copy8_bytes(h, cap_rows)) != hipSuccess ||
-      m8.alloc(meta8_bytes(cap_rows)) != hipSuccess)
-    return ragmi::fail(RAG_ENOMEM, "hipMalloc(int8 scan copy) failed");
-  RAG_HIP(hipMemset(c8.p, 0, copy8_bytes(h, cap_rows)));
-  RAG_HIP(hipMemset(m8.p, 0, meta8_bytes(cap_rows)));
+// a copy's two buffers before the handle owns them (freed on every error return)
+struct CopyBufs {
+  DeviceBuf<char> data;
+  DeviceBuf<float> meta;
+};
+
+// the buffers of copy `kind` for `cap_rows` rows, zeroed
+int alloc_copy(CopyKind kind, int dim, int64_t cap_rows, CopyBufs& b) {
+  if (b.data.alloc(copy_bytes(kind, dim, cap_rows)) != hipSuccess ||
+      b.meta.alloc(meta_bytes(cap_rows)) != hipSuccess)
+    return ragmi::fail(RAG_ENOMEM, kind == kCopy6 ? "hipMalloc(6-bit scan copy) failed"
+                                                  : "hipMalloc(int8 scan copy) failed");
+  RAG_HIP(hipMemset(b.data.p, 0, copy_bytes(kind, dim, cap_rows)));
+  RAG_HIP(hipMemset(b.meta.p, 0, meta_bytes(cap_rows)));
   return RAG_OK;
 }
 
-// the 6-bit copy: whole pairs of tiles over the int8 copy's cap_rows / 16 + 1 tiles
-size_t copy6_bytes(int64_t cap_rows) {
-  return (size_t)((cap_rows / 16 + 2) / 2) * ragmi::kPair6Bytes;
+// The handle takes `nb` as its copy `kind`. What the copy held so far moves over first (reserve):
+// whole tiles of the old capacity, whose spare tile holds no row; for the 6-bit copy whole pairs,
+// an odd last tile's with its spare half. A copy that starts here holds no row yet.
+int grow_copy(rag_index* h, CopyKind kind, CopyBufs& nb) {
+  ScanCopy& c = h->copy[kind];
+  if (c.data) {
+    const int64_t tiles = h->cap_rows / 16;
+    RAG_HIP(hipMemcpy(nb.data.p, c.data, tiles_bytes(kind, h->dim, tiles),
+                      hipMemcpyDeviceToDevice));
+    RAG_HIP(hipMemcpy(nb.meta.p, c.meta, (size_t)tiles * 32 * 4, hipMemcpyDeviceToDevice));
+    (void)hipFree(c.data);
+    (void)hipFree(c.meta);
+  }
+  c.data = nb.data.release();
+  c.meta = nb.meta.release();
+  return RAG_OK;
 }
 
-int alloc_copy6(int64_t cap_rows, DeviceBuf<char>& c6, DeviceBuf<float>& m6) {
-  if (c6.alloc(copy6_bytes(cap_rows)) != hipSuccess ||
-      m6.alloc(meta8_bytes(cap_rows)) != hipSuccess)
-    return ragmi::fail(RAG_ENOMEM, "hipMalloc(6-bit scan copy) failed");
-  RAG_HIP(hipMemset(c6.p, 0, copy6_bytes(cap_rows)));
-  RAG_HIP(hipMemset(m6.p, 0, meta8_bytes(cap_rows)));
-  return RAG_OK;
+// copy `kind` of an index that has none, over its present capacity (creation, ensure_copy6;
+// reserve runs the same two steps around its own allocations)
+int start_copy(rag_index* h, CopyKind kind) {
+  CopyBufs b;
+  const int rc = alloc_copy(kind, h->dim, h->cap_rows, b);
+  return rc ? rc : grow_copy(h, kind, b);
+}
+
+// requant_kernel in the format of copy `kind`, over rows[i] or row0 + i, i < n
+void launch_requant(const rag_index* h, CopyKind kind, const int64_t* rows, int64_t row0,
+                    int64_t n, hipStream_t st) {
+  with_copy(kind, [&](auto c) {
+    ragmi::requant_kernel<384, typename decltype(c)::type><<<dim3((unsigned)n), dim3(64), 0, st>>>(
+        h->corpus, rows, row0, n, h->cap_rows, h->copy[kind].data, h->copy[kind].meta);
+  });
 }
 
 // The scan copies of rows[i] (device list) or row0 + i, i < n, rebuilt from the stored fp16
 // rows: enqueued on `st` right after the kernel that wrote them
 int requant(rag_index* h, const int64_t* rows, int64_t row0, int64_t n, hipStream_t st) {
-  if (!h->c8 || n <= 0) return RAG_OK;
-  ragmi::requant_kernel<384><<<dim3((unsigned)n), dim3(64), 0, st>>>(
-      h->corpus, rows, row0, n, h->cap_rows, h->c8, h->meta8);
-  if (h->c6)
-    ragmi::requant6_kernel<384><<<dim3((unsigned)n), dim3(64), 0, st>>>(
-        h->corpus, rows, row0, n, h->cap_rows, h->c6, h->meta6);
+  if (!h->copy[kCopy8].data || n <= 0) return RAG_OK;
+  for (int k = 0; k < kCopies; ++k)
+    if (h->copy[k].data) launch_requant(h, (CopyKind)k, rows, row0, n, st);
   RAG_HIP(hipGetLastError());
   return RAG_OK;
 }
 
-// the whole 6-bit copy from the stored rows (a copy that starts late: reserve, ensure_copy6)
-int requant6_all(rag_index* h) {
-  if (h->count > 0)
-    ragmi::requant6_kernel<384><<<dim3((unsigned)h->count), dim3(64), 0, nullptr>>>(
-        h->corpus, nullptr, 0, h->count, h->cap_rows, h->c6, h->meta6);
+// a whole copy from the stored rows (a copy that starts late: reserve, ensure_copy6); synchronous
+int rebuild_copy(rag_index* h, CopyKind kind) {
+  if (h->count > 0) launch_requant(h, kind, nullptr, 0, h->count, nullptr);
   RAG_HIP(hipGetLastError());
   RAG_HIP(hipDeviceSynchronize());
   return RAG_OK;
@@ -375,16 +405,11 @@ int ragmi::acquire_view(rag_index* h, hipStream_t st, uint32_t** view) {
 }
 
 int ragmi::ensure_copy6(rag_index* h) {
-  if (h->c6 || !keeps_copy8(h)) return RAG_OK;
+  if (h->copy[kCopy6].data || !keeps_copy8(h)) return RAG_OK;
   RAG_HIP(hipSetDevice(h->device));
-  DeviceBuf<char> c6;
-  DeviceBuf<float> m6;
-  const int rc = alloc_copy6(h->cap_rows, c6, m6);
-  if (rc) return rc;
   RAG_HIP(hipDeviceSynchronize());   // no writer of the rows in flight
-  h->c6 = c6.release();
-  h->meta6 = m6.release();
-  return requant6_all(h);
+  const int rc = start_copy(h, kCopy6);
+  return rc ? rc : rebuild_copy(h, kCopy6);
 }
 
 extern "C" {
@@ -420,25 +445,11 @@ int rag_index_create_ex(int dim, int64_t capacity_rows, int device, int storage,
     return rc;
   }
   if (keeps_copy8(h)) {
-    DeviceBuf<char> c8;
-    DeviceBuf<float> m8;
-    rc = alloc_copy8(h, h->cap_rows, c8, m8);
+    rc = start_copy(h, kCopy8);
+    if (!rc && h->cap_rows >= RAG_PRESCAN6_MIN_ROWS) rc = start_copy(h, kCopy6);
     if (rc) {
       rag_index_destroy(h);
       return rc;
-    }
-    h->c8 = c8.release();
-    h->meta8 = m8.release();
-    if (h->cap_rows >= RAG_PRESCAN6_MIN_ROWS) {
-      DeviceBuf<char> c6;
-      DeviceBuf<float> m6;
-      rc = alloc_copy6(h->cap_rows, c6, m6);
-      if (rc) {
-        rag_index_destroy(h);
-        return rc;
-      }
-      h->c6 = c6.release();
-      h->meta6 = m6.release();
     }
   }
   if (storage == RAG_STORE_FP32) {
@@ -499,10 +510,10 @@ int rag_index_destroy(rag_index_t* h) {
   for (auto* k : h->keys)
     if (k) (void)hipFree(k);
   if (h->rows32) (void)hipFree(h->rows32);
-  if (h->c8) (void)hipFree(h->c8);
-  if (h->meta8) (void)hipFree(h->meta8);
-  if (h->c6) (void)hipFree(h->c6);
-  if (h->meta6) (void)hipFree(h->meta6);
+  for (auto& c : h->copy) {
+    if (c.data) (void)hipFree(c.data);
+    if (c.meta) (void)hipFree(c.meta);
+  }
   if (h->stage) (void)hipFree(h->stage);
   for (auto& v : h->views)
     if (v.p) (void)hipFree(v.p);
@@ -530,20 +541,14 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
     if (n32.alloc(b32) != hipSuccess) return ragmi::fail(RAG_ENOMEM, "hipMalloc(rows32) failed");
     RAG_HIP(hipMemset(n32.p, 0, b32));
   }
-  DeviceBuf<char> n8;
-  DeviceBuf<float> nm8;
-  if (h->c8) {
-    rc = alloc_copy8(h, cap, n8, nm8);
-    if (rc) return rc;
-  }
-  // the 6-bit copy grows with the rest, and starts here when the capacity reaches its threshold
-  DeviceBuf<char> n6;
-  DeviceBuf<float> nm6;
-  const bool start6 = !h->c6 && keeps_copy8(h) && cap >= RAG_PRESCAN6_MIN_ROWS;
-  if (h->c6 || start6) {
-    rc = alloc_copy6(cap, n6, nm6);
-    if (rc) return rc;
-  }
+  // every copy the index keeps grows with the rest, and the 6-bit one starts here when the
+  // capacity reaches its threshold
+  CopyBufs ncopy[kCopies];
+  const bool start6 =
+      !h->copy[kCopy6].data && keeps_copy8(h) && cap >= RAG_PRESCAN6_MIN_ROWS;
+  for (int k = 0; k < kCopies; ++k)
+    if (h->copy[k].data || (k == kCopy6 && start6))
+      if ((rc = alloc_copy((CopyKind)k, h->dim, cap, ncopy[k]))) return rc;
   RAG_HIP(hipDeviceSynchronize());
   // the key columns regrow with the tags: old rows keep their keys, new rows hold ABSENT
   DeviceBuf<int64_t> nk[RAG_KEYS_MAX_COLS];
@@ -555,30 +560,9 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
   if (n32.p)
     RAG_HIP(hipMemcpy(n32.p, h->rows32, (size_t)h->cap_rows * h->dim * 4,
                       hipMemcpyDeviceToDevice));
-  if (n8.p) {
-    // whole tiles of the old capacity (its spare tile holds no row)
-    RAG_HIP(hipMemcpy(n8.p, h->c8, (size_t)(h->cap_rows / 16) * (h->dim / 64) * 1024,
-                      hipMemcpyDeviceToDevice));
-    RAG_HIP(hipMemcpy(nm8.p, h->meta8, (size_t)(h->cap_rows / 16) * 32 * 4,
-                      hipMemcpyDeviceToDevice));
-    (void)hipFree(h->c8);
-    (void)hipFree(h->meta8);
-    h->c8 = n8.release();
-    h->meta8 = nm8.release();
-  }
-  if (h->c6) {
-    // whole pairs of the old capacity; an odd last tile's pair is copied with its spare half
-    RAG_HIP(hipMemcpy(n6.p, h->c6, (size_t)((h->cap_rows / 16 + 1) / 2) * ragmi::kPair6Bytes,
-                      hipMemcpyDeviceToDevice));
-    RAG_HIP(hipMemcpy(nm6.p, h->meta6, (size_t)(h->cap_rows / 16) * 32 * 4,
-                      hipMemcpyDeviceToDevice));
-    (void)hipFree(h->c6);
-    (void)hipFree(h->meta6);
-  }
-  if (n6.p) {
-    h->c6 = n6.release();
-    h->meta6 = nm6.release();
-  }
+  for (int k = 0; k < kCopies; ++k)
+    if (ncopy[k].data.p)
+      if ((rc = grow_copy(h, (CopyKind)k, ncopy[k]))) return rc;
   (void)hipFree(h->corpus);
   (void)hipFree(h->tags);
   if (h->rows32) (void)hipFree(h->rows32);
@@ -590,7 +574,7 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
     h->keys[c] = nk[c].release();
   }
   h->cap_rows = cap;
-  if (start6) return requant6_all(h);   // built from the rows just moved
+  if (start6) return rebuild_copy(h, kCopy6);   // built from the rows just moved
   return RAG_OK;
 }
 

@@ -1,7 +1,8 @@
 // prep_kernels.hip — the storage layout of the in-HBM flat cosine index for gfx950 (MI355X)
 // and the kernels that write into it: ingest (upsert_kernel) and query prep (qprep_*); then
-// the int8 scan copy of the rows (dim 384, fp16 storage): its layout, the one quantiser
-// (quantise_row / requant_kernel), the upper bound u_bound and the int8 query prep (qprep8_*).
+// the scan copies of the rows (dim 384, fp16 storage): the int8 and the 6-bit layout, the int8
+// query prep (qprep8_*) and the upper bound u_bound, the two copy formats (Copy8, Copy6) and the
+// one quantiser over them (quantise_row / requant_kernel).
 // First of the device headers index_search.hip includes; the scan, seed, certify, merge, large-k,
 // re-select and row headers after it all read this layout.
 //
@@ -174,69 +175,12 @@ __device__ __forceinline__ int64_t tile8_byte(int64_t row, int c) {
 // first float of row `row`'s scale in meta (its error: + 16)
 __device__ __forceinline__ int64_t meta_slot(int64_t row) { return (row >> 4) * 32 + (row & 15); }
 
-// The one quantiser of a stored row, by one wave: lane c < D/8 passes piece c (x: the fp16
-// values widened, dims 8c .. 8c+7), other lanes zeros. Max-abs scale s = max|x| / 127, bytes
-// rint(x / s) in [-127, 127]; err = ||x - s*bytes||_2 measured in fp64 and rounded up to fp32.
-// The zero row gives scale 0, bytes 0, error 0. Every lane returns the same s and err.
-__device__ __forceinline__ uint2 quantise_row(const float (&x)[8], float& s, float& err) {
-  float m = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[j]));
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-  s = m / 127.0f;
-  uint32_t w[2] = {0u, 0u};
-  double e2 = 0.0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float v = s > 0.f ? rintf(x[j] / s) : 0.f;
-    v = fminf(fmaxf(v, -127.f), 127.f);
-    const double dd = (double)x[j] - (double)s * (double)v;
-    e2 = fma(dd, dd, e2);
-    w[j >> 2] |= ((uint32_t)(int)v & 0xffu) << (8 * (j & 3));
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) e2 += __shfl_xor(e2, d, 64);
-  // fp64 sum of <= D squares: relative error << 2^-40; 2^-20 covers it and the fp32 RNE
-  err = e2 > 0.0 ? (float)(sqrt(e2) * (1.0 + 0x1p-20)) : 0.f;
-  return uint2{w[0], w[1]};
-}
-
-// rows[i] (rows != nullptr) or row0 + i, i < n: the int8 copy and meta of the stored fp16 row.
-// One wave per row; launched after every kernel that writes `corpus`, on the same stream.
-template <int D>
-__global__ __launch_bounds__(64) void requant_kernel(const half8* __restrict__ corpus,
-                                                     const int64_t* __restrict__ rows,
-                                                     int64_t row0, int64_t n, int64_t cap_rows,
-                                                     char* __restrict__ c8,
-                                                     float* __restrict__ meta) {
-  static_assert(D / 8 <= 64, "one piece per lane");
-  const int64_t i = blockIdx.x;
-  if (i >= n) return;
-  const int lane = threadIdx.x;
-  const int64_t row = rows ? rows[i] : row0 + i;
-  if (row < 0 || row >= cap_rows) return;   // never read or write out of bounds
-  float x[8];
-  const bool has = lane < D / 8;
-  half8 h = {};
-  if (has) h = corpus[tile_slot<D>(row, lane)];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = has ? (float)h[j] : 0.f;
-  float s, err;
-  const uint2 b = quantise_row(x, s, err);
-  if (has) *reinterpret_cast<uint2*>(c8 + tile8_byte<D>(row, lane)) = b;
-  if (lane == 0) {
-    meta[meta_slot(row)] = s;
-    meta[meta_slot(row) + 16] = err;
-  }
-}
-
 // ----------------------------------------------------------------------------------------
 // 6-bit scan copy (D = 384, fp16 storage, the largest shards). A third image of
 // the corpus: per row and dimension one integer v in [-31, 31] (six bits, two's complement),
 // with the row's own scale s_r = max|c| / 31 and measured error E_r = ||c - s_r v||_2. The scan
 // reads each value as the int8 4 v (its six bits are the byte's top six: no sign extension, no
-// bias), so `meta6` (meta_slot, as the int8 copy's) holds s_r / 4, exact, and E_r.
+// bias), so its meta (meta_slot, as the int8 copy's) holds s_r / 4, exact, and E_r.
 // Layout "pair6": the unit is a PAIR of tiles (32 rows, 9216 B, nine 1-KiB wave loads). Lane
 // l = h*16 + r of the wave owns row r and k-group h of both tiles: 36 dwords, dword g of lane l
 // at byte
@@ -248,7 +192,6 @@ __global__ __launch_bounds__(64) void requant_kernel(const half8* __restrict__ c
 // unpack6 rebuilds the four A-fragment dwords (bytes 4 v) in nine bitwise ops.
 // ----------------------------------------------------------------------------------------
 constexpr int kPair6Bytes = 9216;
-constexpr int kQ6Max = 31;     // |v| <= 31
 
 // dword index, within the lane's 36, of part c of k-step s of tile u of a pair
 __host__ __device__ constexpr int pair6_dword(int u, int s, int c) { return 18 * u + 3 * s + c; }
@@ -263,71 +206,6 @@ __device__ __forceinline__ intx4 unpack6(uint32_t p0, uint32_t p1, uint32_t p2) 
   const uint32_t x = ((p0 << 2) & 0x0c0c0c0cu) | ((p1 << 4) & 0x30303030u) |
                      ((p2 << 6) & 0xc0c0c0c0u);
   return intx4{(int)(p0 & 0xfcfcfcfcu), (int)(p1 & 0xfcfcfcfcu), (int)(p2 & 0xfcfcfcfcu), (int)x};
-}
-
-// The one 6-bit quantiser of a stored row, by one wave, as quantise_row: lane c < D/8 passes
-// piece c. Scale s = max|x| / 31, v = rint(x / s) in [-31, 31]; returns the eight values as
-// six-bit two's complement fields, one per byte; err = ||x - s v||_2 measured in fp64 and
-// rounded up. The zero row gives scale 0, v = 0, error 0.
-__device__ __forceinline__ uint2 quantise_row6(const float (&x)[8], float& s, float& err) {
-  float m = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[j]));
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-  s = m / (float)kQ6Max;
-  uint32_t w[2] = {0u, 0u};
-  double e2 = 0.0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float v = s > 0.f ? rintf(x[j] / s) : 0.f;
-    v = fminf(fmaxf(v, -(float)kQ6Max), (float)kQ6Max);
-    const double dd = (double)x[j] - (double)s * (double)v;
-    e2 = fma(dd, dd, e2);
-    w[j >> 2] |= ((uint32_t)(int)v & 0x3fu) << (8 * (j & 3));
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) e2 += __shfl_xor(e2, d, 64);
-  err = e2 > 0.0 ? (float)(sqrt(e2) * (1.0 + 0x1p-20)) : 0.f;
-  return uint2{w[0], w[1]};
-}
-
-// requant_kernel's twin for the 6-bit copy: rows[i] or row0 + i, one wave per row
-template <int D>
-__global__ __launch_bounds__(64) void requant6_kernel(const half8* __restrict__ corpus,
-                                                      const int64_t* __restrict__ rows,
-                                                      int64_t row0, int64_t n, int64_t cap_rows,
-                                                      char* __restrict__ c6,
-                                                      float* __restrict__ meta) {
-  static_assert(D / 8 <= 64, "one piece per lane");
-  const int64_t i = blockIdx.x;
-  if (i >= n) return;
-  const int lane = threadIdx.x;
-  const int64_t row = rows ? rows[i] : row0 + i;
-  if (row < 0 || row >= cap_rows) return;   // never read or write out of bounds
-  float x[8];
-  const bool has = lane < D / 8;
-  half8 h = {};
-  if (has) h = corpus[tile_slot<D>(row, lane)];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = has ? (float)h[j] : 0.f;
-  float s, err;
-  const uint2 b = quantise_row6(x, s, err);
-  // pieces 2m, 2m + 1 are the sixteen dims of one (k-step, k-group): the even lane packs both
-  const uint32_t o0 = __shfl_xor(b.x, 1, 64), o1 = __shfl_xor(b.y, 1, 64);
-  if (has && (lane & 1) == 0) {
-    const int ks = lane >> 3, kg = (lane >> 1) & 3;
-    const int l = kg * 16 + (int)(row & 15), u = (int)(row >> 4) & 1;
-    const uint32_t p[3] = {(b.x << 2) | (o1 & 0x03030303u), (b.y << 2) | ((o1 >> 2) & 0x03030303u),
-                           (o0 << 2) | ((o1 >> 4) & 0x03030303u)};
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      *reinterpret_cast<uint32_t*>(c6 + pair6_byte(row >> 5, pair6_dword(u, ks, c), l)) = p[c];
-  }
-  if (lane == 0) {
-    meta[meta_slot(row)] = 0.25f * s;   // the scale of the bytes 4 v
-    meta[meta_slot(row) + 16] = err;
-  }
 }
 
 // ----------------------------------------------------------------------------------------
@@ -468,6 +346,131 @@ __global__ __launch_bounds__(64) void qprep_kernel(const float* __restrict__ q, 
                                                    float* __restrict__ eps,
                                                    double store_eps = 0.0) {
   qprep_slot<D>(q, B, blockIdx.x, threadIdx.x, filt_in, qn, qfrag, filt, eps, store_eps, true);
+}
+
+// ----------------------------------------------------------------------------------------
+// The two scan copy formats. A format states what differs between the copies and nothing else:
+// the quantiser's range, the scale its scan reads, how a quantised row is stored, how a tile's
+// upper bounds u are produced from memory (tile_u_at, defined in scan_kernels.hip beside the
+// tile arithmetic it uses) and the form of the bound. Everything else — the quantiser, the
+// rebuild, the seed sample, the diagnostic bounds — is written once over a format.
+// ----------------------------------------------------------------------------------------
+template <int D>
+struct Query8;   // scan_kernels.hip: the int8 query batch of a wave
+
+struct Copy8 {
+  static constexpr int kQMax = 127;   // |byte| <= 127
+  static __device__ __forceinline__ float stored_scale(float s) { return s; }
+  // lane c < D/8 (`has`) holds the eight bytes of piece c of `row`
+  template <int D>
+  static __device__ __forceinline__ void store_row(char* __restrict__ data, int64_t row, int lane,
+                                                   bool has, uint2 b) {
+    if (has) *reinterpret_cast<uint2*>(data + tile8_byte<D>(row, lane)) = b;
+  }
+  static __device__ __forceinline__ float bound(int hi, int lo, float s_r, float e_r, float sq,
+                                                float A, float C) {
+    return u_bound(hi, lo, s_r, e_r, sq, A, C);
+  }
+  // u of tile t of the copy against the 32 queries, by one wave
+  template <int D>
+  static __device__ __forceinline__ void tile_u_at(const char* __restrict__ data,
+                                                   const float* __restrict__ meta, int64_t t,
+                                                   const Query8<D>& q, int lane, floatx4& u0,
+                                                   floatx4& u1);
+};
+
+struct Copy6 {
+  static constexpr int kQMax = 31;    // |v| <= 31
+  // the scale of the bytes 4 v the scan multiplies (exact)
+  static __device__ __forceinline__ float stored_scale(float s) { return 0.25f * s; }
+  // b: the eight values as six-bit fields, one per byte. Pieces 2m, 2m + 1 are the sixteen dims
+  // of one (k-step, k-group): the even lane packs both (every lane of the wave calls)
+  template <int D>
+  static __device__ __forceinline__ void store_row(char* __restrict__ data, int64_t row, int lane,
+                                                   bool has, uint2 b) {
+    static_assert(D == 384, "pair6 layout");
+    const uint32_t o0 = __shfl_xor(b.x, 1, 64), o1 = __shfl_xor(b.y, 1, 64);
+    if (has && (lane & 1) == 0) {
+      const int ks = lane >> 3, kg = (lane >> 1) & 3;
+      const int l = kg * 16 + (int)(row & 15), u = (int)(row >> 4) & 1;
+      const uint32_t p[3] = {(b.x << 2) | (o1 & 0x03030303u), (b.y << 2) | ((o1 >> 2) & 0x03030303u),
+                             (o0 << 2) | ((o1 >> 4) & 0x03030303u)};
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<uint32_t*>(data + pair6_byte(row >> 5, pair6_dword(u, ks, c), l)) = p[c];
+    }
+  }
+  static __device__ __forceinline__ float bound(int hi, int lo, float s_r, float e_r, float sq,
+                                                float A, float C) {
+    return u_bound6(hi, lo, s_r, e_r, sq, A, C);
+  }
+  template <int D>
+  static __device__ __forceinline__ void tile_u_at(const char* __restrict__ data,
+                                                   const float* __restrict__ meta, int64_t t,
+                                                   const Query8<D>& q, int lane, floatx4& u0,
+                                                   floatx4& u1);
+};
+
+// The one quantiser of a stored row, by one wave: lane c < D/8 passes piece c (x: the fp16
+// values widened, dims 8c .. 8c+7), other lanes zeros. Max-abs scale s = max|x| / kQMax, values
+// v = rint(x / s) in [-kQMax, kQMax], returned as two's complement fields of the format's width,
+// one per byte; err = ||x - s v||_2 measured in fp64 and rounded up to fp32. The zero row gives
+// scale 0, v = 0, error 0. Every lane returns the same s and err.
+template <typename Copy>
+__device__ __forceinline__ uint2 quantise_row(const float (&x)[8], float& s, float& err) {
+  constexpr float kMax = (float)Copy::kQMax;
+  constexpr uint32_t kField = 2u * Copy::kQMax + 1u;   // 0xff, 0x3f
+  float m = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[j]));
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+  s = m / kMax;
+  uint32_t w[2] = {0u, 0u};
+  double e2 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float v = s > 0.f ? rintf(x[j] / s) : 0.f;
+    v = fminf(fmaxf(v, -kMax), kMax);
+    const double dd = (double)x[j] - (double)s * (double)v;
+    e2 = fma(dd, dd, e2);
+    w[j >> 2] |= ((uint32_t)(int)v & kField) << (8 * (j & 3));
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) e2 += __shfl_xor(e2, d, 64);
+  // fp64 sum of <= D squares: relative error << 2^-40; 2^-20 covers it and the fp32 RNE
+  err = e2 > 0.0 ? (float)(sqrt(e2) * (1.0 + 0x1p-20)) : 0.f;
+  return uint2{w[0], w[1]};
+}
+
+// rows[i] (rows != nullptr) or row0 + i, i < n: the copy (`data`, `meta`) of the stored fp16 row
+// in format Copy. One wave per row; launched after every kernel that writes `corpus`, on the
+// same stream.
+template <int D, typename Copy>
+__global__ __launch_bounds__(64) void requant_kernel(const half8* __restrict__ corpus,
+                                                     const int64_t* __restrict__ rows,
+                                                     int64_t row0, int64_t n, int64_t cap_rows,
+                                                     char* __restrict__ data,
+                                                     float* __restrict__ meta) {
+  static_assert(D / 8 <= 64, "one piece per lane");
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  const int lane = threadIdx.x;
+  const int64_t row = rows ? rows[i] : row0 + i;
+  if (row < 0 || row >= cap_rows) return;   // never read or write out of bounds
+  float x[8];
+  const bool has = lane < D / 8;
+  half8 h = {};
+  if (has) h = corpus[tile_slot<D>(row, lane)];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = has ? (float)h[j] : 0.f;
+  float s, err;
+  const uint2 b = quantise_row<Copy>(x, s, err);
+  Copy::template store_row<D>(data, row, lane, has, b);
+  if (lane == 0) {
+    meta[meta_slot(row)] = Copy::stored_scale(s);
+    meta[meta_slot(row) + 16] = err;
+  }
 }
 
 }  // namespace ragmi

@@ -572,29 +572,130 @@ __device__ __forceinline__ void query8_load(Query8<D>& q, const intx4* __restric
   q.sq1 = p1.x; q.A1 = p1.y; q.C1 = p1.z;
 }
 
-// One int8 tile (a: its D/64 A-fragments; sc / er: scales and errors of the lane's four C/D
-// rows 4(lane >> 4) + r) against the 32 queries -> the upper bounds u, in the accumulator
-// layout of tile_mfma (u0: queries 0-15, u1: 16-31). The one place u is evaluated: the scan,
-// the seed sample and rag_index_prescan_bounds all come here.
-template <int D>
-__device__ __forceinline__ void tile_u8(const intx4 (&a)[steps8<D>()], const Query8<D>& q,
-                                        const float4& sc, const float4& er, floatx4& u0,
-                                        floatx4& u1) {
-  intx4 h0 = {0, 0, 0, 0}, l0 = h0, h1 = h0, l1 = h0;
-#pragma unroll
-  for (int s = 0; s < steps8<D>(); ++s) {
-    h0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.h0[s], h0, 0, 0, 0);
-    h1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.h1[s], h1, 0, 0, 0);
-    l0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.l0[s], l0, 0, 0, 0);
-    l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.l1[s], l1, 0, 0, 0);
-  }
+// The integer dots I of one tile of a copy against both planes of the 32 queries, in the
+// accumulator layout of tile_mfma (h0 / l0: queries 0-15, h1 / l1: 16-31)
+struct Dots {
+  intx4 h0, l0, h1, l1;
+};
+
+// ... and their upper bounds u in format Copy's form (sc / er: scales and errors of the lane's
+// four C/D rows 4(lane >> 4) + r). The one place u is evaluated: the scans, the seed sample and
+// rag_index_prescan_bounds all come here.
+template <int D, typename Copy>
+__device__ __forceinline__ void dots_u(const Dots& d, const Query8<D>& q, const float4& sc,
+                                       const float4& er, floatx4& u0, floatx4& u1) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float s_r = r == 0 ? sc.x : r == 1 ? sc.y : r == 2 ? sc.z : sc.w;
     const float e_r = r == 0 ? er.x : r == 1 ? er.y : r == 2 ? er.z : er.w;
-    u0[r] = u_bound(h0[r], l0[r], s_r, e_r, q.sq0, q.A0, q.C0);
-    u1[r] = u_bound(h1[r], l1[r], s_r, e_r, q.sq1, q.A1, q.C1);
+    u0[r] = Copy::bound(d.h0[r], d.l0[r], s_r, e_r, q.sq0, q.A0, q.C0);
+    u1[r] = Copy::bound(d.h1[r], d.l1[r], s_r, e_r, q.sq1, q.A1, q.C1);
   }
+}
+
+// One int8 tile (a: its D/64 A-fragments) against the 32 queries -> the upper bounds u, in the
+// accumulator layout of tile_mfma (u0: queries 0-15, u1: 16-31)
+template <int D>
+__device__ __forceinline__ void tile_u8(const intx4 (&a)[steps8<D>()], const Query8<D>& q,
+                                        const float4& sc, const float4& er, floatx4& u0,
+                                        floatx4& u1) {
+  Dots d;
+  d.h0 = d.l0 = d.h1 = d.l1 = intx4{0, 0, 0, 0};
+#pragma unroll
+  for (int s = 0; s < steps8<D>(); ++s) {
+    d.h0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.h0[s], d.h0, 0, 0, 0);
+    d.h1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.h1[s], d.h1, 0, 0, 0);
+    d.l0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.l0[s], d.l0, 0, 0, 0);
+    d.l1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[s], q.l1[s], d.l1, 0, 0, 0);
+  }
+  dots_u<D, Copy8>(d, q, sc, er, u0, u1);
+}
+
+// scales and errors of the lane's four C/D rows of tile t, by plain loads
+__device__ __forceinline__ void tile_meta(const float* __restrict__ meta, int64_t t, int lane,
+                                          float4& sc, float4& er) {
+  sc = *reinterpret_cast<const float4*>(meta + t * 32 + 4 * (lane >> 4));
+  er = *reinterpret_cast<const float4*>(meta + t * 32 + 16 + 4 * (lane >> 4));
+}
+
+// the int8 copy's tile t: its D/64 fragments by non-temporal loads, then tile_u8
+template <int D>
+__device__ __forceinline__ void Copy8::tile_u_at(const char* __restrict__ data,
+                                                 const float* __restrict__ meta, int64_t t,
+                                                 const Query8<D>& q, int lane, floatx4& u0,
+                                                 floatx4& u1) {
+  constexpr int S = steps8<D>();
+  const intx4* tp = reinterpret_cast<const intx4*>(data) + t * (S * 64) + lane;
+  intx4 a[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) a[s] = __builtin_nontemporal_load(tp + s * 64);
+  float4 sc, er;
+  tile_meta(meta, t, lane, sc, er);
+  tile_u8<D>(a, q, sc, er, u0, u1);
+}
+
+// ---- what the two prescan kernels share; their pipelines are their own ----
+// A wave's start: its top-k state, its place in the grid, its strided sequence of tile PAIRS
+// (pairs p_first + j p_step, j < n_mine) and the query batch
+struct PairWalk {
+  int gw, nw, p_first, p_step, n_mine;
+};
+
+template <int D, bool FILTER>
+__device__ __forceinline__ void prescan_start(ScanTopK& st, PairWalk& w, Query8<D>& q, int* lds,
+                                              int wid, int lane, const float* __restrict__ seed_thr,
+                                              const uint32_t* __restrict__ filt, int n_tiles,
+                                              const intx4* __restrict__ qfrag8,
+                                              const float* __restrict__ qp8) {
+  topk_init<FILTER>(st, lds, wid, lane, seed_thr, filt);
+  w.gw = blockIdx.x * kWavesPerWG + __builtin_amdgcn_readfirstlane(wid);
+  w.nw = gridDim.x * kWavesPerWG;
+  const int n_pairs = (n_tiles + 1) / 2;
+  tile_sequence<true>(w.gw, w.nw, n_pairs, w.p_first, w.p_step, w.n_mine);
+  query8_load<D>(q, qfrag8, qp8, lane);
+}
+
+// What rides in a pair's load batch beside its image: the scales and errors of the lane's four
+// C/D rows of both tiles and, under FILTER, their tags. The tag column ends at n_tiles * 16
+// rows, so the pair's tag descriptor is clipped there (out-of-range buffer loads return 0)
+struct PairSide {
+  float4 sc[2], er[2];
+  uint4 tg[2];
+};
+
+template <bool FILTER>
+__device__ __forceinline__ void pair_side_load(PairSide& b, const float* __restrict__ meta,
+                                               const uint32_t* __restrict__ tags, int p,
+                                               int n_tiles, int goff) {
+  const __amdgpu_buffer_rsrc_t rm = tile_rsrc(meta + (int64_t)p * 64, 256);
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    b.sc[u] = __builtin_bit_cast(float4,
+                                 __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128, 0));
+    b.er[u] = __builtin_bit_cast(
+        float4, __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128 + 64, 0));
+  }
+  if constexpr (FILTER) {
+    const int left = min(2, n_tiles - 2 * p);   // tiles of this pair the tag column holds
+    const __amdgpu_buffer_rsrc_t rt =
+        tile_rsrc(tags + (int64_t)p * (2 * kTileRows), left * kTileRows * 4);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      b.tg[u] = __builtin_bit_cast(
+          uint4, __builtin_amdgcn_raw_buffer_load_b128(rt, goff, u * (kTileRows * 4), 0));
+  } else {
+    b.tg[0] = b.tg[1] = uint4{0u, 0u, 0u, 0u};
+  }
+}
+
+// MODE 1 (MFMA + bound only): the max of a tile's eight bounds of a lane keeps them alive ...
+__device__ __forceinline__ float max8(const floatx4& u0, const floatx4& u1) {
+  return fmaxf(fmaxf(fmaxf(u0[0], u0[1]), fmaxf(u0[2], u0[3])),
+               fmaxf(fmaxf(u1[0], u1[1]), fmaxf(u1[2], u1[3])));
+}
+// ... and the store that is never taken in practice keeps the max: defeats DCE
+__device__ __forceinline__ void keep_alive(float vmax, float* __restrict__ part_s, int gw) {
+  if (vmax == 12345.0f) part_s[gw] = vmax;
 }
 
 // The scan walks PAIRS of tiles (32 rows, 12 KiB + 256 B of meta per load batch, two batches
@@ -616,21 +717,15 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i8(
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   ScanTopK st;
-  topk_init<FILTER>(st, lds, wid, lane, seed_thr, filt);
-
-  const int gw = blockIdx.x * kWavesPerWG + __builtin_amdgcn_readfirstlane(wid);
-  const int nw = gridDim.x * kWavesPerWG;
-  const int n_pairs = (n_tiles + 1) / 2;
-  int p_first, p_step, n_mine;
-  tile_sequence<true>(gw, nw, n_pairs, p_first, p_step, n_mine);
-
+  PairWalk pw;
   Query8<D> q;
-  query8_load<D>(q, qfrag8, qp8, lane);
+  prescan_start<D, FILTER>(st, pw, q, lds, wid, lane, seed_thr, filt, n_tiles, qfrag8, qp8);
+  const int gw = pw.gw, nw = pw.nw;
+  const int p_first = pw.p_first, p_step = pw.p_step, n_mine = pw.n_mine;
 
   struct Batch {
     intx4 a[2][S];
-    float4 sc[2], er[2];
-    uint4 tg[2];
+    PairSide side;
   };
   const int voff = lane * 16, goff = (lane >> 4) * 16;
   auto load = [&](Batch& b, int j) __attribute__((always_inline)) {
@@ -642,25 +737,7 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i8(
       for (int s = 0; s < S; ++s)
         b.a[u][s] = __builtin_bit_cast(
             intx4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (u * S + s) * 1024, 2));
-    const __amdgpu_buffer_rsrc_t rm = tile_rsrc(meta + (int64_t)p * 64, 256);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      b.sc[u] = __builtin_bit_cast(float4,
-                                   __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128, 0));
-      b.er[u] = __builtin_bit_cast(
-          float4, __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128 + 64, 0));
-    }
-    if constexpr (FILTER) {
-      const int left = min(2, n_tiles - 2 * p);   // tiles of this pair the tag column holds
-      const __amdgpu_buffer_rsrc_t rt =
-          tile_rsrc(tags + (int64_t)p * (2 * kTileRows), left * kTileRows * 4);
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-        b.tg[u] = __builtin_bit_cast(
-            uint4, __builtin_amdgcn_raw_buffer_load_b128(rt, goff, u * (kTileRows * 4), 0));
-    } else {
-      b.tg[0] = b.tg[1] = uint4{0u, 0u, 0u, 0u};
-    }
+    pair_side_load<FILTER>(b.side, meta, tags, p, n_tiles, goff);
     __builtin_amdgcn_sched_barrier(0);
   };
   float vmax = kNegInf;   // MODE 1/2: keeps the work alive
@@ -672,15 +749,14 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i8(
         intx4 x = b.a[u][0];
 #pragma unroll
         for (int s = 1; s < S; ++s) x += b.a[u][s];
-        vmax = fmaxf(vmax, (float)(x[0] + x[1] + x[2] + x[3]) + b.sc[u].x + b.er[u].x);
+        vmax = fmaxf(vmax, (float)(x[0] + x[1] + x[2] + x[3]) + b.side.sc[u].x + b.side.er[u].x);
       } else {
         floatx4 u0, u1;
-        tile_u8<D>(b.a[u], q, b.sc[u], b.er[u], u0, u1);
+        tile_u8<D>(b.a[u], q, b.side.sc[u], b.side.er[u], u0, u1);
         if constexpr (MODE == 0)
-          topk_tile_tg<FILTER>(st, u0, u1, 2 * p + u, n_rows, b.tg[u], lane);
+          topk_tile_tg<FILTER>(st, u0, u1, 2 * p + u, n_rows, b.side.tg[u], lane);
         else
-          vmax = fmaxf(vmax, fmaxf(fmaxf(fmaxf(u0[0], u0[1]), fmaxf(u0[2], u0[3])),
-                                   fmaxf(fmaxf(u1[0], u1[1]), fmaxf(u1[2], u1[3]))));
+          vmax = fmaxf(vmax, max8(u0, u1));
       }
     }
   };
@@ -698,50 +774,10 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i8(
     }
   }
   if constexpr (MODE != 0) {
-    if (vmax == 12345.0f) part_s[gw] = vmax;   // never true in practice; defeats DCE
+    keep_alive(vmax, part_s, gw);
     return;
   }
   topk_finish<2>(st, lane, gw, nw, part_s, part_i, heads_s, heads_i, heads_n);
-}
-
-// u of the 16 rows of tile t against the pass's 32 queries, by one wave, through tile_u8:
-// out[q * n + i] for the requested row i = 16 t + (its position in the tile). One wave per
-// requested row (rag_index_prescan_bounds; a test's direct view of the certificate's premise).
-template <int D>
-__global__ __launch_bounds__(64) void prescan_bounds_kernel(
-    const char* __restrict__ c8, const float* __restrict__ meta,
-    const intx4* __restrict__ qfrag8, const float* __restrict__ qp8,
-    const int64_t* __restrict__ rows, int64_t n, int64_t n_rows, int B,
-    float* __restrict__ out) {
-  constexpr int S = steps8<D>();
-  const int64_t i = blockIdx.x;
-  if (i >= n) return;
-  const int lane = threadIdx.x;
-  const int64_t row = rows[i];
-  if (row < 0 || row >= n_rows) {   // not a stored row: never dereferenced
-    if (lane < B) out[(int64_t)lane * n + i] = kNegInf;
-    return;
-  }
-  Query8<D> q;
-  query8_load<D>(q, qfrag8, qp8, lane);
-  const int64_t t = row >> 4;
-  intx4 a[S];
-  const intx4* tp = reinterpret_cast<const intx4*>(c8) + t * (S * 64) + lane;
-#pragma unroll
-  for (int s = 0; s < S; ++s) a[s] = tp[s * 64];
-  const float4 sc = *reinterpret_cast<const float4*>(meta + t * 32 + 4 * (lane >> 4));
-  const float4 er = *reinterpret_cast<const float4*>(meta + t * 32 + 16 + 4 * (lane >> 4));
-  floatx4 u0, u1;
-  tile_u8<D>(a, q, sc, er, u0, u1);
-  // lane holds rows 4(lane >> 4) + r of queries (lane & 15), 16 + (lane & 15)
-  const int r = (int)(row & 15) - 4 * (lane >> 4);
-  if (r >= 0 && r < 4) {
-    const int qa = lane & 15, qb = 16 + (lane & 15);
-    const float va = r == 0 ? u0[0] : r == 1 ? u0[1] : r == 2 ? u0[2] : u0[3];
-    const float vb = r == 0 ? u1[0] : r == 1 ? u1[1] : r == 2 ? u1[2] : u1[3];
-    if (qa < B) out[(int64_t)qa * n + i] = va;
-    if (qb < B) out[(int64_t)qb * n + i] = vb;
-  }
 }
 
 // ----------------------------------------------------------------------------------------
@@ -750,16 +786,11 @@ __global__ __launch_bounds__(64) void prescan_bounds_kernel(
 // planes, same lists; the A-fragments (bytes 4 v) are unpacked from the packed dwords
 // (unpack6) and the stored scale is s_r / 4.
 // ----------------------------------------------------------------------------------------
-// The integer dots I of one 6-bit tile (w: the lane's eighteen packed dwords of it,
-// pair6_dword(u, s, c) - 18 u) against both planes of the 32 queries, in the accumulator
-// layout of tile_mfma
-struct Dots6 {
-  intx4 h0, l0, h1, l1;
-};
-
+// The dots of one 6-bit tile (w: the lane's eighteen packed dwords of it,
+// pair6_dword(u, s, c) - 18 u)
 template <int D>
 __device__ __forceinline__ void tile_dots6(const uint32_t (&w)[3 * steps8<D>()],
-                                           const Query8<D>& q, Dots6& d) {
+                                           const Query8<D>& q, Dots& d) {
   d.h0 = d.l0 = d.h1 = d.l1 = intx4{0, 0, 0, 0};
 #pragma unroll
   for (int s = 0; s < steps8<D>(); ++s) {
@@ -771,31 +802,7 @@ __device__ __forceinline__ void tile_dots6(const uint32_t (&w)[3 * steps8<D>()],
   }
 }
 
-// ... and their upper bounds u (sc / er: scales and errors of the lane's four C/D rows), as
-// tile_u8's second half. The one place the 6-bit u is evaluated: the scan, the seed sample and
-// rag_index_prescan_bounds all come here.
-template <int D>
-__device__ __forceinline__ void dots6_u(const Dots6& d, const Query8<D>& q, const float4& sc,
-                                        const float4& er, floatx4& u0, floatx4& u1) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float s_r = r == 0 ? sc.x : r == 1 ? sc.y : r == 2 ? sc.z : sc.w;
-    const float e_r = r == 0 ? er.x : r == 1 ? er.y : r == 2 ? er.z : er.w;
-    u0[r] = u_bound6(d.h0[r], d.l0[r], s_r, e_r, q.sq0, q.A0, q.C0);
-    u1[r] = u_bound6(d.h1[r], d.l1[r], s_r, e_r, q.sq1, q.A1, q.C1);
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void tile_u6(const uint32_t (&w)[3 * steps8<D>()], const Query8<D>& q,
-                                        const float4& sc, const float4& er, floatx4& u0,
-                                        floatx4& u1) {
-  Dots6 d;
-  tile_dots6<D>(w, q, d);
-  dots6_u<D>(d, q, sc, er, u0, u1);
-}
-
-// the lane's 36 dwords of pair `pair` by plain loads (seed sample, diagnostic bounds)
+// the lane's 36 dwords of pair `pair` by non-temporal loads (seed sample, diagnostic bounds)
 __device__ __forceinline__ void pair6_load(uint32_t (&w)[36], const char* __restrict__ c6,
                                            int64_t pair, int lane) {
   const intx4* pp = reinterpret_cast<const intx4*>(c6 + pair * kPair6Bytes) + lane;
@@ -807,20 +814,22 @@ __device__ __forceinline__ void pair6_load(uint32_t (&w)[36], const char* __rest
   }
 }
 
-// tile t of the copy against the 32 queries, by one wave (pair6_load, then tile_u6 on its half)
+// the 6-bit copy's tile t: its pair (pair6_load), then the dots and bounds of its half
 template <int D>
-__device__ __forceinline__ void tile_u6_at(const char* __restrict__ c6,
-                                           const float* __restrict__ meta, int64_t t,
-                                           const Query8<D>& q, int lane, floatx4& u0,
-                                           floatx4& u1) {
+__device__ __forceinline__ void Copy6::tile_u_at(const char* __restrict__ data,
+                                                 const float* __restrict__ meta, int64_t t,
+                                                 const Query8<D>& q, int lane, floatx4& u0,
+                                                 floatx4& u1) {
   static_assert(D == 384, "pair6 layout");
   uint32_t w[36], wt[18];
-  pair6_load(w, c6, t >> 1, lane);
+  pair6_load(w, data, t >> 1, lane);
 #pragma unroll
   for (int g = 0; g < 18; ++g) wt[g] = (t & 1) ? w[18 + g] : w[g];
-  const float4 sc = *reinterpret_cast<const float4*>(meta + t * 32 + 4 * (lane >> 4));
-  const float4 er = *reinterpret_cast<const float4*>(meta + t * 32 + 16 + 4 * (lane >> 4));
-  tile_u6<D>(wt, q, sc, er, u0, u1);
+  float4 sc, er;
+  tile_meta(meta, t, lane, sc, er);
+  Dots d;
+  tile_dots6<D>(wt, q, d);
+  dots_u<D, Copy6>(d, q, sc, er, u0, u1);
 }
 
 // As scan_kernel_i8: strided pairs of tiles, one buffer descriptor per pair, the pair's meta
@@ -845,16 +854,11 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   ScanTopK st;
-  topk_init<FILTER>(st, lds, wid, lane, seed_thr, filt);
-
-  const int gw = blockIdx.x * kWavesPerWG + __builtin_amdgcn_readfirstlane(wid);
-  const int nw = gridDim.x * kWavesPerWG;
-  const int n_pairs = (n_tiles + 1) / 2;
-  int p_first, p_step, n_mine;
-  tile_sequence<true>(gw, nw, n_pairs, p_first, p_step, n_mine);
-
+  PairWalk pw;
   Query8<D> q;
-  query8_load<D>(q, qfrag8, qp8, lane);
+  prescan_start<D, FILTER>(st, pw, q, lds, wid, lane, seed_thr, filt, n_tiles, qfrag8, qp8);
+  const int gw = pw.gw, nw = pw.nw;
+  const int p_first = pw.p_first, p_step = pw.p_step, n_mine = pw.n_mine;
   // The lo planes live in accumulation registers, which the MFMAs read as they read vector
   // registers: three batches in flight and both planes do not fit the 256 vector registers, and
   // left to itself the allocator parks fragments there and copies each back before its use
@@ -867,8 +871,7 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
 
   struct Batch {
     intx4 x[9];
-    float4 sc[2], er[2];
-    uint4 tg[2];
+    PairSide side;
   };
   const int voff = lane * 16, goff = (lane >> 4) * 16;
   auto load = [&](Batch& b, int j) __attribute__((always_inline)) {
@@ -878,25 +881,7 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
     for (int L = 0; L < 9; ++L)
       b.x[L] = __builtin_bit_cast(intx4,
                                   __builtin_amdgcn_raw_buffer_load_b128(rs, voff, L * 1024, 2));
-    const __amdgpu_buffer_rsrc_t rm = tile_rsrc(meta + (int64_t)p * 64, 256);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      b.sc[u] = __builtin_bit_cast(float4,
-                                   __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128, 0));
-      b.er[u] = __builtin_bit_cast(
-          float4, __builtin_amdgcn_raw_buffer_load_b128(rm, goff, u * 128 + 64, 0));
-    }
-    if constexpr (FILTER) {
-      const int left = min(2, n_tiles - 2 * p);   // tiles of this pair the tag column holds
-      const __amdgpu_buffer_rsrc_t rt =
-          tile_rsrc(tags + (int64_t)p * (2 * kTileRows), left * kTileRows * 4);
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-        b.tg[u] = __builtin_bit_cast(
-            uint4, __builtin_amdgcn_raw_buffer_load_b128(rt, goff, u * (kTileRows * 4), 0));
-    } else {
-      b.tg[0] = b.tg[1] = uint4{0u, 0u, 0u, 0u};
-    }
+    pair_side_load<FILTER>(b.side, meta, tags, p, n_tiles, goff);
     __builtin_amdgcn_sched_barrier(0);
   };
   float vmax = kNegInf;   // MODE 1/2/3: keeps the work alive
@@ -908,14 +893,14 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
     uint4 tg;
     int t;
   } held;
-  Dots6 dots[2];
+  Dots dots[2];
   dots[1].h0 = dots[1].l0 = dots[1].h1 = dots[1].l1 = intx4{0, 0, 0, 0};
   held.sc = held.er = float4{0.f, 0.f, 0.f, 0.f};
   held.tg = uint4{0u, 0u, 0u, 0u};
   held.t = n_tiles;
-  auto check_held = [&](const Dots6& d) __attribute__((always_inline)) {
+  auto check_held = [&](const Dots& d) __attribute__((always_inline)) {
     floatx4 u0, u1;
-    dots6_u<D>(d, q, held.sc, held.er, u0, u1);
+    dots_u<D, Copy6>(d, q, held.sc, held.er, u0, u1);
     if constexpr (MODE == 0) {
       // a full tile (wave-uniform; every tile but the shard's last) skips the per-row checks
       const int t = __builtin_amdgcn_readfirstlane(held.t);
@@ -924,8 +909,7 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
       else
         topk_tile_tg<FILTER>(st, u0, u1, t, n_rows, held.tg, lane);
     } else {
-      vmax = fmaxf(vmax, fmaxf(fmaxf(fmaxf(u0[0], u0[1]), fmaxf(u0[2], u0[3])),
-                               fmaxf(fmaxf(u1[0], u1[1]), fmaxf(u1[2], u1[3]))));
+      vmax = fmaxf(vmax, max8(u0, u1));
     }
   };
   auto process = [&](const Batch& b, int j) __attribute__((always_inline)) {
@@ -937,7 +921,7 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
 #pragma unroll
         for (int L = 1; L < 9; ++L) x += b.x[L];
         if (u == 0) vmax = fmaxf(vmax, (float)(x[0] + x[1] + x[2] + x[3]));
-        vmax = fmaxf(vmax, b.sc[u].x + b.er[u].x);
+        vmax = fmaxf(vmax, b.side.sc[u].x + b.side.er[u].x);
       } else {
         uint32_t w[18];
 #pragma unroll
@@ -946,13 +930,13 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
           intx4 x = {0, 0, 0, 0};
 #pragma unroll
           for (int s = 0; s < steps8<D>(); ++s) x += unpack6(w[3 * s], w[3 * s + 1], w[3 * s + 2]);
-          vmax = fmaxf(vmax, (float)(x[0] + x[1] + x[2] + x[3]) + b.sc[u].x + b.er[u].x);
+          vmax = fmaxf(vmax, (float)(x[0] + x[1] + x[2] + x[3]) + b.side.sc[u].x + b.side.er[u].x);
         } else {
           tile_dots6<D>(w, q, dots[u]);   // issued first; the held tile's check beside them
           check_held(dots[u ^ 1]);
-          held.sc = b.sc[u];
-          held.er = b.er[u];
-          held.tg = b.tg[u];
+          held.sc = b.side.sc[u];
+          held.er = b.side.er[u];
+          held.tg = b.side.tg[u];
           held.t = 2 * p + u;
         }
       }
@@ -978,16 +962,19 @@ __global__ __launch_bounds__(kScanBlock, 1) void scan_kernel_i6(
     if constexpr (MODE == 0 || MODE == 1) check_held(dots[1]);   // the last tile
   }
   if constexpr (MODE != 0) {
-    if (vmax == 12345.0f) part_s[gw] = vmax;   // never true in practice; defeats DCE
+    keep_alive(vmax, part_s, gw);
     return;
   }
   topk_finish<2>(st, lane, gw, nw, part_s, part_i, heads_s, heads_i, heads_n);
 }
 
-// prescan_bounds_kernel for the 6-bit copy: one wave per requested row, through tile_u6
-template <int D>
-__global__ __launch_bounds__(64) void prescan6_bounds_kernel(
-    const char* __restrict__ c6, const float* __restrict__ meta,
+// u of the 16 rows of tile t of a copy against the pass's 32 queries, by one wave, through the
+// format's tile_u_at: out[q * n + i] for the requested row i = 16 t + (its position in the
+// tile). One wave per requested row (rag_index_prescan_bounds; a test's direct view of the
+// certificate's premise).
+template <int D, typename Copy>
+__global__ __launch_bounds__(64) void prescan_bounds_kernel(
+    const char* __restrict__ data, const float* __restrict__ meta,
     const intx4* __restrict__ qfrag8, const float* __restrict__ qp8,
     const int64_t* __restrict__ rows, int64_t n, int64_t n_rows, int B,
     float* __restrict__ out) {
@@ -1002,7 +989,7 @@ __global__ __launch_bounds__(64) void prescan6_bounds_kernel(
   Query8<D> q;
   query8_load<D>(q, qfrag8, qp8, lane);
   floatx4 u0, u1;
-  tile_u6_at<D>(c6, meta, row >> 4, q, lane, u0, u1);
+  Copy::template tile_u_at<D>(data, meta, row >> 4, q, lane, u0, u1);
   // lane holds rows 4(lane >> 4) + r of queries (lane & 15), 16 + (lane & 15)
   const int r = (int)(row & 15) - 4 * (lane >> 4);
   if (r >= 0 && r < 4) {

@@ -156,56 +156,27 @@ __global__ __launch_bounds__(256) void sample_kernel(const half8* __restrict__ c
   sample_epilogue<FILTER>(sc, st, lane, tags, filt, n_rows, n_sample, smax);
 }
 
-// sample for a pass that scans the int8 copy (scan_kernel_i8): the same sample tiles scored
-// with the same upper bound u (tile_u8), so thresh_kernel's seed is a lower bound of the
-// 32nd-best u, which is what that scan's thresholds compare.
-template <int D, bool FILTER>
-__global__ __launch_bounds__(256) void sample_kernel_i8(
-    const char* __restrict__ c8, const float* __restrict__ meta,
-    const uint32_t* __restrict__ tags, const uint32_t* __restrict__ filt,
-    const intx4* __restrict__ qfrag8, const float* __restrict__ qp8, int n_rows, int n_tiles,
-    int n_sample, float* __restrict__ smax) {
-  constexpr int S = steps8<D>();
-  const int lane = threadIdx.x & 63;
-  SampleTiles st;
-  // a tile of the copy is S * 64 16-byte fragments, as sample_tiles strides a half8 tile
-  if (!sample_tiles<S>(st, reinterpret_cast<const half8*>(c8), n_tiles, n_sample, lane)) return;
-  Query8<D> q;
-  query8_load<D>(q, qfrag8, qp8, lane);
-  floatx4 sc[2][2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const intx4* tp = reinterpret_cast<const intx4*>(u == 0 ? st.p0 : st.p1);
-    const int t = u == 0 ? st.t0 : st.t1;
-    intx4 a[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) a[s] = __builtin_nontemporal_load(tp + s * 64);
-    const float4 rs = *reinterpret_cast<const float4*>(meta + (int64_t)t * 32 + 4 * (lane >> 4));
-    const float4 re =
-        *reinterpret_cast<const float4*>(meta + (int64_t)t * 32 + 16 + 4 * (lane >> 4));
-    tile_u8<D>(a, q, rs, re, sc[u][0], sc[u][1]);
-  }
-  sample_epilogue<FILTER>(sc, st, lane, tags, filt, n_rows, n_sample, smax);
-}
-
-// sample for a pass that scans the 6-bit copy (scan_kernel_i6): the same sample tiles, scored
-// with that scan's own u (tile_u6)
-template <int D, bool FILTER>
-__global__ __launch_bounds__(256) void sample_kernel_i6(
-    const char* __restrict__ c6, const float* __restrict__ meta,
+// sample for a pass that scans a copy (scan_kernel_i8 / scan_kernel_i6): the same sample tiles
+// scored with that scan's own upper bound u (the format's tile_u_at), so thresh_kernel's seed is
+// a lower bound of the 32nd-best u, which is what that scan's thresholds compare.
+// Four waves per SIMD asked for: left to itself the allocator gave the same code three or four
+// (136 or 120 registers) depending on what else the unit instantiates.
+template <int D, bool FILTER, typename Copy>
+__global__ __launch_bounds__(256, 4) void sample_kernel_q(
+    const char* __restrict__ data, const float* __restrict__ meta,
     const uint32_t* __restrict__ tags, const uint32_t* __restrict__ filt,
     const intx4* __restrict__ qfrag8, const float* __restrict__ qp8, int n_rows, int n_tiles,
     int n_sample, float* __restrict__ smax) {
   const int lane = threadIdx.x & 63;
   SampleTiles st;
-  // only the tile numbers are used: the copy is addressed by pair (tile_u6_at)
-  if (!sample_tiles<1>(st, reinterpret_cast<const half8*>(c6), n_tiles, n_sample, lane)) return;
+  // only the tile numbers are used: the format addresses its own tiles (tile_u_at)
+  if (!sample_tiles<1>(st, reinterpret_cast<const half8*>(data), n_tiles, n_sample, lane)) return;
   Query8<D> q;
   query8_load<D>(q, qfrag8, qp8, lane);
   floatx4 sc[2][2];
 #pragma unroll
   for (int u = 0; u < 2; ++u)
-    tile_u6_at<D>(c6, meta, u == 0 ? st.t0 : st.t1, q, lane, sc[u][0], sc[u][1]);
+    Copy::template tile_u_at<D>(data, meta, u == 0 ? st.t0 : st.t1, q, lane, sc[u][0], sc[u][1]);
   sample_epilogue<FILTER>(sc, st, lane, tags, filt, n_rows, n_sample, smax);
 }
 

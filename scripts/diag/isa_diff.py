@@ -20,7 +20,17 @@ exists on one side only, parent against result. `--must-match REGEX` (repeatable
 that have to be identical; the exit status is 1 if one of them differs, if a kernel's scratch
 grows from 0 or if its occupancy drops.
 
-    python scripts/diag/isa_diff.py parent.s result.s [--must-match 'scan_kernel'] > record.jsonl
+Kernels are paired by their demangled names. `--rename 'REGEX=REPLACEMENT'` (repeatable, applied
+in order, `\\1` for a group) rewrites the parent's demangled names before pairing, so that a
+kernel that changed its name or its template arguments is compared with its predecessor and the
+scratch and occupancy conditions hold for it too; without it both sides are reported as "only
+in" and the tool fails (a name the demangler cannot read stays mangled; its rename is written
+over the mangled form):
+
+    --rename 'sample_kernel_i8<(\\d+), (\\w+)>=sample_kernel_q<\\1, \\2, ragmi::Copy8>'
+
+    python scripts/diag/isa_diff.py parent.s result.s [--must-match 'scan_kernel'] \\
+           [--rename 'OLD=NEW'] > record.jsonl
 """
 from __future__ import annotations
 
@@ -79,7 +89,9 @@ def kernels(path: str) -> dict[str, dict]:
         j = i + 1
         while j < n and not text[j].startswith(".Lfunc_end"):
             j += 1
-        entry: dict = {"body": _normalise(text[i + 1:j])}
+        # (the kernel's own symbol, in its descriptor and section lines, is not code: a renamed
+        # kernel with the same instructions compares equal)
+        entry: dict = {"body": [ln.replace(sym, "<self>") for ln in _normalise(text[i + 1:j])]}
         # the kernel-info comments follow the end label, up to the next section or label
         k = j + 1
         while k < n and not _LABEL.match(text[k]) and not text[k].lstrip().startswith(".amdhsa_kernel"):
@@ -108,37 +120,57 @@ def main() -> int:
     ap.add_argument("result")
     ap.add_argument("--must-match", action="append", default=[],
                     help="regex over the symbol or its demangled name: must be identical")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPLACEMENT",
+                    help="rewrite the parent's demangled names before pairing")
     a = ap.parse_args()
-    old, new = kernels(a.parent), kernels(a.result)
-    names = demangle(sorted(set(old) | set(new)))
+    renames = []
+    for spec in a.rename:
+        rx, eq, to = spec.partition("=")
+        if not eq:
+            ap.error(f"--rename {spec!r}: expected REGEX=REPLACEMENT")
+        renames.append((re.compile(rx), to))
+
+    def renamed(name: str) -> str:
+        for rx, to in renames:
+            name = rx.sub(to, name)
+        return name
+
+    old_syms, new_syms = kernels(a.parent), kernels(a.result)
+    dem = demangle(sorted(set(old_syms) | set(new_syms)))
+    # demangled name -> (symbol, entry); the parent's after --rename
+    old = {renamed(dem[s]): (s, e) for s, e in old_syms.items()}
+    new = {dem[s]: (s, e) for s, e in new_syms.items()}
     must = [re.compile(r) for r in a.must_match]
     keys = list(_NOTES)
     lines, bad, same, n_must = [], [], 0, 0
-    for sym in sorted(names, key=names.get):
-        o, r = old.get(sym), new.get(sym)
-        pinned = any(rx.search(names[sym]) or rx.search(sym) for rx in must)
+    for name in sorted(set(old) | set(new)):
+        (so, o), (sr, r) = old.get(name, (None, None)), new.get(name, (None, None))
+        pinned = any(rx.search(name) or any(s and rx.search(s) for s in (so, sr)) for rx in must)
         n_must += pinned
         if o and r and o["body"] == r["body"] and all(o.get(k) == r.get(k) for k in keys):
             same += 1
             continue
-        rec = {"kernel": names[sym]}
+        rec = {"kernel": name}
+        if so and dem[so] != name:
+            rec["parent_name"] = dem[so]
         if not o or not r:
             rec["only_in"] = "result" if r else "parent"
-            bad.append(f"{names[sym]}: only in the {rec['only_in']}")
+            bad.append(f"{name}: only in the {rec['only_in']}")
         else:
             rec["lines"] = [len(o["body"]), len(r["body"])]
             for k in keys:
                 rec[k] = [o.get(k), r.get(k)]
             if pinned:
-                bad.append(f"{names[sym]}: must be identical")
+                bad.append(f"{name}: must be identical")
             if o.get("scratch") == 0 and (r.get("scratch") or 0) > 0:
-                bad.append(f"{names[sym]}: scratch 0 -> {r.get('scratch')}")
+                bad.append(f"{name}: scratch 0 -> {r.get('scratch')}")
             if (r.get("occupancy") or 0) < (o.get("occupancy") or 0):
-                bad.append(f"{names[sym]}: occupancy {o.get('occupancy')} -> {r.get('occupancy')}")
+                bad.append(f"{name}: occupancy {o.get('occupancy')} -> {r.get('occupancy')}")
         lines.append(rec)
     head = {"note": "device code per kernel, parent against result; pairs are [parent, result]",
             "kernels_parent": len(old), "kernels_result": len(new), "identical": same,
-            "differing": len(lines), "must_match": a.must_match, "must_match_kernels": n_must,
+            "differing": len(lines), "must_match": a.must_match, "rename": a.rename,
+            "must_match_kernels": n_must,
             "violations": bad}
     print(json.dumps(head))
     for rec in lines:

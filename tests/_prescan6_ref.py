@@ -7,7 +7,7 @@ import numpy as np
 
 K_ROW_NORM = 1.001          # kRowNorm
 SLACK = np.float32(2.0 ** -20)   # kU8Slack
-QMAX = 31                   # kQ6Max
+QMAX = 31                   # Copy6::kQMax
 UP = 1.0 + 2.0 ** -20
 
 f32 = np.float32

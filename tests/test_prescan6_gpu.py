@@ -289,3 +289,74 @@ def test_copy_follows_the_rows(gpu):
     idx.upsert(fresh[32:], np.arange(c0, c0 + 32, dtype=np.int64), np.full(32, 3, np.uint32))
     check()
     idx.close()
+
+
+def _upper_bounds8(c, hi, lo, sq, A, C):
+    """The int8 copy's u [b, n] restated as _prescan6_ref restates the 6-bit one (prep_kernels.hip
+    quantise_row over Copy8, u_bound): bytes v = rint(c / s) in [-127, 127] with s = max|c| / 127,
+    E = ||c - s v||_2 rounded up; I = 254 (v . hi) + v . lo rounded to fp32 once (u_bound's fma of
+    two exact conversions), then the same two fp32 fmas."""
+    c = np.asarray(c, R.f32)
+    s = (np.abs(c).max(axis=1) / R.f32(127)).astype(R.f32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = np.where(s[:, None] > 0, np.rint((c / s[:, None]).astype(R.f32)), R.f32(0))
+    v = np.clip(v, -127, 127)
+    d = c.astype(np.float64) - s.astype(np.float64)[:, None] * v.astype(np.float64)
+    e2 = (d * d).sum(axis=1)
+    E = np.where(e2 > 0, np.sqrt(e2) * R.UP, 0.0).astype(R.f32)
+    v = v.astype(np.int64)
+    I8 = 254 * (hi @ v.T) + lo @ v.T                         # exact integers [b, n]
+    assert np.abs(I8).max(initial=0) < 2 ** 31
+    If = I8.astype(R.f32)
+    scale = (s[None, :] * sq[:, None]).astype(R.f32)
+    tail = R._fma32(np.broadcast_to(E[None, :], If.shape), np.broadcast_to(A[:, None], If.shape),
+                    np.broadcast_to(C[:, None], If.shape))
+    return R._fma32(If, scale, tail)
+
+
+def test_copy_at_the_threshold_capacity(gpu):
+    """The 6-bit copy's threshold paths: started inside reserve() when the capacity reaches
+    PRESCAN6_MIN_ROWS (index A), kept from creation at that capacity and grown by a later
+    reserve() (index B). 3017 rows, 189 tiles: the last pair of the copy has a spare half. After
+    every step the mode-3 bounds of all rows are the restatement's bit for bit and a k = 15
+    search is the oracle's under modes 0, 2 and 3; at the end the grown int8 copy's bounds are
+    its restatement's too."""
+    from ragmi.index import FlatIndex, PRESCAN6_MIN_ROWS
+    c = PR.world()
+    x, q, k = c["x"], c["q"][:32], 15
+    n = len(x)
+    assert n == 3017 and n < PRESCAN6_MIN_ROWS
+    planes = R.query_planes(O.normalize(q))
+
+    def check(idx):
+        got = three_modes(idx, lambda: lists(idx.search(q, k)), 1, 32)
+        enc = idx.export_rows()
+        same(got, oracle(enc, q, k))
+        u = idx.prescan_bounds(q, np.arange(idx.count, dtype=np.int64)).cpu().numpy()
+        rows = enc.view(np.float16).astype(np.float32)
+        want = R.upper_bounds(*R.quantise_rows6(rows), *planes)
+        np.testing.assert_array_equal(bits(u), bits(want))
+        return rows, enc
+
+    a = FlatIndex(dim=D, capacity=n, device=gpu)
+    a.upsert(x, np.arange(n, dtype=np.int64), None, new_count=n)
+    a.reserve(PRESCAN6_MIN_ROWS)              # the copy starts here, from the rows just moved
+    a.set_prescan(3)
+    check(a)
+    a.close()
+
+    b = FlatIndex(dim=D, capacity=PRESCAN6_MIN_ROWS, device=gpu)   # the copy exists from creation
+    b.upsert(x, np.arange(n, dtype=np.int64), None, new_count=n)
+    b.set_prescan(3)
+    check(b)
+    b.reserve(PRESCAN6_MIN_ROWS + 48)         # grows an existing copy from an odd tile count
+    fresh = np.random.default_rng(5).standard_normal((32, D)).astype(np.float32)
+    b.upsert(fresh, np.arange(n, n + 32, dtype=np.int64), np.full(32, 3, np.uint32))
+    assert b.count == n + 32
+    rows, enc = check(b)
+    b.set_prescan(2)                          # the grown int8 copy
+    u8 = b.prescan_bounds(q, np.arange(b.count, dtype=np.int64)).cpu().numpy()
+    np.testing.assert_array_equal(bits(u8), bits(_upper_bounds8(rows, *planes)))
+    e = O.rescore(enc, O.normalize(q), np.broadcast_to(np.arange(b.count), (32, b.count)).copy())
+    assert np.isfinite(u8).all() and (u8 >= e).all()
+    b.close()
