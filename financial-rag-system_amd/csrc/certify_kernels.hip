@@ -1,15 +1,34 @@
 // certify_kernels.hip — the exactness certificate of a search pass (included by index_search.hip
 // after scan_kernels.hip and seed_kernels.hip): the canonical exact score (exact_scores_*),
 // select_kernel (the scan's per-wave lists -> the exact top-k, or a verdict that the lists do
-// not prove it) and rescan_kernel (tier 2: the shard streamed once more for the queries select
-// could not certify), with the bookkeeping they share (ExactStats, mark_unanswered_kernel).
+// not prove it), band_kernel (tier 1 of the 6-bit route, spread over every CU) and rescan_kernel
+// (tier 2: the shard streamed once more for the queries select could not certify), with the
+// bookkeeping they share (ExactStats, mark_unanswered_kernel).
 namespace ragmi {
 
 constexpr int kCandCap = 256;   // select: compacted heads at/above the lane-max threshold
 constexpr int kBandLists = 32;  // select tier 1: lists gathered per chunk (8 per wave)
 // ... after the 6-bit prescan (select_kernel<D, FILTER, kBandLists6>): its band is ~200 rows in
 // as many lists per query, seven chunks of 32; 128 per chunk make that two gather round trips
+// (the build with kBandSlices = 0 of index_search.hip; production spreads tier 1, next)
 constexpr int kBandLists6 = 128;
+// ... spread over the chip (select_kernel<D, FILTER, kBandHead> then band_kernel, below): the
+// head instantiation gathers nothing; on verdict 1 it leaves a record per query in the workspace
+//   rec[q][0] n_q: the qualifying lists (-1: not tier 1, band_kernel's workgroups return)
+//   rec[q][1], [2] L and e_k (float bits)   [32..63], [64..95] A's exact scores and rows, sorted
+//   rec[q][kBandRecHdr ...] the ids of the n_q lists
+// pub[q][slice] is a slice's 32 best band rows (scores, rows) and its full-list flag at [64];
+// tk[q] the query's arrival ticket (zero between passes)
+constexpr int kBandHead = 0;
+constexpr int kBandSlicesMax = 16;
+constexpr int kBandRecHdr = 96;
+constexpr int kBandRec = kBandRecHdr + kMaxLists;
+constexpr int kBandPub = 72;
+struct BandWs {
+  int* rec;
+  int* pub;
+  int* tk;
+};
 
 // Wave 0 merges the four waves' top-32 lists (best first, one row of ws / wi per wave) out of
 // LDS: lanes 0..31 end with the best 32 of the 128 entries, best first. `none` pads list 0 in
@@ -119,6 +138,122 @@ struct ExactStats {
   float* t2;        // [B][2] tier-2 hand-off: (L, e_k) of each tier-2 query (rescan_kernel)
 };
 
+// Query bq's result row: lanes < k of one wave hold (s, id) sorted best-first
+__device__ __forceinline__ void emit_topk(float s, int id, int lane, int bq, int k,
+                                          int64_t id_offset, float* __restrict__ out_s,
+                                          int64_t* __restrict__ out_i,
+                                          int32_t* __restrict__ out_packed) {
+  if (lane < k) {
+    const bool ok = s != kNegInf;
+    if (out_packed) {
+      // multi-GPU exchange format: [B][k][2] int32 = (score bits, global row; -1 = none)
+      out_packed[((int64_t)bq * k + lane) * 2] = __float_as_int(s);
+      out_packed[((int64_t)bq * k + lane) * 2 + 1] = ok ? (int32_t)(id + id_offset) : -1;
+    } else {
+      out_s[(int64_t)bq * k + lane] = s;
+      out_i[(int64_t)bq * k + lane] = ok ? (int64_t)id + id_offset : (int64_t)-1;
+    }
+  }
+}
+
+// Tier 2 (one thread): query bq is handed to rescan_kernel (launched after every select, many
+// workgroups). Its floor L and the k-th exact score of A go to the hand-off record; nothing is
+// emitted by the caller (the rescan writes this query's output)
+__device__ __forceinline__ void hand_to_tier2(const ExactStats& fb, int bq, float L, float e_k,
+                                              const float* __restrict__ eps_t2) {
+  fb.tier[bq] = 2;
+  // the rescan bands on fp16 MFMA scores: after an int8 prescan (eps_t2 = qprep's fp16
+  // bound; `eps` is then the prescan's) its floor is e_k - the fp16 bound, not this L
+  fb.t2[2 * bq] = eps_t2 ? e_k - eps_t2[bq] : L;
+  fb.t2[2 * bq + 1] = e_k;
+  atomicAdd(&fb.cnt[1], 1ull);
+}
+
+// One chunk of tier 1 (select_kernel step 5, band_kernel), by a 256-thread workgroup: the lists
+// qlist[c0 .. c0 + BL) of the query's nql qualifying ones (slot b of the group part_s / part_i /
+// heads_n point at) are gathered, their entries >= L outside A (a_row: A's rows, one per lane
+// and half-wave) go to the LDS band buffer and are rescored, and wave 0 folds them into its
+// running exact top-32 (rs, ri in lanes 0..31, by (score desc, row asc)). false: a full list
+// holds an entry >= L (verdict = 2, nothing rescored). `more`: another chunk follows (the band
+// buffer is reset for it). n_band is zero on entry; rnd counts the rounds across chunks.
+template <int D, int BL, typename ListP>
+__device__ __forceinline__ bool band_chunk(ListP qlist, int c0, int nql, bool more,
+                                           const float* __restrict__ part_s,
+                                           const int* __restrict__ part_i,
+                                           const int* __restrict__ heads_n, int n_lists, int b,
+                                           float L, int a_row, const half8* __restrict__ corpus,
+                                           const float* __restrict__ qq,
+                                           const float* __restrict__ rows32,
+                                           int (&band)[BL * kKS], int& n_band,
+                                           float (&n_s)[2][32], int (&n_i)[2][32], int& verdict,
+                                           float& rs, int& ri, int& rnd) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  auto at = [&](int l, int pos) { return ((int64_t)l * kQ + b) * kKS + pos; };
+  // gather: a half-wave per list, a lane per entry; wave w takes the chunk's lists w, w + 4,
+  // ... Every load is issued before the first use (clamped, selects afterwards: step 1).
+  constexpr int kG = BL / 8;
+  const int pos = lane & (kKS - 1);
+  float gs[kG];
+  int gi[kG], gn[kG];
+#pragma unroll
+  for (int j = 0; j < kG; ++j) {
+    const int l = qlist[min(c0 + (2 * j + (lane >> 5)) * 4 + wid, nql - 1)];
+    gs[j] = part_s[at(l, pos)];
+    gi[j] = part_i[at(l, pos)];
+    gn[j] = heads_n[(int64_t)b * n_lists + l];
+  }
+#pragma unroll
+  for (int j = 0; j < kG; ++j) {
+    // entries past a list's length are stale memory
+    const bool in = c0 + (2 * j + (lane >> 5)) * 4 + wid < nql && pos < gn[j] && gs[j] >= L;
+    // lane 31 of the half-wave holds the tail: a full list may have dropped a row >= L
+    if (in && gn[j] >= kKS && pos == kKS - 1) verdict = 2;
+    bool in_a = false;
+#pragma unroll
+    for (int t = 0; t < 32; ++t) in_a |= gi[j] == __builtin_amdgcn_readlane(a_row, t);
+    if (in && !in_a) band[atomicAdd(&n_band, 1)] = gi[j];
+  }
+  __syncthreads();
+  if (verdict == 2) return false;
+  // rescoring: the band rows 32 per round, 8 per wave; wave 0 folds each round into the
+  // running exact top-32
+  const int nb = n_band;
+  for (int r0 = 0; r0 < nb; r0 += 32, ++rnd) {
+    int rows[8];
+    float es[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = r0 + wid * 8 + j;
+      const int r = band[min(c, nb - 1)];
+      rows[j] = c < nb ? r : -1;
+    }
+    exact_scores_wave<D, 8>(corpus, rows, qq, lane, es, rows32);
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        n_s[rnd & 1][wid * 8 + j] = es[j];
+        n_i[rnd & 1][wid * 8 + j] = rows[j] >= 0 ? rows[j] : kIdNone32;
+      }
+    }
+    // one barrier per round: round r + 2 overwrites this slot only after round r + 1's
+    // barrier, which wave 0 reaches after the read below
+    __syncthreads();
+    if (wid == 0) {
+      if (lane >= 32) {
+        rs = n_s[rnd & 1][lane - 32];
+        ri = n_i[rnd & 1][lane - 32];
+      }
+      bitonic_sort64(rs, ri, lane);
+    }
+  }
+  if (more) {   // the band buffer is reused by the next chunk
+    __syncthreads();
+    if (tid == 0) n_band = 0;
+    __syncthreads();
+  }
+  return true;
+}
+
 // ----------------------------------------------------------------------------------------
 // select: one 256-thread workgroup per query merges the n_lists sorted per-wave top-32
 // lists (approximate MFMA scores) into the exact top-k.
@@ -143,7 +278,11 @@ struct ExactStats {
 //       buffer and are rescored 32 per round (8 per wave); the result is the top-k of A's 32
 //       exact scores and theirs. One gather round trip, one rescoring round trip per 32 new
 //       rows and one merge per round, whatever the number of lists below kBandLists; more
-//       lists cost a chunk each, with a running top-32 across chunks.
+//       lists cost a chunk each, with a running top-32 across chunks (band_chunk).
+//       After the 6-bit prescan every query takes tier 1 with ~200 qualifying lists: there the
+//       head instantiation (BL = kBandHead) stops at the verdict, writes L, e_k, A by exact
+//       score and the qualifying lists to the workspace, and band_kernel, launched next with S
+//       workgroups per query, runs the same chunks spread over the chip and emits (below).
 //     tier 2 (rescan_kernel): otherwise the shard is streamed once more for this query by
 //       the rescan kernel launched after every select (its workgroups split the shard); here
 //       select only records L and e_k. Only inputs with more than 32 in-band rows inside one
@@ -174,7 +313,10 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
                                                      int64_t* __restrict__ out_i,
                                                      int32_t* __restrict__ out_packed,
                                                      const float* __restrict__ rows32,
-                                                     const float* __restrict__ eps_t2 = nullptr) {
+                                                     const float* __restrict__ eps_t2 = nullptr,
+                                                     BandWs bw = {}) {
+  constexpr bool kHead = BL == kBandHead;            // (its gather below is dead code)
+  constexpr int kChunk = kHead ? kBandLists : BL;
   __shared__ float w_s[4][32];
   __shared__ int64_t w_i[4][32];
   __shared__ int sel[32];
@@ -189,7 +331,7 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
   __shared__ int e_i[32];
   __shared__ int qlist[kMaxLists];   // tier 1: lists whose head is >= L
   __shared__ int n_q;
-  __shared__ int band[BL * kKS];   // tier 1: a chunk's rows with a >= L outside A
+  __shared__ int band[kChunk * kKS];   // tier 1: a chunk's rows with a >= L outside A
   __shared__ int n_band;
   __shared__ float n_s[2][32];       // tier 1: a round's exact scores / rows (two rounds in
   __shared__ int n_i[2][32];         // flight: one barrier per round)
@@ -403,17 +545,7 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
   __syncthreads();
 
   auto emit = [&](float s, int id) {   // wave 0, lanes < k: (s, id) sorted best-first
-    if (lane < k) {
-      const bool ok = s != kNegInf;
-      if (out_packed) {
-        // multi-GPU exchange format: [B][k][2] int32 = (score bits, global row; -1 = none)
-        out_packed[((int64_t)bq * k + lane) * 2] = __float_as_int(s);
-        out_packed[((int64_t)bq * k + lane) * 2 + 1] = ok ? (int32_t)(id + id_offset) : -1;
-      } else {
-        out_s[(int64_t)bq * k + lane] = s;
-        out_i[(int64_t)bq * k + lane] = ok ? (int64_t)id + id_offset : (int64_t)-1;
-      }
-    }
+    emit_topk(s, id, lane, bq, k, id_offset, out_s, out_i, out_packed);
   };
 
   // ---- 4. order by exact score; 5. exactness check
@@ -446,9 +578,40 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
       emit(rs, ri);
       if (lane == 0) fb.tier[bq] = 0;
     }
+    if constexpr (kHead) {
+      // ---- head: the record band_kernel reads (launched next on the stream): A by exact score
+      int* rq = bw.rec + (int64_t)bq * kBandRec;
+      if (lane < 32 && v == 1) {
+        rq[32 + lane] = __float_as_int(rs);
+        rq[64 + lane] = ri;
+      }
+      if (lane == 0 && v != 1) rq[0] = -1;
+    }
   }
   __syncthreads();
   if (verdict == 0) return;
+  if constexpr (kHead) {
+    // tier 1 is band_kernel's: the qualifying lists (as below) go to the record, n_q last; tier 2
+    // by the seed is handed over here
+    int* rq = bw.rec + (int64_t)bq * kBandRec;
+    if (verdict == 1) {
+#pragma unroll
+      for (int j = 0; j < kCols; ++j)
+        if (hs[j] != kNegInf && hs[j] >= floor_L)
+          rq[kBandRecHdr + atomicAdd(&n_q, 1)] = (j * 4 + wid) * 64 + lane;
+      __syncthreads();
+    }
+    if (tid == 0) {
+      if (verdict == 1) {
+        rq[0] = n_q;
+        rq[1] = __float_as_int(floor_L);
+        rq[2] = __float_as_int(floor_E);
+      } else {
+        hand_to_tier2(fb, bq, floor_L, floor_E, eps_t2);
+      }
+    }
+    return;
+  }
 
   // ---- tier 1: every row with approximate score >= L is in a list (checked by the gather).
   //      The qualifying lists, from step 1's head scores (list of hs[j] = (4j + wid) 64 + lane)
@@ -463,82 +626,13 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
   const int nql = seeded ? n_q : 0;
   const int a_row = e_i[lane & 31];   // A's rows, one per lane: their exact scores are known
   int rnd = 0;
-  for (int c0 = 0; c0 < nql; c0 += BL) {
-    // gather: a half-wave per list, a lane per entry; wave w takes the chunk's lists w, w + 4,
-    // ... Every load is issued before the first use (clamped, selects afterwards: step 1).
-    constexpr int kG = BL / 8;
-    const int pos = lane & (kKS - 1);
-    float gs[kG];
-    int gi[kG], gn[kG];
-#pragma unroll
-    for (int j = 0; j < kG; ++j) {
-      const int l = qlist[min(c0 + (2 * j + (lane >> 5)) * 4 + wid, nql - 1)];
-      gs[j] = part_s[at(l, pos)];
-      gi[j] = part_i[at(l, pos)];
-      gn[j] = heads_n[(int64_t)b * n_lists + l];
-    }
-#pragma unroll
-    for (int j = 0; j < kG; ++j) {
-      // entries past a list's length are stale memory
-      const bool in = c0 + (2 * j + (lane >> 5)) * 4 + wid < nql && pos < gn[j] && gs[j] >= L;
-      // lane 31 of the half-wave holds the tail: a full list may have dropped a row >= L
-      if (in && gn[j] >= kKS && pos == kKS - 1) verdict = 2;
-      bool in_a = false;
-#pragma unroll
-      for (int t = 0; t < 32; ++t) in_a |= gi[j] == __builtin_amdgcn_readlane(a_row, t);
-      if (in && !in_a) band[atomicAdd(&n_band, 1)] = gi[j];
-    }
-    __syncthreads();
-    if (verdict == 2) break;
-    // rescoring: the band rows 32 per round, 8 per wave; wave 0 folds each round into the
-    // running exact top-32 (which starts as A)
-    const int nb = n_band;
-    for (int r0 = 0; r0 < nb; r0 += 32, ++rnd) {
-      int rows[8];
-      float es[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int c = r0 + wid * 8 + j;
-        const int r = band[min(c, nb - 1)];
-        rows[j] = c < nb ? r : -1;
-      }
-      exact_scores_wave<D, 8>(corpus, rows, qq, lane, es, rows32);
-      if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          n_s[rnd & 1][wid * 8 + j] = es[j];
-          n_i[rnd & 1][wid * 8 + j] = rows[j] >= 0 ? rows[j] : kIdNone32;
-        }
-      }
-      // one barrier per round: round r + 2 overwrites this slot only after round r + 1's
-      // barrier, which wave 0 reaches after the read below
-      __syncthreads();
-      if (wid == 0) {
-        if (lane >= 32) {
-          rs = n_s[rnd & 1][lane - 32];
-          ri = n_i[rnd & 1][lane - 32];
-        }
-        bitonic_sort64(rs, ri, lane);
-      }
-    }
-    if (c0 + BL < nql) {   // the band buffer is reused by the next chunk
-      __syncthreads();
-      if (tid == 0) n_band = 0;
-      __syncthreads();
-    }
-  }
+  for (int c0 = 0; c0 < nql; c0 += kChunk)
+    if (!band_chunk<D, kChunk>(qlist, c0, nql, c0 + kChunk < nql, part_s, part_i, heads_n, n_lists,
+                               b, L, a_row, corpus, qq, rows32, band, n_band, n_s, n_i, verdict,
+                               rs, ri, rnd))
+      break;
   if (verdict == 2) {
-    // ---- tier 2: handed to rescan_kernel (launched after every select, many workgroups):
-    // its floor L and the k-th exact score of A go to the hand-off record; nothing is emitted
-    // here (the rescan writes this query's output)
-    if (tid == 0) {
-      fb.tier[bq] = 2;
-      // the rescan bands on fp16 MFMA scores: after an int8 prescan (eps_t2 = qprep's fp16
-      // bound; `eps` is then the prescan's) its floor is e_k - the fp16 bound, not this L
-      fb.t2[2 * bq] = eps_t2 ? floor_E - eps_t2[bq] : L;
-      fb.t2[2 * bq + 1] = floor_E;
-      atomicAdd(&fb.cnt[1], 1ull);
-    }
+    if (tid == 0) hand_to_tier2(fb, bq, L, floor_E, eps_t2);
     return;
   }
   // tier 1 certified: the top-k of A and the band rows, by (exact score desc, row asc)
@@ -547,6 +641,126 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ p
     atomicAdd(&fb.cnt[0], 1ull);
   }
   if (wid == 0) emit(rs, ri);
+}
+
+// ----------------------------------------------------------------------------------------
+// band: tier 1 of the queries select_kernel<D, FILTER, kBandHead> left a record for, spread over
+// the chip (the 6-bit prescan: every query takes tier 1 with ~200 qualifying lists, and one
+// workgroup per query kept 32 CUs busy for ~0.3 ms beside the other batch's scan). Grid (S, Bq):
+// workgroup (s, bq) takes the chunks s, s + S, ... of kBandLists qualifying lists of query bq
+// (band_chunk, select's own gather and rescoring) and keeps the 32 best of ITS band rows; a full
+// list with an entry >= L ends its work. It publishes the 32 pairs and the full-list flag to
+// pub[bq][s] and arrives at the query's ticket (rescan_kernel's publish sequence, below); slices
+// with no chunk arrive too. The last arriver of bq either hands the query to tier 2 (a slice saw a
+// full list) or merges A with the S slice lists and emits the top-k by (exact score desc, row
+// asc) - the top-k of A and all band rows, whichever slice held them - then re-arms the ticket
+// for the workspace's next pass (stream order). Every slice rewrites its flag in every pass.
+// ----------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256) void band_kernel(const float* __restrict__ part_s,
+                                                   const int* __restrict__ part_i,
+                                                   const int* __restrict__ heads_n, int n_lists,
+                                                   const half8* __restrict__ corpus,
+                                                   const float* __restrict__ qn, int k,
+                                                   BandWs bw, ExactStats fb,
+                                                   const float* __restrict__ eps_t2,
+                                                   int64_t id_offset, float* __restrict__ out_s,
+                                                   int64_t* __restrict__ out_i,
+                                                   int32_t* __restrict__ out_packed,
+                                                   const float* __restrict__ rows32) {
+  __shared__ int band[kBandLists * kKS];
+  __shared__ int n_band;
+  __shared__ float n_s[2][32];
+  __shared__ int n_i[2][32];
+  __shared__ int verdict;   // 2: a full list of this slice holds an entry >= L
+  __shared__ int last;
+  const int S = gridDim.x, s = blockIdx.x, bq = blockIdx.y, grp = bq / kQ, b = bq % kQ;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  // plain loads of the head's record: a kernel boundary lies between its stores and these
+  const int* rq = bw.rec + (int64_t)bq * kBandRec;
+  const int nql = rq[0];
+  if (nql < 0) return;   // not a tier-1 query (block-uniform)
+  const float L = __int_as_float(rq[1]), floor_E = __int_as_float(rq[2]);
+  const int a_row = rq[64 + (lane & 31)];
+  part_s += (int64_t)grp * n_lists * (kQ * kKS);
+  part_i += (int64_t)grp * n_lists * (kQ * kKS);
+  heads_n += (int64_t)grp * kQ * n_lists;
+  const float* qq = qn + (int64_t)bq * D;
+  if (tid == 0) {
+    n_band = 0;
+    verdict = 1;
+  }
+  __syncthreads();
+  float rs = kNegInf;   // wave 0, lanes 0..31: the slice's running exact top-32
+  int ri = kIdNone32;
+  int rnd = 0;
+  constexpr int BL = kBandLists;
+  for (int c0 = s * BL; c0 < nql; c0 += S * BL)
+    if (!band_chunk<D, BL>(rq + kBandRecHdr, c0, nql, c0 + S * BL < nql, part_s, part_i, heads_n,
+                           n_lists, b, L, a_row, corpus, qq, rows32, band, n_band, n_s, n_i,
+                           verdict, rs, ri, rnd))
+      break;
+  int* pub = bw.pub + ((int64_t)bq * kBandSlicesMax + s) * kBandPub;
+  if (wid == 0 && lane < 32) {
+    pub[lane] = __float_as_int(rs);
+    pub[32 + lane] = ri;
+  }
+  if (tid == 0) pub[64] = verdict == 2;
+  // ---- publish: stores drained, agent release, then the ticket (rescan_kernel)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = atomicAdd(&bw.tk[bq], 1) == S - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+  // ---- last arriver of bq (wave 0): the S flags, then A and the S lists -> the exact top-k.
+  //      The lists are loaded 8 ahead of their merges, and one whose best entry scores below
+  //      the running 32nd is skipped (rescan_kernel's tail)
+  if (wid != 0) return;
+  const int* pq = bw.pub + (int64_t)bq * kBandSlicesMax * kBandPub;
+  const bool full = __ballot(lane < S && pq[(lane < S ? lane : 0) * kBandPub + 64] != 0) != 0;
+  if (full) {
+    if (lane == 0) hand_to_tier2(fb, bq, L, floor_E, eps_t2);
+  } else {
+    float x = lane < 32 ? __int_as_float(rq[32 + lane]) : kNegInf;
+    int id = lane < 32 ? rq[64 + lane] : kIdNone32;
+    constexpr int kPf = 8;
+    for (int u0 = 0; u0 < S; u0 += kPf) {
+      float xs[kPf];
+      int is[kPf];
+#pragma unroll
+      for (int u = 0; u < kPf; ++u) {
+        const int* p = pq + min(u0 + u, S - 1) * kBandPub + (lane >= 32 ? 63 - lane : 0);
+        const bool use = u0 + u < S && lane >= 32;
+        xs[u] = use ? __int_as_float(p[0]) : kNegInf;
+        is[u] = use ? p[32] : kIdNone32;
+      }
+#pragma unroll
+      for (int u = 0; u < kPf; ++u) {
+        const float head = __shfl(xs[u], 63, 64), t32 = __shfl(x, 31, 64);
+        if (head < t32 || head == kNegInf) continue;   // wave-uniform
+        if (lane >= 32) {
+          x = xs[u];
+          id = is[u];
+        }
+        bitonic_merge64(x, id, lane);
+      }
+    }
+    emit_topk(x, id, lane, bq, k, id_offset, out_s, out_i, out_packed);
+    if (lane == 0) {
+      fb.tier[bq] = 1;
+      atomicAdd(&fb.cnt[0], 1ull);
+    }
+  }
+  if (lane == 0) bw.tk[bq] = 0;   // re-armed for the workspace's next pass (stream order)
 }
 
 // ----------------------------------------------------------------------------------------

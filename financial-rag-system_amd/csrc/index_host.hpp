@@ -52,6 +52,12 @@ struct Workspace {
   char* qfrag8 = nullptr;
   float* qp8 = nullptr;
   float* eps8 = nullptr;
+  // tier 1 spread over the chip after the 6-bit prescan (certify_kernels.hip band_kernel): the
+  // head's per-query records [32][kBandRec], the slices' lists [32][kBandSlicesMax][kBandPub] and
+  // the per-query arrival tickets [32] (zero between passes)
+  int* bd_rec = nullptr;
+  int* bd_pub = nullptr;
+  int* bd_tk = nullptr;
   // large-k path (k > RAG_MAX_K; lk_* kernels), allocated on first use: sample maxima
   // [32][kLkSampleMax], per query thr / count / round flag, round flags, candidates
   // [32][kLkCap]

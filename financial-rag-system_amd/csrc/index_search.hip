@@ -56,7 +56,7 @@ std::array<WsBuf, 7> lk_buffers(Workspace& w) {
 
 // The buffers every Workspace of `h` holds from creation to destruction (h->dim, groups and
 // max_wgs set), in allocation order (alloc_workspaces: one hipMalloc each; free_workspaces)
-std::array<WsBuf, 22> ws_buffers(const rag_index* h, Workspace& w) {
+std::array<WsBuf, 25> ws_buffers(const rag_index* h, Workspace& w) {
   const size_t G = (size_t)h->groups, Q = kQ, dim = (size_t)h->dim;
   const size_t max_lists = (size_t)std::min(h->max_wgs * kWavesPerWG, kMaxLists);
   return {ws_buf(w.qn, G * Q * dim * 4),
@@ -80,7 +80,11 @@ std::array<WsBuf, 22> ws_buffers(const rag_index* h, Workspace& w) {
           ws_buf(w.t2_tk, 64, true),
           ws_buf(w.qfrag8, h->copy[kCopy8].data ? 4 * (dim / 64) * 64 * 16 : 0),
           ws_buf(w.qp8, h->copy[kCopy8].data ? Q * 4 * 4 : 0),
-          ws_buf(w.eps8, h->copy[kCopy8].data ? Q * 4 : 0)};
+          ws_buf(w.eps8, h->copy[kCopy8].data ? Q * 4 : 0),
+          // (an index that keeps the int8 copy may start a 6-bit one later: ensure_copy6)
+          ws_buf(w.bd_rec, h->copy[kCopy8].data ? Q * kBandRec * 4 : 0),
+          ws_buf(w.bd_pub, h->copy[kCopy8].data ? Q * kBandSlicesMax * kBandPub * 4 : 0),
+          ws_buf(w.bd_tk, h->copy[kCopy8].data ? Q * 4 : 0, true)};
 }
 
 // qprep's extra error-bound term for fp32 storage (prep_kernels.hip qprep_kernel): the exact
@@ -139,6 +143,17 @@ int rescan_grid(const rag_index* h) {
   return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)cap, (int64_t)kRescanMaxWG,
                                                       (int64_t)h->n_cu, n_tiles / 128}));
 }
+
+// Slices per query of the 6-bit route's tier 1 (band_kernel, grid (kBandSlices, Bq)): 4 make 128
+// workgroups of a 32-query pass with ~50 of a query's ~200 qualifying lists each, two gather
+// chunks. Measured at 10M rows with builds that took the count from the environment, same visit,
+// queries/s: 4 slices 63.8-64.2K, 8 (one workgroup per CU, one chunk each) 62.9-63.3K, and in
+// another visit 4 / 8 / 16: 65.2K / 64.6K / 63.5K, against 63.0K with tier 1 inside select
+// (DESIGN.md R17). A compile-time choice (no RAGMI_* knob): 1 .. kBandSlicesMax; 0 builds tier 1
+// inside select's one workgroup per query with the wider gather chunk (kBandLists6), as before
+// band_kernel
+constexpr int kBandSlices = 4;
+static_assert(kBandSlices >= 0 && kBandSlices <= kBandSlicesMax, "bd_pub holds kBandSlicesMax lists");
 
 // RAGMI_SAMPLE_DIV (diagnostic A/B): 1 / the sampled fraction of the shard's tiles
 int sample_div() {
@@ -431,17 +446,27 @@ int launch_search_pass(rag_index* h, Workspace& w, const PassArgs& a, hipStream_
   const ExactStats fb{w.fb_tier, w.fb_cnt, w.t2};
   // select certifies every query's top-k; its fallbacks (list re-scoring, a workgroup-local
   // second pass over the shard) run inside the same launch
-  // (after the 6-bit prescan with the wider gather chunk: its band spans ~200 lists a query)
+  // (after the 6-bit prescan every query takes tier 1, its band spanning ~200 lists: the head
+  // instantiation stops at the verdict and band_kernel spreads tier 1 over the chip)
+  const BandWs bw{w.bd_rec, w.bd_pub, w.bd_tk};
   with_filter(filt, [&](auto f) {
     with_flag(copy == kCopy6, [&](auto six) {
-      constexpr int BL = (D == 384 && decltype(six)::value) ? kBandLists6 : kBandLists;
+      constexpr int BL = !(D == 384 && decltype(six)::value) ? kBandLists
+                         : kBandSlices > 0                   ? kBandHead
+                                                             : kBandLists6;
       select_kernel<D, decltype(f)::value, BL><<<dim3(Bq), dim3(256), 0, st>>>(
           w.part_s, w.part_i, w.heads_s, w.heads_i, w.heads_n, n_lists, h->corpus, a.tags, w.filt,
           w.qfrag, (int)h->count, w.qn, a.k, copy != kNoCopy ? w.eps8 : w.eps, w.seed, fb,
           a.id_offset, a.out_s, a.out_i, a.out_packed, h->rows32,
-          copy != kNoCopy ? w.eps : nullptr);
+          copy != kNoCopy ? w.eps : nullptr, bw);
     });
   });
+  if constexpr (D == 384 && kBandSlices > 0) {
+    if (copy == kCopy6)
+      band_kernel<D><<<dim3(kBandSlices, Bq), dim3(256), 0, st>>>(
+          w.part_s, w.part_i, w.heads_n, n_lists, h->corpus, w.qn, a.k, bw, fb, w.eps,
+          a.id_offset, a.out_s, a.out_i, a.out_packed, h->rows32);
+  }
   // tier 2 of the certificate (rescan_kernel): returns at once unless select marked a query
   // of the pass; otherwise its R workgroups stream the shard once per 16 marked queries.
   // RAGMI_RESCAN_WG (diagnostic A/B) caps R; 0 skips the launch, and mark_unanswered_kernel
