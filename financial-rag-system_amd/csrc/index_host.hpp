@@ -68,6 +68,11 @@ struct Workspace {
   int* lk_need = nullptr;
   int* lk_cand = nullptr;
   float* lk_es = nullptr;       // [32][kLkCap] exact scores of the candidates (lk_rescore)
+  // recommend passes (reco_kernels.hip), allocated on first use: the request's [32][1024] query
+  // block followed by AVERAGE_VECTOR's target [1024], and the request's parameters / the last
+  // hot pass's counters (kRecoPar*)
+  float* reco_q = nullptr;
+  float* reco_par = nullptr;
   hipEvent_t ev_in = nullptr;   // scan-stream order: caller stream -> scan stream -> caller
   hipEvent_t ev_out = nullptr;
   hipStream_t owner = nullptr;  // stream of the last pass that used this slot
@@ -228,6 +233,10 @@ struct rag_index {
   int prescan = 1;        // rag_index_set_prescan: 0 off, 1 auto, 2 always (int8), 3 always 6-bit
   // passes that streamed each copy (rag_index_prescan_passes: their sum; _prescan6_passes)
   int64_t copy_passes[ragmi::kCopies] = {};
+  // recommend passes since creation by path, and the workspace of the last hot one
+  // (rag_index_reco_stats)
+  int64_t reco_hot = 0, reco_full = 0;
+  ragmi::Workspace* reco_last = nullptr;
   int n_cu = 256;
   int max_wgs = 0;        // scan workgroups at full occupancy
   int scan_wgs = 0;       // D <= 384 scan grid cap: 3/4 of the CUs (scan_grid)

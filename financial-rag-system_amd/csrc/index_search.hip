@@ -11,6 +11,7 @@
 #include "certify_kernels.hip"
 #include "merge_kernels.hip"
 #include "largek_kernels.hip"
+#include "reco_kernels.hip"
 #include "reselect_kernels.hip"
 #include "formula_kernels.hip"
 
@@ -52,6 +53,13 @@ std::array<WsBuf, 7> lk_buffers(Workspace& w) {
           ws_buf(w.lk_cnt, Q * 4),                 ws_buf(w.lk_again, Q * 4),
           ws_buf(w.lk_need, 64),                   ws_buf(w.lk_cand, Q * kLkCap * 4),
           ws_buf(w.lk_es, Q * kLkCap * 4)};
+}
+
+// The recommend buffers, allocated together on first use (ensure_reco): the query block
+// [32][1024] + the AVERAGE_VECTOR target [1024], and the parameter words (kRecoPar*)
+constexpr size_t kRecoQFloats = (size_t)(kQ + 1) * 1024;
+std::array<WsBuf, 2> reco_buffers(Workspace& w) {
+  return {ws_buf(w.reco_q, kRecoQFloats * 4), ws_buf(w.reco_par, 64, true)};
 }
 
 // The buffers every Workspace of `h` holds from creation to destruction (h->dim, groups and
@@ -691,6 +699,31 @@ int packed_ids_args(const rag_index* h, int64_t id_offset) {
   return RAG_OK;
 }
 
+// The workspace of a pass of Bq queries on stream `st` (lock held): the slot bound to `st`, a
+// free one, or — every slot being bound to another stream whose last pass may still be running —
+// the least recently used one after a device drain; bound to `st`, its CU count current
+int take_workspace(rag_index* h, hipStream_t st, int Bq, Workspace** out) {
+  Workspace* lru = nullptr;
+  Workspace* wp = pick_slot(h->ws, st, lru);
+  if (!wp) {
+    RAG_HIP(hipDeviceSynchronize());
+    wp = lru;
+  }
+  Workspace& w = *wp;
+  const uint64_t gen = g_stream_gen.load(std::memory_order_acquire);
+  if (!w.used || w.owner != st || w.cus == 0 || w.cus_gen != gen) {
+    w.cus = stream_cus(h, st);
+    w.cus_gen = gen;
+  }
+  w.used = true;
+  w.owner = st;
+  w.tick = ++h->ws_tick;
+  h->last_ws = &w;
+  h->last_bq = Bq;
+  *out = wp;
+  return RAG_OK;
+}
+
 // full: the full exact path for every query (rag_index_search_full); it is also taken for
 // k > RAG_MAX_K_LARGE (unpacked output only: the exchange merge holds at most that many)
 // tags: the column the passes filter on: the stored tags, or rag_index_search_view's view
@@ -705,24 +738,9 @@ int search_locked(rag_index* h, const float* q, int B, int k, const uint32_t* fi
   const int per_pass = large ? kQ : kQ * h->groups;
   for (int b0 = 0; b0 < B; b0 += per_pass) {
     const int Bq = std::min(per_pass, B - b0);
-    Workspace* lru = nullptr;
-    Workspace* wp = pick_slot(h->ws, st, lru);
-    if (!wp) {
-      // every slot is bound to another stream whose last pass may still be running
-      RAG_HIP(hipDeviceSynchronize());
-      wp = lru;
-    }
+    Workspace* wp = nullptr;
+    if (const int rc = take_workspace(h, st, Bq, &wp)) return rc;
     Workspace& w = *wp;
-    const uint64_t gen = g_stream_gen.load(std::memory_order_acquire);
-    if (!w.used || w.owner != st || w.cus == 0 || w.cus_gen != gen) {
-      w.cus = stream_cus(h, st);
-      w.cus_gen = gen;
-    }
-    w.used = true;
-    w.owner = st;
-    w.tick = ++h->ws_tick;
-    h->last_ws = &w;
-    h->last_bq = Bq;
     const PassArgs a{q + (int64_t)b0 * h->dim,
                      Bq,
                      k,
@@ -740,6 +758,200 @@ int search_locked(rag_index* h, const float* q, int B, int k, const uint32_t* fi
     if (rc) return rc;
   }
   return RAG_OK;
+}
+
+// ---- recommend queries (reco_kernels.hip; the contract: ragmi.h "Recommend queries") ----
+
+// one request's examples (device pointers, [n][dim] fp32) and its strategy
+struct RecoArgs {
+  const float* pos;
+  int P;
+  const float* neg;
+  int N;
+  int strat;
+};
+
+// the argument rules of the recommend entry points, checked before any HIP call
+int reco_args(const RecoArgs& r, bool average_ok) {
+  static_assert(kRecoSide == RAG_RECO_MAX_SIDE && kRecoAverage == RAG_RECO_AVERAGE &&
+                    kRecoBest == RAG_RECO_BEST && kRecoSum == RAG_RECO_SUM && 2 * kRecoSide == kQ,
+                "reco_kernels.hip's slots and strategies");
+  if (r.P < 0 || r.N < 0 || r.P > RAG_RECO_MAX_SIDE || r.N > RAG_RECO_MAX_SIDE)
+    return ragmi::fail(RAG_ERANGE,
+                       "recommend: a side holds 0 to RAG_RECO_MAX_SIDE=16 examples");
+  if (r.strat != RAG_RECO_BEST && r.strat != RAG_RECO_SUM &&
+      !(average_ok && r.strat == RAG_RECO_AVERAGE))
+    return ragmi::fail(RAG_EINVAL, average_ok
+                                       ? "recommend: unknown strategy (RAG_RECO_AVERAGE=0, "
+                                         "RAG_RECO_BEST=1, RAG_RECO_SUM=2)"
+                                       : "recommend: bounds exist for RAG_RECO_BEST=1 and "
+                                         "RAG_RECO_SUM=2 only");
+  if (r.P + r.N == 0) return ragmi::fail(RAG_EINVAL, "recommend: needs at least one example");
+  if (r.strat == RAG_RECO_AVERAGE && r.P == 0)
+    return ragmi::fail(RAG_EINVAL, "recommend: RAG_RECO_AVERAGE needs a positive example");
+  if ((r.P > 0 && !r.pos) || (r.N > 0 && !r.neg))
+    return ragmi::fail(RAG_EINVAL, "recommend: a NULL example pointer");
+  return RAG_OK;
+}
+
+int ensure_reco(Workspace& w) {
+  if (w.reco_q) return RAG_OK;
+  if (ragmi::ws_alloc_all(reco_buffers(w)) != hipSuccess) {
+    (void)hipGetLastError();
+    return ragmi::fail(RAG_ENOMEM, "recommend workspace allocation failed");
+  }
+  return RAG_OK;
+}
+
+// the request's query block in w: slots assembled, prepared by qprep (qn, qfrag, eps), and the
+// request's parameters
+template <int D>
+int launch_reco_prep(rag_index* h, Workspace& w, const RecoArgs& r, hipStream_t st) {
+  static_assert(D <= 1024, "reco_q holds [32][1024]");
+  if (const int rc = ensure_reco(w)) return rc;
+  reco_assemble_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(r.pos, r.P, r.neg, r.N, w.reco_q);
+  qprep_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(w.reco_q, kQ, nullptr, w.qn, w.qfrag, w.filt,
+                                                  w.eps, store_eps(h));
+  reco_prep_kernel<<<dim3(1), dim3(64), 0, st>>>(w.eps, r.P, r.N, w.reco_par);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// go(strategy tag) with the strategy as a compile-time constant (BEST or SUM)
+template <typename F>
+auto with_reco_strategy(int strat, F&& f) {
+  if (strat == kRecoBest) return f(std::integral_constant<int, kRecoBest>{});
+  return f(std::integral_constant<int, kRecoSum>{});
+}
+
+// The hot pass of one BEST / SUM request, k <= RAG_MAX_K_LARGE (reco_kernels.hip): prep, the
+// sample and its bound, then kLkRounds (collect, rescore, final) launch triples. a.filt: the
+// request's (mask, value) pair or nullptr. Always over the fp16 rows.
+template <int D>
+int launch_reco_hot(rag_index* h, Workspace& w, const RecoArgs& r, const PassArgs& a,
+                    hipStream_t st) {
+  if (const int rc = ensure_lk(w)) return rc;
+  if (const int rc = launch_reco_prep<D>(h, w, r, st)) return rc;
+  const int k = a.k;
+  const int n_tiles = (int)((h->count + 15) / 16);
+  // the large-k pass's sample (launch_large_k_pass)
+  const int n_sample = n_tiles == 0 ? 0 : std::min({n_tiles, std::max(4 * k, n_tiles / 32),
+                                                    kLkSampleMax});
+  const int cgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2 * h->n_cu, (n_tiles + 3) / 4));
+  const int per_wg = reco_rescore_per_wg(r.P + r.N);
+  const int rgrid = (kLkCap + per_wg - 1) / per_wg;
+  with_filter(a.filt, [&](auto f) {
+    with_reco_strategy(r.strat, [&](auto s) {
+      constexpr bool F = decltype(f)::value;
+      constexpr int STRAT = decltype(s)::value;
+      if (n_sample > 0)
+        reco_sample_kernel<D, F, STRAT><<<dim3((n_sample + 3) / 4), dim3(256), 0, st>>>(
+            h->corpus, a.tags, a.filt, w.qfrag, w.eps, w.reco_par, r.P, r.N, (int)h->count,
+            n_tiles, n_sample, w.lk_smax);
+      // T = the k-th largest sample maximum (L is a bound already: the eps it subtracts is 0)
+      lk_bound_kernel<<<dim3(1), dim3(256), 0, st>>>(w.lk_smax, n_sample, k, w.reco_par,
+                                                     w.lk_thr, w.lk_cnt, w.lk_again, w.lk_need);
+      for (int round = 0; round < kLkRounds; ++round) {
+        reco_collect_kernel<D, F, STRAT><<<dim3(cgrid), dim3(256), 0, st>>>(
+            h->corpus, a.tags, a.filt, w.qfrag, w.eps, w.reco_par, r.P, r.N, (int)h->count,
+            n_tiles, w.lk_thr, w.lk_cnt, w.lk_cand, w.lk_again, w.lk_need, round);
+        reco_rescore_kernel<D><<<dim3(rgrid), dim3(256), 0, st>>>(
+            h->corpus, w.qn, r.P, r.N, r.strat, w.lk_cnt, w.lk_cand, w.lk_again, w.lk_need, round,
+            w.lk_es, h->rows32, w.reco_par);
+        lk_final_kernel<D><<<dim3(1), dim3(256), 0, st>>>(
+            h->corpus, w.qn, k, w.lk_cnt, w.lk_cand, w.lk_es, w.reco_par, w.lk_thr, w.lk_again,
+            w.lk_need, round, w.fb_tier, w.fb_cnt, a.id_offset, a.out_s, a.out_i, nullptr,
+            h->rows32);
+      }
+    });
+  });
+  RAG_HIP(hipGetLastError());
+  ++h->reco_hot;
+  h->reco_last = &w;
+  return RAG_OK;
+}
+
+// The full pass of one BEST / SUM request, any k: every row's exact combined score, the full
+// pass's stable sort and emit (launch_full_pass). No thresholds: nothing can overflow.
+template <int D>
+int launch_reco_full(rag_index* h, Workspace& w, const RecoArgs& r, const PassArgs& a,
+                     hipStream_t st) {
+  if (const int rc = launch_reco_prep<D>(h, w, r, st)) return rc;
+  const int n = (int)h->count, k = a.k;
+  const dim3 egrid((unsigned)std::min<int64_t>(1024, ((int64_t)k + 255) / 256));
+  StreamScratch scratch(st);
+  ++h->reco_full;
+  if (n == 0) {
+    RAG_HIP(scratch.alloc(4));
+    RAG_HIP(hipMemsetAsync(scratch.p, 0, 4, st));
+    full_emit_kernel<<<egrid, dim3(256), 0, st>>>(nullptr, nullptr,
+                                                  reinterpret_cast<const int*>(scratch.p), k,
+                                                  a.id_offset, a.out_s, a.out_i, nullptr);
+    RAG_HIP(hipGetLastError());
+    return RAG_OK;
+  }
+  size_t tmp_bytes = 0;
+  RAG_HIP(hipcub::DeviceRadixSort::SortPairsDescending(
+      nullptr, tmp_bytes, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
+      static_cast<const int*>(nullptr), static_cast<int*>(nullptr), n, 0, 32, st));
+  const size_t nb = (size_t)n * 4;
+  const size_t m_off = 4 * nb, t_off = m_off + 256;
+  RAG_HIP(scratch.alloc(t_off + tmp_bytes));
+  char* const buf = scratch.p;
+  uint32_t* k_in = reinterpret_cast<uint32_t*>(buf);
+  uint32_t* k_out = reinterpret_cast<uint32_t*>(buf + nb);
+  int* v_in = reinterpret_cast<int*>(buf + 2 * nb);
+  int* v_out = reinterpret_cast<int*>(buf + 3 * nb);
+  int* n_match = reinterpret_cast<int*>(buf + m_off);
+  RAG_HIP(hipMemsetAsync(n_match, 0, 4, st));
+  // one wave per reco_group rows per step; up to 8 workgroups per CU (launch_full_pass)
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(8 * h->n_cu, (n + 3) / 4));
+  with_filter(a.filt, [&](auto f) {
+    reco_full_score_kernel<D, decltype(f)::value><<<dim3(grid), dim3(256), 0, st>>>(
+        h->corpus, a.tags, a.filt, w.qn, r.P, r.N, r.strat, n, h->rows32, k_in, v_in, n_match);
+  });
+  if (hipGetLastError() != hipSuccess ||
+      sort_pairs_desc(buf + t_off, tmp_bytes, k_in, k_out, v_in, v_out, n, st) != hipSuccess)
+    return ragmi::fail(RAG_EHIP, "recommend full pass: score / sort launch failed");
+  full_emit_kernel<<<egrid, dim3(256), 0, st>>>(k_out, v_out, n_match, k, a.id_offset, a.out_s,
+                                                a.out_i, nullptr);
+  RAG_HIP(hipGetLastError());
+  (void)hipMemsetAsync(w.fb_tier, 0, 4, st);   // certified by construction
+  return RAG_OK;
+}
+
+// AVERAGE_VECTOR's target of a request in w.reco_q's tail (reco_average_kernel)
+template <int D>
+int launch_reco_average(rag_index* h, Workspace& w, const RecoArgs& r, hipStream_t st) {
+  if (const int rc = launch_reco_prep<D>(h, w, r, st)) return rc;
+  reco_average_kernel<<<grid1d(D, 256), dim3(256), 0, st>>>(w.qn, D, r.P, r.N,
+                                                            w.reco_q + (size_t)kQ * 1024);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// one recommend request under the handle's lock; tags: the stored tags or a filter view
+int recommend_locked(rag_index* h, const RecoArgs& r, int k, const uint32_t* filt,
+                     const uint32_t* tags, int64_t id_offset, bool full, float* out_s,
+                     int64_t* out_i, hipStream_t st) {
+  Workspace* wp = nullptr;
+  if (const int rc = take_workspace(h, st, 1, &wp)) return rc;
+  Workspace& w = *wp;
+  if (r.strat == kRecoAverage) {
+    // v is the query of the ordinary exact search, every route of it included
+    const int rc = with_dim(h->dim, [&](auto d) {
+      return launch_reco_average<decltype(d)::value>(h, w, r, st);
+    });
+    if (rc) return rc;
+    return search_locked(h, w.reco_q + (size_t)kQ * 1024, 1, k, filt, id_offset, out_s, out_i,
+                         nullptr, st, full, tags);
+  }
+  const PassArgs a{nullptr, 1, k, filt, tags, id_offset, out_s, out_i, nullptr};
+  full = full || k > RAG_MAX_K_LARGE;
+  return with_dim(h->dim, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    return full ? launch_reco_full<D>(h, w, r, a, st) : launch_reco_hot<D>(h, w, r, a, st);
+  });
 }
 
 // Diagnostic A/B of scan variants (see scan_kernel's knobs). Returns avg device ms/launch.
@@ -962,6 +1174,7 @@ void ragmi::free_workspaces(rag_index* h) {
   for (auto& w : h->ws) {
     ws_free_all(ws_buffers(h, w));
     ws_free_all(lk_buffers(w));
+    ws_free_all(reco_buffers(w));
     if (w.ev_in) (void)hipEventDestroy(w.ev_in);
     if (w.ev_out) (void)hipEventDestroy(w.ev_out);
   }
@@ -1059,6 +1272,108 @@ int rag_index_search_view(rag_index_t* h, const float* q, int B, int k, const ui
   if (const int rc = launch_filter_view(h, progs, words, n_programs, v, st)) return rc;
   return search_locked(h, q, B, k, filters, id_offset, out_s, out_i, out_packed, st,
                        (flags & RAG_SEARCH_FULL) != 0, v);
+}
+
+// ---- recommend queries (reco_kernels.hip) ----
+
+int rag_index_recommend(rag_index_t* h, const float* pos, int n_pos, const float* neg, int n_neg,
+                        int strategy, int k, const uint32_t* progs, int64_t words, int n_programs,
+                        const uint32_t* filter, int64_t id_offset, int flags, float* out_s,
+                        int64_t* out_i, void* stream) {
+  ragmi::clear_error();
+  const RecoArgs r{pos, n_pos, neg, n_neg, strategy};
+  if (const int rc = reco_args(r, true)) return rc;
+  if (k < 1) return ragmi::fail(RAG_ERANGE, "recommend: k must be >= 1");
+  if (flags & ~RAG_SEARCH_FULL) return ragmi::fail(RAG_EINVAL, "recommend: unknown flags");
+  if (progs) {
+    if (const int rc = view_args(progs, words, n_programs)) return rc;
+  } else if (words != 0 || n_programs != 0) {
+    return ragmi::fail(RAG_EINVAL, "recommend: programs is NULL but words / n_programs are not 0");
+  }
+  if (!out_s || !out_i) return ragmi::fail(RAG_EINVAL, "recommend: a NULL output pointer");
+  if (!h) return ragmi::fail(RAG_EINVAL, "recommend: index is NULL");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  // view and passes under this one hold of the lock (rag_index_search_view)
+  const uint32_t* tags = h->tags;
+  if (progs) {
+    uint32_t* v = nullptr;
+    if (const int rc = acquire_view(h, st, &v)) return rc;
+    if (const int rc = launch_filter_view(h, progs, words, n_programs, v, st)) return rc;
+    tags = v;
+  }
+  return recommend_locked(h, r, k, filter, tags, id_offset, (flags & RAG_SEARCH_FULL) != 0, out_s,
+                          out_i, st);
+}
+
+int rag_index_reco_bounds(rag_index_t* h, const float* pos, int n_pos, const float* neg, int n_neg,
+                          int strategy, const int64_t* rows_dev, int64_t n, float* out_lo,
+                          float* out_hi, void* stream) {
+  ragmi::clear_error();
+  const RecoArgs r{pos, n_pos, neg, n_neg, strategy};
+  if (const int rc = reco_args(r, false)) return rc;
+  if (n < 0 || (n > 0 && (!rows_dev || !out_lo || !out_hi)))
+    return ragmi::fail(RAG_EINVAL, "reco_bounds: a NULL row or output pointer");
+  if (n > 0x7fffffff) return ragmi::fail(RAG_ERANGE, "reco_bounds: n too large for one call");
+  if (!h) return ragmi::fail(RAG_EINVAL, "reco_bounds: index is NULL");
+  if (n == 0) return RAG_OK;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  Workspace* wp = nullptr;
+  if (const int rc = take_workspace(h, st, 1, &wp)) return rc;
+  Workspace& w = *wp;
+  return with_dim(h->dim, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (const int rc = launch_reco_prep<D>(h, w, r, st)) return rc;
+    with_reco_strategy(r.strat, [&](auto s) {
+      reco_bounds_kernel<D, decltype(s)::value><<<dim3((unsigned)n), dim3(64), 0, st>>>(
+          h->corpus, w.qfrag, w.eps, w.reco_par, r.P, r.N, rows_dev, n, h->count, out_lo, out_hi);
+    });
+    RAG_HIP(hipGetLastError());
+    return (int)RAG_OK;
+  });
+}
+
+int rag_index_reco_vector(rag_index_t* h, const float* pos, int n_pos, const float* neg, int n_neg,
+                          float* out_v, void* stream) {
+  ragmi::clear_error();
+  const RecoArgs r{pos, n_pos, neg, n_neg, RAG_RECO_AVERAGE};
+  if (const int rc = reco_args(r, true)) return rc;
+  if (!out_v) return ragmi::fail(RAG_EINVAL, "reco_vector: a NULL output pointer");
+  if (!h) return ragmi::fail(RAG_EINVAL, "reco_vector: index is NULL");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  Workspace* wp = nullptr;
+  if (const int rc = take_workspace(h, st, 1, &wp)) return rc;
+  const int rc = with_dim(h->dim, [&](auto d) {
+    return launch_reco_average<decltype(d)::value>(h, *wp, r, st);
+  });
+  if (rc) return rc;
+  RAG_HIP(hipMemcpyAsync(out_v, wp->reco_q + (size_t)kQ * 1024, (size_t)h->dim * 4,
+                         hipMemcpyDeviceToDevice, st));
+  return RAG_OK;
+}
+
+int rag_index_reco_stats(rag_index_t* h, int64_t out[4]) {
+  ragmi::clear_error();
+  if (!h || !out) return ragmi::fail(RAG_EINVAL, "reco_stats: bad args");
+  std::lock_guard<std::mutex> lk(h->mu);
+  out[0] = h->reco_hot;
+  out[1] = h->reco_full;
+  out[2] = out[3] = 0;
+  if (h->reco_last) {
+    RAG_HIP(hipSetDevice(h->device));
+    RAG_HIP(hipDeviceSynchronize());
+    int32_t c[2];
+    RAG_HIP(hipMemcpy(c, reinterpret_cast<const int32_t*>(h->reco_last->reco_par) + kRecoParCnt,
+                      sizeof(c), hipMemcpyDeviceToHost));
+    out[2] = c[0];
+    out[3] = c[1];
+  }
+  return RAG_OK;
 }
 
 // ---- MMR re-selection (mmr_kernel, reselect_kernels.hip) ----

@@ -161,6 +161,16 @@ INDEX_API = {
     "rag_index_search_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp,
                                              ctypes.c_int64, ctypes.c_int, c_vp, ctypes.c_int64,
                                              ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rag_index_recommend": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int64,
+                                           ctypes.c_int, c_vp, ctypes.c_int64, ctypes.c_int, c_vp,
+                                           c_vp, c_vp]),
+    "rag_index_reco_bounds": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int,
+                                             ctypes.c_int, c_vp, ctypes.c_int64, c_vp, c_vp,
+                                             c_vp]),
+    "rag_index_reco_vector": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp,
+                                             c_vp]),
+    "rag_index_reco_stats": (ctypes.c_int, [c_vp, c_i64p]),
     "rag_index_select_rows_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp,
                                                   ctypes.c_int64, c_vp, c_vp]),
     "rag_shardset_search_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp,

@@ -42,6 +42,12 @@ def _norm_id(pid):
     raise ValueError(f"unsupported point id type {type(pid)!r}")
 
 
+def _is_vector(example) -> bool:
+    """A recommend example is a point id (what _norm_id takes: an int, a UUID, a str) or,
+    being anything else, a vector."""
+    return not isinstance(example, (bool, int, np.integer, uuid.UUID, str))
+
+
 def parse_selector(points_selector):
     """The `points_selector` of QdrantClient.delete -> ("ids", [normalised ids]) or
     ("filter", Filter): a plain list of ids, a PointIdsList, a FilterSelector or a bare
@@ -397,6 +403,65 @@ class Collection:
         with self.lock:
             return self._points(self.search_mmr(queries, limits, filters, diversity, candidates),
                                 with_vectors)
+
+    def search_recommend(self, requests: list):
+        """Recommend queries. `requests`: per request (positive, negative,
+        strategy, compiled filter, limit) — the examples point ids and / or vectors, as
+        recommend_params returns them. Under the lock: every id resolves to its row (an unknown
+        id is a ValueError naming it) and the example rows are gathered on the device in their
+        stored form (fp32 storage: the fp32 row; fp16: the halves widened), from where an id
+        example is a caller's vector. Each request is one index.recommend call for limit + m
+        hits, m its distinct id examples, with rescue: the example rows are dropped and the
+        list is cut to limit, so example points never appear and `limit` hits still arrive.
+        limit < 1, an empty collection and a filter nothing can match give [] without a launch.
+        Returns per request [(row, score)], best first."""
+        if not hasattr(self.index, "recommend"):               # a ShardSet has none
+            raise NotImplementedError("recommend over a shard set is not built")
+        with self.lock:
+            out = []
+            for pos, neg, strategy, c, limit in requests:
+                # position in its side -> row, for the examples given by id
+                by_id = [{j: self._example_row(x) for j, x in enumerate(side)
+                          if not _is_vector(x)} for side in (pos, neg)]
+                own = set(by_id[0].values()) | set(by_id[1].values())
+                count = self.index.count
+                if limit < 1 or count == 0 or c is None:
+                    out.append([])
+                    continue
+                sides = []
+                for side, rows in zip((pos, neg), by_id):
+                    vecs = list(side)
+                    if rows:
+                        got = self.index.gather_rows(np.asarray(list(rows.values()), np.int64))
+                        stored = got[1] if got[1] is not None else \
+                            got[0].view(torch.float16).float()
+                        for j, v in zip(rows, stored):
+                            vecs[j] = v
+                    sides.append(stack_queries(vecs, self.dim) if vecs else None)
+                view = {}
+                if isinstance(c, FilterProgram):
+                    view = {"programs": pack_view([c]), "filters": (1, 1)}
+                elif tuple(c) != (0, 0):
+                    view = {"filters": tuple(c)}
+                k = min(int(limit) + len(own), count)
+                hits = hits_of(*(t.unsqueeze(0) for t in self.index.recommend(
+                    sides[0], sides[1], strategy, k, rescue=True, **view)))[0]
+                out.append([h for h in hits if h[0] not in own][:int(limit)])
+            return out
+
+    def _example_row(self, pid) -> int:
+        """The row of example point `pid`, or ValueError naming the id. Under the lock."""
+        r = self.id_to_row.get(_norm_id(pid))
+        if r is None:
+            raise ValueError(f"recommend: example point {pid!r} is not in collection "
+                             f"{self.name!r}")
+        return r
+
+    def search_points_recommend(self, requests: list, with_vectors=False):
+        """search_recommend with every hit resolved to its ScoredPoint under the same hold of
+        the lock (_points)."""
+        with self.lock:
+            return self._points(self.search_recommend(requests), with_vectors)
 
     def search_fusion(self, requests: list):
         """Fusion queries. `requests`: per request (rrf_k, [(vector, Filter or

@@ -39,6 +39,33 @@ PRESCAN_ALWAYS6 = 3            # RAG_PRESCAN_ALWAYS6: every k <= 32 pass over th
 PRESCAN_MIN_ROWS = 500000      # RAG_PRESCAN_MIN_ROWS: auto mode's smallest shard
 PRESCAN6_MIN_ROWS = 4000000    # RAG_PRESCAN6_MIN_ROWS: auto mode's smallest 6-bit shard
 CREATE_DIAGNOSTIC = 0x100          # RAG_CREATE_DIAGNOSTIC: honour the RAGMI_* A/B knobs
+RECO_AVERAGE, RECO_BEST, RECO_SUM = 0, 1, 2   # RAG_RECO_AVERAGE / _BEST / _SUM
+RECO_MAX_SIDE = 16                 # RAG_RECO_MAX_SIDE: examples per side of a recommend request
+RECO_STRATEGIES = {"average_vector": RECO_AVERAGE, "best_score": RECO_BEST,
+                   "sum_scores": RECO_SUM}
+
+
+class RecoStats(NamedTuple):
+    """rag_index_reco_stats: recommend passes since creation by path, and the last hot pass's
+    counted candidates (of its last round) and rounds."""
+    hot: int
+    full: int
+    candidates: int
+    rounds: int
+
+
+def reco_strategy(strategy) -> int:
+    """A recommend strategy — None (average_vector), a RecommendStrategy, its value, or a
+    RAG_RECO_* code — as its code; ValueError for anything else."""
+    s = getattr(strategy, "value", strategy)
+    if s is None:
+        return RECO_AVERAGE
+    if isinstance(s, str) and s in RECO_STRATEGIES:
+        return RECO_STRATEGIES[s]
+    if isinstance(s, (int, np.integer)) and not isinstance(s, bool) and \
+            int(s) in RECO_STRATEGIES.values():
+        return int(s)
+    raise ValueError(f"unknown recommend strategy {strategy!r}: one of {sorted(RECO_STRATEGIES)}")
 
 
 def _stream_ptr(device: torch.device) -> int:
@@ -361,6 +388,100 @@ class FlatIndex(ListOps):
                 q[redo], k, None if f is None else f[redo], id_offset, full=True, programs=p,
                 n_programs=U))
         return out
+
+    # ---------------------------------------------------------------- recommend
+    def _reco_sides(self, pos, neg, strategy, average_ok=True):
+        """(pos tensor or None, P, neg tensor or None, N, strategy code) of a recommend
+        request, refused as the C ABI refuses it, but as ValueError."""
+        code = reco_strategy(strategy)
+        sides = []
+        for name, x in (("positive", pos), ("negative", neg)):
+            if x is None or len(x) == 0:
+                sides.append((None, 0))
+                continue
+            t = _as_dev(x, torch.float32, self.device)
+            if t.dim() == 1:
+                t = t.unsqueeze(0)
+            if t.dim() != 2 or t.shape[1] != self.dim:
+                raise ValueError(f"{name} examples must be [n, {self.dim}]")
+            if t.shape[0] > RECO_MAX_SIDE:
+                raise ValueError(f"at most {RECO_MAX_SIDE} {name} examples (RAG_RECO_MAX_SIDE), "
+                                 f"got {t.shape[0]}")
+            sides.append((t, int(t.shape[0])))
+        (p, P), (n, N) = sides
+        if P + N == 0:
+            raise ValueError("a recommend request needs at least one example")
+        if code == RECO_AVERAGE and (P == 0 or not average_ok):
+            raise ValueError("average_vector needs a positive example" if average_ok else
+                             "bounds exist for best_score and sum_scores only")
+        return p, P, n, N, code
+
+    def recommend(self, pos, neg, strategy, k: int, filters=None, programs=None,
+                  full: bool = False, rescue: bool = False, n_programs: int | None = None,
+                  id_offset: int = 0):
+        """One recommend request (rag_index_recommend; the contract: include/ragmi.h "Recommend
+        queries"): `pos` / `neg` the example vectors [n, dim] (None or empty: none; at most 16
+        a side), `strategy` a RecommendStrategy, its value or its RAG_RECO_* code. Returns
+        (scores fp32 [k], ids int64 [k]) as cuda tensors, the k best rows by (score desc, row
+        asc), -inf / -1 past the matching rows, enqueued on the current stream. The example rows
+        themselves are not excluded (Collection.search_recommend does that).
+        `filters`: None or one (tag_mask, tag_value) pair; `programs`: a filter-program blob,
+        `filters` then being a pair over the view's bits, as in search. full=True forces the
+        full pass. rescue=True: a request the hot pass left unanswered (more than 16384 rows
+        within its bounds of the k-th best) is re-answered on the full pass and counted in
+        `rescued` (rescue_unanswered); reads the list back, so it synchronises."""
+        p, P, n, N, code = self._reco_sides(pos, neg, strategy)
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        f = None
+        if filters is not None:
+            f = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(filters, dtype=np.uint32).reshape(2)).view(np.int32)).to(self.device)
+        view = None if programs is None else view_blob(programs, n_programs, self.device)
+        def launch(full_pass: bool):
+            s = torch.empty((1, k), dtype=torch.float32, device=self.device)
+            ids = torch.empty((1, k), dtype=torch.int64, device=self.device)
+            vp, words, U = (None, 0, 0) if view is None else (view[0].data_ptr(), view[1], view[2])
+            check(self._L.rag_index_recommend(
+                self._h, p.data_ptr() if P else None, P, n.data_ptr() if N else None, N, code,
+                int(k), vp, words, U, f.data_ptr() if f is not None else None, int(id_offset),
+                SEARCH_FULL if full_pass else 0, s.data_ptr(), ids.data_ptr(),
+                _stream_ptr(self.device)))
+            return s, ids
+
+        s, ids = launch(full)
+        if rescue and not full:
+            rescue_unanswered(self, s, ids, lambda redo: launch(True))
+        return s[0], ids[0]
+
+    def reco_bounds(self, pos, neg, strategy, rows):
+        """(lo, hi) fp32 [n]: the hot pass's certified bounds of the exact combined score of
+        stored rows `rows` (best_score or sum_scores; rag_index_reco_bounds, diagnostic)."""
+        p, P, n, N, code = self._reco_sides(pos, neg, strategy, average_ok=False)
+        r = _as_dev(rows, torch.int64, self.device).reshape(-1)
+        lo = torch.empty((r.numel(),), dtype=torch.float32, device=self.device)
+        hi = torch.empty_like(lo)
+        check(self._L.rag_index_reco_bounds(
+            self._h, p.data_ptr() if P else None, P, n.data_ptr() if N else None, N, code,
+            r.data_ptr() if r.numel() else None, r.numel(), lo.data_ptr(), hi.data_ptr(),
+            _stream_ptr(self.device)))
+        return lo, hi
+
+    def reco_vector(self, pos, neg=None) -> torch.Tensor:
+        """average_vector's target v fp32 [dim] (rag_index_reco_vector, diagnostic)."""
+        p, P, n, N, _ = self._reco_sides(pos, neg, RECO_AVERAGE)
+        v = torch.empty((self.dim,), dtype=torch.float32, device=self.device)
+        check(self._L.rag_index_reco_vector(self._h, p.data_ptr(), P,
+                                            n.data_ptr() if N else None, N, v.data_ptr(),
+                                            _stream_ptr(self.device)))
+        return v
+
+    def reco_stats(self) -> "RecoStats":
+        """(hot passes, full passes, candidates the last hot pass counted, rounds it ran) —
+        rag_index_reco_stats; synchronises the device."""
+        out = (ctypes.c_int64 * 4)()
+        check(self._L.rag_index_reco_stats(self._h, out))
+        return RecoStats(*[int(x) for x in out])
 
     # ---------------------------------------------------------------- MMR
     def mmr(self, cand_scores, cand_rows, k: int, diversity, ncand=None,

@@ -9,8 +9,8 @@ Drop-in for the calls the reference makes on `qdrant_client.QdrantClient`:
                                           main.py:232-237, main2.py:163
 plus query_batch_points (one GPU scan for a whole micro-batch; main2.py:281-295 stage 2),
 the prefetch routes of query_points (FusionQuery / RrfQuery, FormulaQuery), its OrderByQuery
-route, scroll (in storage order, or order_by a range field), facet,
-count (also filtered), retrieve, delete (by ids or by filter) and delete_collection.
+and RecommendQuery routes, recommend (the legacy spelling of the latter), scroll (in storage
+order, or order_by a range field), facet, count (also filtered), retrieve, delete (by ids or by filter) and delete_collection.
 
 `url` is accepted and ignored: the collection lives in this process's GPU memory (the
 Qdrant service of docker-compose.yml:22 is replaced, not contacted). `path=` plays the role
@@ -38,7 +38,7 @@ from .coalesce import Coalescer                                           # noqa
 from .collection import Collection, _norm_id, parse_selector, stack_queries  # noqa: F401
 from .filters import (DEFAULT_TAG_FIELDS, PayloadTags, UnsupportedFilter,  # noqa: F401
                       compile_filter)
-from .index import FUSION_MAX_LISTS, MAX_K, MMR_MAX_CANDIDATES
+from .index import FUSION_MAX_LISTS, MAX_K, MMR_MAX_CANDIDATES, RECO_MAX_SIDE, reco_strategy
 from .shardset import parse_devices
 
 
@@ -150,6 +150,8 @@ def prefetch_lists(prefetch, what: str, to: str, verb: str) -> list:
         vec, mmr = nearest_of(p.query)
         if isinstance(vec, models.OrderByQuery):
             raise ValueError(f"prefetch[{n}]: an OrderByQuery inside a Prefetch is not built")
+        if isinstance(vec, models.RecommendQuery):
+            raise ValueError(f"prefetch[{n}]: a RecommendQuery inside a Prefetch is not built")
         if vec is None or is_fusion(vec) or isinstance(vec, models.FormulaQuery):
             raise ValueError(f"prefetch[{n}] needs a query: a vector or a NearestQuery")
         if mmr is not None:
@@ -178,15 +180,19 @@ def formula_params(query, prefetch, limit, query_filter=None) -> list:
 
 FUSION, FORMULA, MMR, PLAIN = "fusion", "formula", "mmr", "plain"   # the routes of a request
 ORDER = "order"
+RECOMMEND = "recommend"
 
 
 def route_of(query, prefetch=None) -> str:
     """The route of a request, decided once: FORMULA (prefetched candidates re-scored by a
     FormulaQuery), FUSION (prefetched lists fused; every other use of a prefetch goes there to
     be refused), ORDER (an OrderByQuery: no vector, the points by a range field's value), MMR (a
-    NearestQuery with an Mmr) or PLAIN."""
+    NearestQuery with an Mmr), RECOMMEND (a RecommendQuery, with or without a prefetch: it
+    refuses the prefetch itself) or PLAIN."""
     if isinstance(query, models.FormulaQuery):
         return FORMULA
+    if isinstance(query, models.RecommendQuery):
+        return RECOMMEND
     if isinstance(query, models.OrderByQuery):
         return ORDER
     if prefetch is not None or isinstance(query, (models.FusionQuery, models.RrfQuery)):
@@ -205,6 +211,54 @@ def order_params(col: Collection, req) -> tuple:
     return req.query.order_by, col.compile_filter(req.filter), int(req.limit)
 
 
+def recommend_params(query, limit) -> tuple:
+    """(positive, negative, strategy code) of a recommend request — the examples as lists of
+    point ids and / or vectors — or ValueError: the query must be a RecommendQuery over a
+    RecommendInput, each side a list of at most RAG_RECO_MAX_SIDE examples, with at least one
+    example in all and, for average_vector (the default), a positive one; the strategy must be a
+    RecommendStrategy; the limit must be an int."""
+    if not isinstance(query, models.RecommendQuery) or \
+            not isinstance(query.recommend, models.RecommendInput):
+        raise ValueError("recommend_params: query must be RecommendQuery(recommend="
+                         "RecommendInput(...))")
+    if not _is_int(limit):
+        raise ValueError("a recommend query needs an int limit")
+    rec = query.recommend
+    sides = []
+    for name, side in (("positive", rec.positive), ("negative", rec.negative)):
+        if side is None:
+            side = []
+        if isinstance(side, (str, bytes, dict)) or not hasattr(side, "__len__"):
+            raise ValueError(f"RecommendInput.{name} must be a list of point ids and / or vectors")
+        if len(side) > RECO_MAX_SIDE:
+            raise ValueError(f"a recommend query takes at most {RECO_MAX_SIDE} {name} examples "
+                             f"(RAG_RECO_MAX_SIDE), got {len(side)}")
+        sides.append(list(side))
+    strategy = reco_strategy(rec.strategy)              # ValueError for an unknown one
+    pos, neg = sides
+    if not pos and not neg:
+        raise ValueError("a recommend query needs at least one positive or negative example")
+    if strategy == reco_strategy(None) and not pos:
+        raise ValueError("RecommendStrategy.AVERAGE_VECTOR needs a positive example; "
+                         "best_score and sum_scores take negatives alone")
+    return pos, neg, strategy
+
+
+def recommend_request(col: Collection, req) -> tuple:
+    """(positive, negative, strategy, compiled filter, limit) of a RECOMMEND request, or
+    ValueError: prefetched candidates cannot be recommended from, and neither a named vector
+    (`using`) nor another collection's points (`lookup_from`) exist here."""
+    if getattr(req, "prefetch", None) is not None:
+        raise ValueError("a RecommendQuery over prefetched candidates (prefetch=...) is not "
+                         "built: it scores every point a query_filter matches")
+    for name in ("using", "lookup_from"):
+        if getattr(req, name, None) is not None:
+            raise ValueError(f"a RecommendQuery with {name}=... is not built: a collection has "
+                             "one unnamed vector and examples are its own points")
+    pos, neg, strategy = recommend_params(req.query, req.limit)
+    return pos, neg, strategy, col.compile_filter(req.filter), int(req.limit)
+
+
 def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=False) -> list:
     """The requests of one route (QueryRequests, in order) answered by one call on the
     collection: per request its resolved points (the ORDER route: one order_rows per request
@@ -220,6 +274,9 @@ def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=Fals
              for r in reqs], with_vectors)
     if route == ORDER:
         return col.search_points_order([order_params(col, r) for r in reqs], with_vectors)
+    if route == RECOMMEND:
+        return col.search_points_recommend([recommend_request(col, r) for r in reqs],
+                                           with_vectors)
     qs, filters, limits, div, cand = [], [], [], [], []
     for r in reqs:
         q, mmr = nearest_of(r.query)
@@ -431,9 +488,9 @@ class QdrantClient:
                      query_filter: models.Filter | None = None, with_payload=True,
                      with_vectors=False, prefetch=None, **kwargs) -> models.QueryResponse:
         """One request on its route (route_of, answer). A plain request with a limit the scan
-        serves rides the coalescer; fusion, formula, MMR and order_by requests never do: their
-        prefetches, their candidate search, their ranking of a key column are passes of their
-        own."""
+        serves rides the coalescer; fusion, formula, MMR, order_by and recommend requests never
+        do: their prefetches, their candidate search, their ranking of a key column, their
+        pass over the examples are passes of their own."""
         col = self._col(collection_name)
         route = route_of(query, prefetch)
         if route == PLAIN and self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
@@ -442,7 +499,8 @@ class QdrantClient:
             pts = col.coalescer.search(q, int(limit), flt)
         else:
             req = models.QueryRequest(query=query, filter=query_filter, limit=limit,
-                                      prefetch=prefetch)
+                                      prefetch=prefetch, using=kwargs.get("using"),
+                                      lookup_from=kwargs.get("lookup_from"))
             pts = answer(col, route, [req], with_vectors, one=True)[0]
         return models.QueryResponse(points=_payloads(pts, with_payload))
 
@@ -450,20 +508,21 @@ class QdrantClient:
                            **kwargs) -> list[models.QueryResponse]:
         """One GPU scan for the whole batch (per-query filters ride along in the kernel). The
         requests are partitioned by route once, each non-empty route is answered by one call
-        (answer), fusion and formula first, then the order_by requests (a route of their own,
-        answered one request at a time), and the results are scattered back in request order.
+        (answer), fusion and formula first, then the order_by and the recommend requests
+        (routes of their own, answered one request at a time, in order), and the results are
+        scattered back in request order.
         With MMR requests in the batch the plain requests ride with them, at diversity 0 with their own
         limit as candidate count: one search at the batch's largest candidate count and one
         MMR launch — unless a plain limit exceeds RAG_MMR_MAX_CANDIDATES, in which case the
         plain requests are searched on their own."""
         col = self._col(collection_name)
-        routes: dict = {FUSION: [], FORMULA: [], ORDER: [], PLAIN: [], MMR: []}
+        routes: dict = {FUSION: [], FORMULA: [], ORDER: [], RECOMMEND: [], PLAIN: [], MMR: []}
         for i, r in enumerate(requests):
             routes[route_of(r.query, getattr(r, "prefetch", None))].append(i)
         if routes[MMR] and all(int(requests[i].limit) <= MMR_MAX_CANDIDATES
                                for i in routes[PLAIN]):
             routes = {FUSION: routes[FUSION], FORMULA: routes[FORMULA], ORDER: routes[ORDER],
-                      MMR: sorted(routes[MMR] + routes[PLAIN])}
+                      RECOMMEND: routes[RECOMMEND], MMR: sorted(routes[MMR] + routes[PLAIN])}
         out: list = [None] * len(requests)
         for route, members in routes.items():
             if members:
@@ -492,6 +551,9 @@ class QdrantClient:
                 kwargs.get("prefetch") is not None:
             raise ValueError("a grouped query over prefetched candidates (prefetch, FusionQuery, "
                              "RrfQuery) is not built")
+        if isinstance(query, models.RecommendQuery):
+            raise ValueError("a grouped query cannot be a RecommendQuery: grouped recommend is "
+                             "not built")
         query, mmr = nearest_of(query)
         if mmr is not None:
             raise ValueError("a grouped query cannot be an MMR query (NearestQuery.mmr)")
@@ -501,6 +563,16 @@ class QdrantClient:
         for g in found:
             _payloads(g.hits, with_payload)
         return models.GroupsResult(groups=found)
+
+    def recommend(self, collection_name: str, positive=None, negative=None, query_filter=None,
+                  limit: int = 10, strategy=None, with_payload=True, with_vectors=False,
+                  **kwargs):
+        """Legacy qdrant_client.recommend: list[ScoredPoint] of
+        query_points(query=RecommendQuery(RecommendInput(positive, negative, strategy)))."""
+        query = models.RecommendQuery(recommend=models.RecommendInput(
+            positive=positive, negative=negative, strategy=strategy))
+        return self.query_points(collection_name, query, limit, query_filter, with_payload,
+                                 with_vectors, **kwargs).points
 
     def search_groups(self, collection_name: str, query_vector, group_by: str,
                       query_filter=None, limit: int = 10, group_size: int = 1,

@@ -234,6 +234,29 @@ class NearestQuery:
     mmr: Optional[Mmr] = None
 
 
+class RecommendStrategy(str, enum.Enum):
+    AVERAGE_VECTOR = "average_vector"
+    BEST_SCORE = "best_score"
+    SUM_SCORES = "sum_scores"
+
+
+@dataclass
+class RecommendInput:
+    """The examples of a recommend query: `positive` and `negative` are lists of point ids
+    and / or vectors (at most 16 each); `strategy` None takes RecommendStrategy.AVERAGE_VECTOR."""
+    positive: Optional[list] = None
+    negative: Optional[list] = None
+    strategy: Optional[RecommendStrategy] = None
+
+
+@dataclass
+class RecommendQuery:
+    """query_points(query=RecommendQuery(recommend=RecommendInput(...))): the points most like
+    the positive examples and least like the negative ones; points given as examples by id are
+    never among the hits."""
+    recommend: RecommendInput
+
+
 class Fusion(str, enum.Enum):
     RRF = "rrf"
     DBSF = "dbsf"
@@ -433,9 +456,12 @@ class FacetResponse:
 @dataclass
 class QueryRequest:
     """Batched query entry for query_batch_points (one per request of a micro-batch); `query`
-    is a vector or a NearestQuery, or with `prefetch` a FusionQuery / RrfQuery / FormulaQuery."""
+    is a vector or a NearestQuery, or with `prefetch` a FusionQuery / RrfQuery / FormulaQuery,
+    or a RecommendQuery. `using` and `lookup_from` exist to be refused where they are set."""
     query: Any
     filter: Optional[Filter] = None
     limit: int = 10
     with_payload: Any = True
     prefetch: Any = None
+    using: Any = None
+    lookup_from: Any = None

@@ -14,6 +14,8 @@ ingest.py's hot-path functions, same names, arguments, return shapes and TESTING
 plus the batched forms a rewritten main2.batch_processor uses:
   retrieve_batch  -> one GPU scan for all requests of a micro-batch (per-query filters)
   rerank_batch    -> one cross-encoder forward for all (query, chunk) pairs of a micro-batch
+and, not in the reference:
+  similar_chunks  -> the chunks most like some chunks and least like others (recommend query)
 
 Models come from local directories (env RAGMI_BGE_DIR, RAGMI_CE_DIR: config.json +
 model.safetensors + vocab.txt) — the reference's hub names cannot be fetched here. Env
@@ -236,6 +238,25 @@ def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEV
                                          limit=limit,
                                          query_filter=_filter(ticker, document_type,
                                                               ingested_since, ingested_until))
+    except Exception:
+        return type("obj", (object,), {"points": []})
+
+
+def similar_chunks(point_ids, not_like=(), ticker=None, limit=RETRIEVE_LIMIT):
+    """Not in the reference: the `limit` chunks most like the chunks `point_ids` and least like
+    the chunks `not_like` (point ids both; "like these two risk-factor paragraphs, not like this
+    boilerplate one"), by Qdrant's best_score recommendation, under retrieve_from_qdrant's ticker
+    filter when `ticker` is given. The example chunks are never among the hits. Every failure
+    reads as no documents, as in retrieve_from_qdrant."""
+    if _testing():
+        return type("obj", (object,), {"points": []})
+    query = models.RecommendQuery(recommend=models.RecommendInput(
+        positive=list(point_ids), negative=list(not_like),
+        strategy=models.RecommendStrategy.BEST_SCORE))
+    try:
+        return get_qdrant().query_points(collection_name=COLLECTION_NAME, query=query,
+                                         limit=limit,
+                                         query_filter=_filter(ticker) if ticker else None)
     except Exception:
         return type("obj", (object,), {"points": []})
 

@@ -544,6 +544,67 @@ int rag_shardset_search_view(rag_shardset_t* set, const float* queries_dev, int 
                              const uint32_t* filters_dev, int flags, float* out_scores_dev,
                              int64_t* out_ids_dev, uint8_t* out_empty_dev, void* stream);
 
+/* Recommend queries ("more like these points, less like those": Qdrant's RecommendQuery /
+ * client.recommend). One request has P positive and N negative examples,
+ * 0 <= P, N <= RAG_RECO_MAX_SIDE, each a vector of the index's dim (pos_dev [n_pos][dim],
+ * neg_dev [n_neg][dim], fp32, device; the caller resolves point ids to stored rows with
+ * rag_index_gather_rows). Every example goes through the canonical query normalisation into
+ * x_i (fp32), exactly as a search query does; e_i(r) is the canonical exact score of stored row
+ * r against x_i — the arithmetic of every exact score of this library, never another dot
+ * product. A zero-vector example normalises to the zero query: e_i(r) = 0 for every row, and it
+ * adds the zero vector to AVERAGE's mean.
+ *   RAG_RECO_BEST (P + N >= 1): mp = max over the positives of e_i(r) in fp32 (-inf when P = 0),
+ *     mn the same over the negatives (-inf when N = 0); sig(x) = 0.5 (x / (1 + |x|) + 1) in fp64
+ *     on the fp32 value, rounded once to fp32; score = sig(mp) if mp > mn, else -sig(mn).
+ *   RAG_RECO_SUM (P + N >= 1): score = sum over positives of e_i - sum over negatives of e_j,
+ *     accumulated in fp64 in example order, positives first, rounded once to fp32.
+ *   RAG_RECO_AVERAGE (P >= 1): v = a_pos when N = 0, else a_pos + (a_pos - a_neg), a_* the mean
+ *     of the side's x_i; per component accumulated in fp64 in example order, divided, combined
+ *     and rounded once to fp32. v is then the query of the ordinary exact search (every route
+ *     of rag_index_search, scan copies included): the scores are rag_index_search's for v.
+ * Result: the k best rows passing the filter by (score desc, row asc), -inf / -1 past the
+ * matching rows — rag_index_search's order and padding; ids are id_offset + row. The example
+ * points themselves are NOT excluded here: the host layer asks for k + m and drops them.
+ * The BEST form is Qdrant's scaled-fast-sigmoid scoring restated from memory of its source:
+ * parity with a Qdrant server's own arithmetic is unpinned (as for MMR and formulas). Results
+ * are exact with respect to the contract above.
+ *
+ * rag_index_recommend: one request, asynchronous on `stream`, under the handle's lock.
+ * progs_dev NULL (words = n_programs = 0): the filter is over the stored tags; else over the
+ * blob's filter view (rag_index_search_view's rules). filter_dev: one (mask, value) pair [2] or
+ * NULL. BEST and SUM with k <= RAG_MAX_K_LARGE take the hot pass — one MFMA stream of the fp16
+ * rows whatever P + N: certified bounds [L, U] of every row's score, a sampled threshold,
+ * candidates (at most 16384 kept) scored exactly; a request with more than 16384 rows within
+ * its bounds of the k-th best after the last round is left unanswered (-inf / -1, counted in
+ * rag_index_unanswered): re-run it with RAG_SEARCH_FULL. flags RAG_SEARCH_FULL, or
+ * k > RAG_MAX_K_LARGE: the full pass (every row scored exactly, sorted), which always answers.
+ * Both give the same lists bit for bit.
+ * rag_index_reco_bounds: diagnostic; out_lo_dev[i] <= exact score of rows_dev[i] <= out_hi_dev[i]
+ * as the hot pass computes them (BEST or SUM), (-inf, +inf) for a row outside [0, count).
+ * rag_index_reco_vector: diagnostic; AVERAGE's v (fp32 [dim], device).
+ * rag_index_reco_stats: out[0] hot passes and out[1] full passes since creation, out[2] the
+ * candidates the last hot pass counted in its last round, out[3] the rounds it ran;
+ * synchronises the device.
+ * Argument errors are refused before any HIP call: a NULL pointer where one is needed, a side
+ * above RAG_RECO_MAX_SIDE, P = 0 for AVERAGE, P + N = 0, an unknown strategy, k < 1, unknown
+ * flags, the program rules of rag_index_search_view. */
+#define RAG_RECO_AVERAGE 0
+#define RAG_RECO_BEST 1
+#define RAG_RECO_SUM 2
+#define RAG_RECO_MAX_SIDE 16
+int rag_index_recommend(rag_index_t* index, const float* pos_dev, int n_pos,
+                        const float* neg_dev, int n_neg, int strategy, int k,
+                        const uint32_t* progs_dev, int64_t words, int n_programs,
+                        const uint32_t* filter_dev /* [2] or NULL */, int64_t id_offset,
+                        int flags, float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+int rag_index_reco_bounds(rag_index_t* index, const float* pos_dev, int n_pos,
+                          const float* neg_dev, int n_neg, int strategy,
+                          const int64_t* rows_dev, int64_t n,
+                          float* out_lo_dev, float* out_hi_dev, void* stream);
+int rag_index_reco_vector(rag_index_t* index, const float* pos_dev, int n_pos,
+                          const float* neg_dev, int n_neg, float* out_v_dev, void* stream);
+int rag_index_reco_stats(rag_index_t* index, int64_t out[4]);
+
 /* Key columns (range and datetime filters: the numeric payload fields of a collection, in HBM).
  * An index holds 0 to RAG_KEYS_MAX_COLS columns, each int64 [capacity] (8 B per row, the tag
  * array's extent: a multiple of 16 rows). A column holds KEYS: for a double x, -0.0 taken as
