@@ -257,7 +257,9 @@ __device__ __forceinline__ double canon_sumsq(const float* __restrict__ x, int l
 // max of values that are never NaN (MFMA scores, exp2 outputs, -inf masks): IEEE-754
 // `maximum` lowers to v_maximum(3)_f32 on gfx950, where fmaxf's maxnum first canonicalises
 // every input that is not provably canonical (one v_max_f32 x, x per MFMA result: 11 VALU
-// for an 8-value max instead of 5). Equal to fmaxf for every non-NaN input.
+// for an 8-value max instead of 5). Equal to fmaxf for every non-NaN input. MFMA scores are
+// never NaN because no stored row and no prepared query holds a NaN or an inf: canon_norm below
+// stores a non-finite vector as the zero vector, and the imports refuse non-finite rows.
 __device__ __forceinline__ float fmax_nc(float a, float b) {
   return __builtin_elementwise_maximum(a, b);
 }
@@ -279,7 +281,22 @@ __device__ __forceinline__ _Float16 f32_to_f16(float y) {
   return (_Float16)y;
 }
 
-// y = fp32(x / sqrt(sumsq)) with fp64 division; zero vector stays zero.
+// Largest L2 norm of a stored row: fp16(unit vector) has ||c|| <= 1 + 2^-11 + sqrt(D) 2^-25.
+// Every certificate assumes it (prep_kernels.hip: eps, the int8 and 6-bit u bounds); the imports
+// refuse a row beyond it (index_store.hip).
+constexpr double kRowNorm = 1.001;
+
+// The canonical norm of a vector from its canonical sumsq. A vector whose canonical sumsq is not
+// finite, or is zero, normalises to the zero vector: 0.0 here makes canon_scale return +0.0 for
+// every element. fp32 squares of D <= 1024 elements cannot overflow fp64, so sumsq is non-finite
+// exactly when some component is non-finite. One compare per vector (wave-uniform), none per
+// element; oracle/scan_ref.c:orc_canon_norm restates it.
+__host__ __device__ __forceinline__ double canon_norm(double sumsq) {
+  const double norm = sqrt(sumsq);
+  return norm < __builtin_inf() ? norm : 0.0;
+}
+
+// y = fp32(x / norm) with fp64 division, norm from canon_norm; norm 0 gives the zero vector.
 __device__ __forceinline__ float canon_scale(float x, double norm) {
   return norm > 0.0 ? (float)((double)x / norm) : 0.0f;
 }

@@ -111,9 +111,55 @@ int alloc_corpus(rag_index* h, int64_t cap_rows, half8** corpus, uint32_t** tags
   return RAG_OK;
 }
 
+// One element of an imported row as fp64, exact; false for a non-finite one. fp16 by its
+// exponent bits (no float conversion of an inf or NaN): (h & 0x7fff) << 13 read as fp32 is the
+// value scaled by 2^-112, normal or subnormal.
+inline bool import_value(uint16_t h, double& v) {
+  if ((h & 0x7c00u) == 0x7c00u) return false;
+  const uint32_t u = (uint32_t)(h & 0x7fffu) << 13;
+  float f;
+  std::memcpy(&f, &u, 4);
+  v = (double)(f * 0x1p112f);   // the sign does not enter the norm
+  return true;
+}
+inline bool import_value(float x, double& v) {
+  uint32_t u;
+  std::memcpy(&u, &x, 4);
+  if ((u & 0x7f800000u) == 0x7f800000u) return false;
+  v = (double)x;
+  return true;
+}
+
+// The rows an import may write: every element finite and the fp64 L2 norm at most kRowNorm, what
+// every certificate assumes of a stored row (device_common.hpp). The first row that is neither is
+// named in the error; nothing has been copied by then.
+template <typename T>
+int check_import_rows(const T* rows, int64_t row0, int64_t n, int dim) {
+  for (int64_t r = 0; r < n; ++r) {
+    const T* x = rows + r * dim;
+    double s = 0.0;
+    for (int k = 0; k < dim; ++k) {
+      double v;
+      if (!import_value(x[k], v))
+        return ragmi::fail(RAG_EINVAL, "import: row " + std::to_string(row0 + r) +
+                                           " holds a non-finite element (index " +
+                                           std::to_string(k) + ")");
+      s += v * v;
+    }
+    const double norm = std::sqrt(s);
+    if (norm > ragmi::kRowNorm)
+      return ragmi::fail(RAG_EINVAL, "import: row " + std::to_string(row0 + r) + " has norm " +
+                                         std::to_string(norm) + " > " +
+                                         std::to_string(ragmi::kRowNorm) +
+                                         ": not a stored (normalised) row");
+  }
+  return RAG_OK;
+}
+
 // rag_index_import_rows (T = uint16_t: fp16 rows into an fp16-storage index) and
 // rag_index_import_rows32 (T = float: fp32 rows into an fp32-storage index, the scan's fp16
-// copy derived on the device): staged through device memory, synchronous
+// copy derived on the device): checked on the host (check_import_rows), then staged through
+// device memory, synchronous
 template <typename T>
 int import_rows(rag_index* h, int64_t row0, int64_t n, const T* rows, const uint32_t* tags,
                 int64_t new_count) {
@@ -126,6 +172,7 @@ int import_rows(rag_index* h, int64_t row0, int64_t n, const T* rows, const uint
     return ragmi::fail(RAG_EINVAL, "fp32-storage index: load its fp32 rows (rag_index_import_rows32)");
   if (new_count < 0 || new_count > h->cap_rows)
     return ragmi::fail(RAG_ERANGE, "new_count exceeds capacity");
+  if (const int rc = check_import_rows(rows, row0, n, h->dim)) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   RAG_HIP(hipSetDevice(h->device));
   if (n > 0) {

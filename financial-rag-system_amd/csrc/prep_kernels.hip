@@ -49,7 +49,7 @@ __global__ __launch_bounds__(64) void upsert_kernel(const float* __restrict__ ve
   const int64_t row = rows[i];
   if (row < 0 || row >= cap_rows) return;  // host validates; never write out of bounds
   const float* x = vecs + i * D;
-  const double norm = sqrt(canon_sumsq<D>(x, lane));
+  const double norm = canon_norm(canon_sumsq<D>(x, lane));
   for (int c = lane; c < D / 8; c += 64) {
     half8 h;
     float y[8];
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64) void upsert_kernel(const float* __restrict__ ve
 // inflated by 2^-10 relative + 2^-22 absolute so the fp32 comparisons that use it in select
 // stay conservative.
 // ----------------------------------------------------------------------------------------
-constexpr double kRowNorm = 1.001;   // fp16(unit vector): ||c|| <= 1 + 2^-11 + sqrt(D) 2^-25
+// kRowNorm: device_common.hpp (the imports check it on the host)
 
 // one query slot b by one wave. The B-fragment goes to qf (global or an LDS image of the same
 // layout); qn / filt / eps are written only when `publish` (the fused qprep_sample_kernel:
@@ -118,7 +118,7 @@ __device__ __forceinline__ void qprep_slot(const float* __restrict__ q, int B, i
     }
   }
   double norm = 0.0;
-  if (live) norm = sqrt(canon_sumsq<D>(q + (int64_t)b * D, lane));
+  if (live) norm = canon_norm(canon_sumsq<D>(q + (int64_t)b * D, lane));
   const int qt = b >> 4, c16 = b & 15;
   double dq2 = 0.0, hh2 = 0.0;   // ||h - qn||^2, ||h||^2 (lane partials)
   for (int c = lane; c < D / 8; c += 64) {
@@ -268,7 +268,7 @@ __device__ __forceinline__ void qprep8_slot(const float* __restrict__ q, int B, 
   static_assert(D / 8 <= 64, "one piece per lane");
   const bool live = b < B;
   double norm = 0.0;
-  if (live) norm = sqrt(canon_sumsq<D>(q + (int64_t)b * D, lane));
+  if (live) norm = canon_norm(canon_sumsq<D>(q + (int64_t)b * D, lane));
   const bool has = lane < D / 8;
   float y[8];
   float m = 0.f;

@@ -67,11 +67,30 @@ def parse_selector(points_selector):
     return "ids", [_norm_id(pid) for pid in sel]
 
 
-def stack_queries(qs: list, dim: int, one: bool = False, host: bool = False):
+def require_finite(vecs, what: str, names=None) -> None:
+    """ValueError for the first vector of the batch `vecs` [n, dim] (array or tensor) that holds
+    a non-finite component, naming it: `what` and names[i] (the point id) or its position i.
+    Real Qdrant cannot receive such a vector at all (JSON has no spelling for inf or NaN); the
+    index below does not check (its inputs may be device tensors) and stores or searches it as
+    the zero vector (DESIGN.md "Values at the edges"). A tensor on a device is read back for
+    this, so the check synchronises."""
+    if isinstance(vecs, torch.Tensor):
+        bad = (~torch.isfinite(vecs).all(dim=1)).cpu().numpy()
+    else:
+        bad = ~np.isfinite(np.asarray(vecs)).all(axis=1)
+    if bad.any():
+        i = int(np.argmax(bad))
+        which = f"{names[i]!r}" if names is not None else f"at position {i}"
+        raise ValueError(f"{what} {which} holds a non-finite component (inf or NaN)")
+
+
+def stack_queries(qs: list, dim: int, one: bool = False, host: bool = False,
+                  what: str = "query"):
     """The query stacker: query vectors given as lists, arrays or tensors, as one [n, dim]
     batch: a tensor when any of them is one, else a float32 array. one=True: `qs` is the one
     vector of a single request. host=True (the coalescer route, whose leader stacks its riders'
-    queries on the host): tensors are brought to host numpy first."""
+    queries on the host): tensors are brought to host numpy first. A vector with a non-finite
+    component is refused (require_finite), named by `what` and its position in `qs`."""
     if host:
         qs = [x.detach().float().cpu().numpy() if isinstance(x, torch.Tensor) else x for x in qs]
     if len(qs) == 1:
@@ -85,6 +104,7 @@ def stack_queries(qs: list, dim: int, one: bool = False, host: bool = False):
         Q = np.stack([np.asarray(x, np.float32).reshape(-1) for x in qs])
     if Q.shape[1] != dim:
         raise ValueError(f"{'query' if one else 'every query'} must be one {dim}-dim vector")
+    require_finite(Q, what)
     return Q
 
 
@@ -175,6 +195,8 @@ class Collection:
             vec = host_or_tensor(vectors)
             if vec.ndim != 2 or vec.shape[1] != self.dim:
                 raise ValueError(f"vectors must be [n, {self.dim}]")
+            require_finite(vec, "upsert: the vector of point",
+                           list(ids) if len(ids) == vec.shape[0] else None)
             # last write wins for duplicate ids inside one batch (Qdrant semantics)
             last: dict[Any, int] = {}
             for i, pid in enumerate(ids):
@@ -424,6 +446,12 @@ class Collection:
                 by_id = [{j: self._example_row(x) for j, x in enumerate(side)
                           if not _is_vector(x)} for side in (pos, neg)]
                 own = set(by_id[0].values()) | set(by_id[1].values())
+                # the caller's vectors, before anything else: a refusal does not depend on limits
+                for side, what in ((pos, "recommend: positive example"),
+                                   (neg, "recommend: negative example")):
+                    for j, x in enumerate(side):
+                        if _is_vector(x):
+                            require_finite(host_or_tensor(x).reshape(1, -1), what, [j])
                 count = self.index.count
                 if limit < 1 or count == 0 or c is None:
                     out.append([])
@@ -437,7 +465,8 @@ class Collection:
                             got[0].view(torch.float16).float()
                         for j, v in zip(rows, stored):
                             vecs[j] = v
-                    sides.append(stack_queries(vecs, self.dim) if vecs else None)
+                    sides.append(stack_queries(vecs, self.dim, what="recommend: example")
+                                 if vecs else None)
                 view = {}
                 if isinstance(c, FilterProgram):
                     view = {"programs": pack_view([c]), "filters": (1, 1)}
@@ -463,6 +492,16 @@ class Collection:
         with self.lock:
             return self._points(self.search_recommend(requests), with_vectors)
 
+    @staticmethod
+    def _check_prefetch_vectors(requests: list, route: str) -> None:
+        """Every prefetch vector of a fusion or formula request list, searched or not, so that
+        a refusal does not depend on the limits (require_finite): the error names the request
+        and the prefetch."""
+        for b, (_, pres, _) in enumerate(requests):
+            for l, (vec, _, _) in enumerate(pres):
+                require_finite(host_or_tensor(vec).reshape(1, -1),
+                               f"{route}: request {b}, the query of prefetch", [l])
+
     def search_fusion(self, requests: list):
         """Fusion queries. `requests`: per request (rrf_k, [(vector, Filter or
         None, limit), ...], limit), as fusion_params returns them. Every prefetch of every
@@ -476,6 +515,7 @@ class Collection:
             count = self.index.count
             # every filter is compiled, so that a refusal does not depend on the limits
             compiled = [[self.compile_filter(f) for _, f, _ in pres] for _, pres, _ in requests]
+            self._check_prefetch_vectors(requests, "fusion")
             qs, filters, where = [], [], []          # the searched prefetches, flattened
             for b, (_, pres, limit) in enumerate(requests):
                 if limit < 1 or count == 0:
@@ -543,6 +583,7 @@ class Collection:
             formulas = [compile_formula(q, None, len(pres), self.tags, self.ranges)
                         for q, pres, _ in requests]
             compiled = [[self.compile_filter(f) for _, f, _ in pres] for _, pres, _ in requests]
+            self._check_prefetch_vectors(requests, "formula")
             qs, filters, where = [], [], []          # the searched prefetches, flattened
             for b, (_, pres, limit) in enumerate(requests):
                 if limit < 1 or count == 0:

@@ -92,7 +92,7 @@ def read_meta(path: str) -> dict:
     return meta
 
 
-# Row-norm bounds the exact top-k certificate assumes (prep_kernels.hip kRowNorm, index_search.hip
+# Row-norm bounds the exact top-k certificate assumes (device_common.hpp kRowNorm, index_search.hip
 # store_eps): a stored fp16 row is the RNE rounding of a unit vector, ||c|| - 1 within
 # 2^-11 + sqrt(D) 2^-25 (<= 1e-3 for D <= 1024); a stored fp32 row is fp32(x / ||x||),
 # ||y|| - 1 within 2^-20. Zero rows (never-filled slots, zero vectors) are allowed.

@@ -35,6 +35,16 @@
  *     (score desc, row asc), optionally restricted per query to rows whose tag satisfies
  *     (tag & tag_mask) == tag_value (the payload `must` filter, main.py:218-236).
  *     Missing results (fewer than k matching rows) are reported as id -1, score -inf.
+ *   - edges: a vector whose canonical sumsq is not finite, or is zero, normalises to the zero
+ *     vector: fp32 +0.0 in every element, so fp16 0x0000. fp32 squares of dim <= 1024 elements
+ *     cannot overflow fp64, so sumsq is non-finite exactly when some component is non-finite
+ *     (inf or NaN). Finite inputs keep every bit. This holds for upserted vectors, queries and
+ *     recommend examples alike. A zero query scores +0.0 against every row; the ranking is
+ *     then row ascending. The imports (rag_index_import_rows[32]) write caller bits and so
+ *     refuse, with RAG_EINVAL naming the first offending row and the index unchanged, a row
+ *     with a non-finite element or with an fp64 L2 norm above 1.001, the row norm every
+ *     exactness certificate assumes. Candidate scores handed in from outside (rag_index_mmr,
+ *     rag_group_select, rag_fuse_rrf, rag_formula_rescore) are not checked.
  */
 #ifndef RAGMI_H
 #define RAGMI_H
@@ -171,7 +181,10 @@ int rag_index_search_packed(rag_index_t* index, const float* queries_dev, int B,
 int rag_index_export_rows(rag_index_t* index, int64_t row0, int64_t n, uint16_t* out_host);
 /* Load already-stored rows back (persistence): row-major fp16 bits [n][dim] (host) are
  * written to rows [row0, row0+n) unchanged (no renormalisation), tags (host, may be NULL)
- * likewise; `new_count` = valid rows afterwards. Synchronous. */
+ * likewise; `new_count` = valid rows afterwards. Synchronous. Checked on the host before
+ * anything is copied: a row with a non-finite element (fp16: all exponent bits set) or an fp64
+ * L2 norm above 1.001 is refused with RAG_EINVAL, the message naming the first such row, and
+ * the index stays unchanged ("edges" above). rag_index_import_rows32 checks alike. */
 int rag_index_import_rows(rag_index_t* index, int64_t row0, int64_t n, const uint16_t* rows_host,
                           const uint32_t* tags_host, int64_t new_count);
 /* fp32 storage: copy the stored fp32 rows [row0, row0+n) out ([n][dim] float, host), and

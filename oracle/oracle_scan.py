@@ -90,7 +90,9 @@ def _rows_f32(corpus: np.ndarray, r0: int, n: int) -> np.ndarray:
 
 
 def normalize(x: np.ndarray) -> np.ndarray:
-    """Canonical fp32 normalisation of each row of x [n, D]."""
+    """Canonical fp32 normalisation of each row of x [n, D]. A vector whose canonical sumsq is
+    not finite (some component is inf or NaN), or is zero, normalises to the zero vector: fp32
+    +0.0 in every element (scan_ref.c "edges")."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = np.empty_like(x)
     for i in range(x.shape[0]):
@@ -263,7 +265,9 @@ def search_f64_reference(corpus16: np.ndarray, queries: np.ndarray, k: int):
     """Independent numpy formulation used to pin the C oracle in tests: float64 matmul on
     the fp16 corpus against canonically normalised queries, rounded to fp32, full lexsort.
     (Summation order differs from the canonical one; equal to it whenever no fp32 rounding
-    boundary is straddled, which the tests check on fixtures.)"""
+    boundary is straddled, which the tests check on fixtures.) A query whose canonical sumsq is
+    not finite, or is zero, is the zero vector (normalize): it scores +0.0 against every row
+    and ranks them row ascending."""
     qn = normalize(queries).astype(np.float64)
     c = corpus16.view(np.float16).astype(np.float64)
     s = (qn @ c.T).astype(np.float32)

@@ -21,7 +21,12 @@
  *   sumsq   : 64 lane partials, lane l sums chunks c = l, l+64, ... (8 elems each) with
  *             fp64 fma in order; xor-butterfly d = 32..1 (v[i] += v[i^d]); take v[0].
  *   norm    : sqrt(sumsq) (fp64, correctly rounded)
- *   y_k     : fp32(fp64(x_k) / norm), 0 if norm == 0
+ *   y_k     : fp32(fp64(x_k) / norm)
+ *   edges   : a vector whose canonical sumsq is not finite, or is zero, normalises to the zero
+ *             vector: fp32 +0.0 in every element, so fp16 0x0000. fp32 squares of D <= 1024
+ *             elements cannot overflow fp64, so sumsq is non-finite exactly when some component
+ *             is non-finite (inf or NaN). Finite inputs keep every bit. A zero query scores
+ *             +0.0 against every row; the ranking is then row ascending.
  *   stored  : fp16_rne(y_k)            (fp16 storage; fp32 storage keeps y_k itself:
  *                                        Qdrant's default Float32 vectors, database.py:124-130)
  *   score   : fp32( canonical fp64 sum of fp64(c_k) * fp64(qn_k) ), c = the stored row (fp16
@@ -107,9 +112,16 @@ ORC_API double orc_canon_sumsq(const float* x, int D) {
   return v[0];
 }
 
+/* The canonical norm from the canonical sumsq: 0 (hence the zero vector) when sumsq is not
+ * finite, as device_common.hpp:canon_norm. */
+static double orc_canon_norm(double sumsq) {
+  const double norm = sqrt(sumsq);
+  return norm < INFINITY ? norm : 0.0;
+}
+
 /* y = canonical normalised fp32 vector; h (optional) = its fp16 bits. */
 ORC_API void orc_normalize(const float* x, int D, float* y, uint16_t* h) {
-  const double norm = sqrt(orc_canon_sumsq(x, D));
+  const double norm = orc_canon_norm(orc_canon_sumsq(x, D));
   for (int k = 0; k < D; ++k) {
     const float v = norm > 0.0 ? (float)((double)x[k] / norm) : 0.0f;
     y[k] = v;

@@ -23,7 +23,8 @@ def example(corpus, x):
 
 
 def examples(corpus, side) -> np.ndarray:
-    """x_i fp32 [n, D]: the side's examples through the canonical normalisation."""
+    """x_i fp32 [n, D]: the side's examples through the canonical normalisation (an example with
+    a non-finite component, or the zero vector, is the zero vector: it scores +0.0 everywhere)."""
     d = corpus.shape[1]
     if side is None or len(side) == 0:
         return np.empty((0, d), np.float32)
