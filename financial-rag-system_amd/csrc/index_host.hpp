@@ -73,6 +73,9 @@ struct Workspace {
   // hot pass's counters (kRecoPar*)
   float* reco_q = nullptr;
   float* reco_par = nullptr;
+  // sparse searches (sparse_kernels.hip), allocated on first use: the pass's query table
+  // (kSpTabWords words)
+  uint32_t* sp_tab = nullptr;
   hipEvent_t ev_in = nullptr;   // scan-stream order: caller stream -> scan stream -> caller
   hipEvent_t ev_out = nullptr;
   hipStream_t owner = nullptr;  // stream of the last pass that used this slot
@@ -220,6 +223,11 @@ struct rag_index {
   // keys, the tag array's extent; entries at or past n_keys are nullptr
   int64_t* keys[RAG_KEYS_MAX_COLS] = {};
   int n_keys = 0;
+  // sparse column (rag_index_sparse_create; sparse_kernels.hip): sp_slots slots per row, terms
+  // uint16 [cap_rows][sp_slots] and values fp32 alike; nullptr / 0 in an index without one
+  uint16_t* sp_terms = nullptr;
+  float* sp_vals = nullptr;
+  int sp_slots = 0;
   // storage (rag_index_create_ex): RAG_STORE_FP16 keeps only the scan's fp16 tile16 rows;
   // RAG_STORE_FP32 also the normalised fp32 rows (row-major [cap][dim]), which the exact
   // rescoring reads — Qdrant's default Float32 datatype
@@ -294,6 +302,12 @@ inline int ensure_stage(rag_index* h, size_t bytes) {
 #pragma GCC visibility push(hidden)
 // index_search.hip: a new handle's workspaces (dim, groups, max_wgs, copies set), one hipMalloc per
 // buffer in the tables' order; their release; the shard set's id remap (remap_ids_kernel)
+// ... the sparse column of an index that has one (lock held): its rows moved with their dense
+// rows on `st` (rag_index_move_rows), regrown to `cap` rows with the old rows kept and the new
+// ones empty (rag_index_reserve, before cap_rows changes; synchronous)
+int sparse_move_rows(rag_index* h, const int64_t* src_rows, const int64_t* dst_rows, int64_t n,
+                     hipStream_t st);
+int sparse_reserve(rag_index* h, int64_t cap);
 hipError_t alloc_workspaces(rag_index* h);
 void free_workspaces(rag_index* h);
 int remap_shard_ids(int64_t* ids, int B, int k, int n, uint8_t* out_empty, hipStream_t st);

@@ -12,6 +12,7 @@
 #include "merge_kernels.hip"
 #include "largek_kernels.hip"
 #include "reco_kernels.hip"
+#include "sparse_kernels.hip"
 #include "reselect_kernels.hip"
 #include "formula_kernels.hip"
 
@@ -954,6 +955,191 @@ int recommend_locked(rag_index* h, const RecoArgs& r, int k, const uint32_t* fil
   });
 }
 
+// ---- sparse vectors (sparse_kernels.hip; the contract: ragmi.h "Sparse vectors") ----
+
+static_assert(kSpQueryNnz == RAG_SPARSE_MAX_QUERY_NNZ && kSpNone == RAG_SPARSE_TERM_NONE &&
+                  kSpUnion == RAG_SPARSE_MAX_UNION,
+              "sparse_kernels.hip's constants");
+
+// the padded queries of a sparse search (device pointers): terms uint16 [B][64], values fp32
+// [B][64], nonzeros int32 [B]
+struct SparseQueries {
+  const uint16_t* terms;
+  const float* vals;
+  const int32_t* nnz;
+};
+
+int ensure_sparse(Workspace& w) {
+  if (w.sp_tab) return RAG_OK;
+  if (hipMalloc(reinterpret_cast<void**>(&w.sp_tab), (size_t)kSpTabWords * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    w.sp_tab = nullptr;
+    return ragmi::fail(RAG_ENOMEM, "sparse workspace allocation failed");
+  }
+  return RAG_OK;
+}
+
+// the query table of queries [b0, b0 + Bq) of `sq` in w.sp_tab; filt: their pairs or nullptr
+void launch_sparse_prep(Workspace& w, const SparseQueries& sq, int b0, int Bq,
+                        const uint32_t* filt, hipStream_t st) {
+  sp_prep_kernel<<<dim3(1), dim3(256), 0, st>>>(
+      sq.terms + (int64_t)b0 * kSpQueryNnz, sq.vals + (int64_t)b0 * kSpQueryNnz, sq.nnz + b0, Bq,
+      filt, w.sp_tab);
+}
+
+// the scorer's grid: two workgroups per CU (their LDS tables fill the CU), fewer for few rows
+int sparse_grid(const rag_index* h, int64_t wave_items) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(2 * h->n_cu,
+                                                      (wave_items + kSpWaves - 1) / kSpWaves));
+}
+
+// The hot pass of <= 32 sparse queries, k <= RAG_MAX_K_LARGE: the large-k pass's selection
+// (launch_large_k_pass) over exact scores — a sample of 16-row tiles and lk_bound_kernel's
+// threshold (eps = 0), kLkRounds (collect, final) pairs; lk_final_kernel reads the scores the
+// collect wrote, so nothing is rescored. a.q is unused.
+int launch_sparse_hot(rag_index* h, Workspace& w, const SparseQueries& sq, int b0,
+                      const PassArgs& a, hipStream_t st) {
+  if (const int rc = ensure_lk(w)) return rc;
+  const int Bq = a.Bq, k = a.k, S = h->sp_slots, n = (int)h->count;
+  launch_sparse_prep(w, sq, b0, Bq, a.filt, st);
+  const float* zero_eps = reinterpret_cast<const float*>(w.sp_tab + kSpTabEps);
+  const int n_tiles = (n + kSpTileRows - 1) / kSpTileRows;
+  const int n_sample = n_tiles == 0 ? 0 : std::min({n_tiles, std::max(4 * k, n_tiles / 32),
+                                                    kLkSampleMax});
+  if (n_sample > 0)
+    sp_score_kernel<kSpSample><<<dim3(sparse_grid(h, n_sample)), dim3(kSpScoreBlock), 0, st>>>(
+        h->sp_terms, h->sp_vals, a.tags, S, n, Bq, w.sp_tab, n_tiles, n_sample, w.lk_smax,
+        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+  lk_bound_kernel<<<dim3(Bq), dim3(256), 0, st>>>(w.lk_smax, n_sample, k, zero_eps, w.lk_thr,
+                                                  w.lk_cnt, w.lk_again, w.lk_need);
+  const int cgrid = sparse_grid(h, ((int64_t)n + kSpRowGroup - 1) / kSpRowGroup);
+  for (int r = 0; r < kLkRounds; ++r) {
+    sp_score_kernel<kSpCollect><<<dim3(cgrid), dim3(kSpScoreBlock), 0, st>>>(
+        h->sp_terms, h->sp_vals, a.tags, S, n, Bq, w.sp_tab, 0, 0, nullptr, w.lk_thr, w.lk_cnt,
+        w.lk_cand, w.lk_es, w.lk_again, w.lk_need, r, nullptr, nullptr, nullptr);
+    // (the kernel's dim and row pointers serve the dense rescoring only: unused here)
+    lk_final_kernel<384><<<dim3(Bq), dim3(256), 0, st>>>(
+        nullptr, nullptr, k, w.lk_cnt, w.lk_cand, w.lk_es, zero_eps, w.lk_thr, w.lk_again,
+        w.lk_need, r, w.fb_tier, w.fb_cnt, a.id_offset, a.out_s, a.out_i, nullptr, nullptr);
+  }
+  sp_overflow_kernel<<<dim3(1), dim3(64), 0, st>>>(w.sp_tab, Bq, w.fb_tier, w.fb_cnt);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// The full pass of <= 32 sparse queries, any k: one query at a time every row scored, the full
+// pass's stable sort and emit (launch_full_pass). Always answers: one query's terms never exceed
+// the union cap.
+int launch_sparse_full(rag_index* h, Workspace& w, const SparseQueries& sq, int b0,
+                       const PassArgs& a, hipStream_t st) {
+  const int Bq = a.Bq, k = a.k, n = (int)h->count;
+  const dim3 egrid((unsigned)std::min<int64_t>(1024, ((int64_t)k + 255) / 256));
+  StreamScratch scratch(st);
+  if (n == 0) {
+    RAG_HIP(scratch.alloc(4));
+    RAG_HIP(hipMemsetAsync(scratch.p, 0, 4, st));
+    for (int j = 0; j < Bq; ++j)
+      full_emit_kernel<<<egrid, dim3(256), 0, st>>>(
+          nullptr, nullptr, reinterpret_cast<const int*>(scratch.p), k, a.id_offset,
+          a.out_s + (int64_t)j * k, a.out_i + (int64_t)j * k, nullptr);
+    RAG_HIP(hipGetLastError());
+    return RAG_OK;
+  }
+  size_t tmp_bytes = 0;
+  RAG_HIP(hipcub::DeviceRadixSort::SortPairsDescending(
+      nullptr, tmp_bytes, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
+      static_cast<const int*>(nullptr), static_cast<int*>(nullptr), n, 0, 32, st));
+  const size_t nb = (size_t)n * 4;
+  const size_t m_off = 4 * nb, t_off = m_off + 256;
+  RAG_HIP(scratch.alloc(t_off + tmp_bytes));
+  char* const buf = scratch.p;
+  uint32_t* k_in = reinterpret_cast<uint32_t*>(buf);
+  uint32_t* k_out = reinterpret_cast<uint32_t*>(buf + nb);
+  int* v_in = reinterpret_cast<int*>(buf + 2 * nb);
+  int* v_out = reinterpret_cast<int*>(buf + 3 * nb);
+  int* n_match = reinterpret_cast<int*>(buf + m_off);
+  RAG_HIP(hipMemsetAsync(n_match, 0, 4 * kQ, st));
+  const int grid = sparse_grid(h, ((int64_t)n + kSpRowGroup - 1) / kSpRowGroup);
+  for (int j = 0; j < Bq; ++j) {
+    launch_sparse_prep(w, sq, b0 + j, 1, a.filt ? a.filt + 2 * j : nullptr, st);
+    sp_score_kernel<kSpFull><<<dim3(grid), dim3(kSpScoreBlock), 0, st>>>(
+        h->sp_terms, h->sp_vals, a.tags, h->sp_slots, n, 1, w.sp_tab, 0, 0, nullptr, nullptr,
+        nullptr, nullptr, nullptr, nullptr, nullptr, 0, k_in, v_in, n_match + j);
+    if (hipGetLastError() != hipSuccess ||
+        sort_pairs_desc(buf + t_off, tmp_bytes, k_in, k_out, v_in, v_out, n, st) != hipSuccess)
+      return ragmi::fail(RAG_EHIP, "sparse full pass: score / sort launch failed");
+    full_emit_kernel<<<egrid, dim3(256), 0, st>>>(k_out, v_out, n_match + j, k, a.id_offset,
+                                                  a.out_s + (int64_t)j * k,
+                                                  a.out_i + (int64_t)j * k, nullptr);
+    RAG_HIP(hipGetLastError());
+  }
+  (void)hipMemsetAsync(w.fb_tier, 0, 4 * kQ, st);   // answered by construction
+  return RAG_OK;
+}
+
+// a sparse search under the handle's lock; tags: the stored tags or a filter view
+int sparse_search_locked(rag_index* h, const SparseQueries& sq, int B, int k,
+                         const uint32_t* filt, const uint32_t* tags, int64_t id_offset, bool full,
+                         float* out_s, int64_t* out_i, hipStream_t st) {
+  full = full || k > RAG_MAX_K_LARGE;
+  for (int b0 = 0; b0 < B; b0 += kQ) {
+    const int Bq = std::min(kQ, B - b0);
+    Workspace* wp = nullptr;
+    if (const int rc = take_workspace(h, st, Bq, &wp)) return rc;
+    if (const int rc = ensure_sparse(*wp)) return rc;
+    const PassArgs a{nullptr, Bq, k, filt ? filt + 2 * b0 : nullptr, tags, id_offset,
+                     out_s + (int64_t)b0 * k, out_i + (int64_t)b0 * k, nullptr};
+    const int rc = full ? launch_sparse_full(h, *wp, sq, b0, a, st)
+                        : launch_sparse_hot(h, *wp, sq, b0, a, st);
+    if (rc) return rc;
+  }
+  return RAG_OK;
+}
+
+// rag_index_sparse_write / _gather: the shared argument checks, then `launch(grid, stream)` under
+// the handle's lock
+template <typename F>
+int sparse_rows_call(rag_index* h, const int64_t* rows, const void* t, const void* v, int64_t n,
+                     void* stream, F&& launch) {
+  ragmi::clear_error();
+  if (n < 0) return ragmi::fail(RAG_EINVAL, "sparse: n must be >= 0");
+  if (n > 0 && (!rows || !t || !v))
+    return ragmi::fail(RAG_EINVAL, "sparse: a NULL rows, terms or values pointer");
+  if (!h) return ragmi::fail(RAG_EINVAL, "sparse: index is NULL");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->sp_slots == 0)
+    return ragmi::fail(RAG_EINVAL, "sparse: no sparse column (call rag_index_sparse_create)");
+  if (n == 0) return RAG_OK;
+  RAG_HIP(hipSetDevice(h->device));
+  launch(grid1d(n * h->sp_slots, kSpBlock), static_cast<hipStream_t>(stream));
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// a sparse column of `cap` rows of S slots: rows [0, keep) copied from the old column (may be
+// NULL with keep = 0), the rest empty. On the null stream; synchronises the device.
+int alloc_sparse(int64_t cap, int S, const uint16_t* old_t, const float* old_v, int64_t keep,
+                 DeviceBuf<uint16_t>& nt, DeviceBuf<float>& nv) {
+  const int64_t slots = cap * S, kept = keep * S;
+  if (nt.alloc((size_t)std::max<int64_t>(slots, 1) * 2) != hipSuccess ||
+      nv.alloc((size_t)std::max<int64_t>(slots, 1) * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    return ragmi::fail(RAG_ENOMEM, "hipMalloc(sparse column) failed");
+  }
+  RAG_HIP(hipDeviceSynchronize());
+  if (kept > 0) {
+    RAG_HIP(hipMemcpy(nt.p, old_t, (size_t)kept * 2, hipMemcpyDeviceToDevice));
+    RAG_HIP(hipMemcpy(nv.p, old_v, (size_t)kept * 4, hipMemcpyDeviceToDevice));
+  }
+  if (slots > kept) {
+    sp_fill_kernel<<<grid1d(slots - kept, kSpBlock), dim3(kSpBlock), 0, nullptr>>>(nt.p, nv.p,
+                                                                                   kept, slots);
+    RAG_HIP(hipGetLastError());
+  }
+  RAG_HIP(hipDeviceSynchronize());
+  return RAG_OK;
+}
+
 // Diagnostic A/B of scan variants (see scan_kernel's knobs). Returns avg device ms/launch.
 template <int D, int V>
 void launch_variant(rag_index* h, Workspace& w, int grid, hipStream_t st) {
@@ -1175,6 +1361,8 @@ void ragmi::free_workspaces(rag_index* h) {
     ws_free_all(ws_buffers(h, w));
     ws_free_all(lk_buffers(w));
     ws_free_all(reco_buffers(w));
+    if (w.sp_tab) (void)hipFree(w.sp_tab);
+    w.sp_tab = nullptr;
     if (w.ev_in) (void)hipEventDestroy(w.ev_in);
     if (w.ev_out) (void)hipEventDestroy(w.ev_out);
   }
@@ -1184,6 +1372,26 @@ int ragmi::remap_shard_ids(int64_t* ids, int B, int k, int n, uint8_t* out_empty
   const unsigned gx = (unsigned)std::min<size_t>(1024, ((size_t)B * k + 255) / 256);
   remap_ids_kernel<<<dim3(gx, n), dim3(256), 0, st>>>(ids, B, k, n, out_empty);
   RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+int ragmi::sparse_move_rows(rag_index* h, const int64_t* src_rows, const int64_t* dst_rows,
+                            int64_t n, hipStream_t st) {
+  sp_move_kernel<<<grid1d(n * h->sp_slots, kSpBlock), dim3(kSpBlock), 0, st>>>(
+      h->sp_terms, h->sp_vals, src_rows, dst_rows, n, h->sp_slots, h->cap_rows);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+int ragmi::sparse_reserve(rag_index* h, int64_t cap) {
+  DeviceBuf<uint16_t> nt;
+  DeviceBuf<float> nv;
+  if (const int rc = alloc_sparse(cap, h->sp_slots, h->sp_terms, h->sp_vals, h->cap_rows, nt, nv))
+    return rc;
+  (void)hipFree(h->sp_terms);
+  (void)hipFree(h->sp_vals);
+  h->sp_terms = nt.release();
+  h->sp_vals = nv.release();
   return RAG_OK;
 }
 
@@ -1305,6 +1513,102 @@ int rag_index_recommend(rag_index_t* h, const float* pos, int n_pos, const float
   }
   return recommend_locked(h, r, k, filter, tags, id_offset, (flags & RAG_SEARCH_FULL) != 0, out_s,
                           out_i, st);
+}
+
+// ---- sparse vectors (sparse_kernels.hip) ----
+
+int rag_index_sparse_create(rag_index_t* h, int slots) {
+  ragmi::clear_error();
+  if (!h) return ragmi::fail(RAG_EINVAL, "sparse_create: index is NULL");
+  if (slots < 16 || slots > RAG_SPARSE_MAX_SLOTS || slots % 16 != 0)
+    return ragmi::fail(RAG_EINVAL, "sparse_create: slots must be a multiple of 16 in [16, 512]");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->sp_slots == slots) return RAG_OK;
+  if (h->sp_slots != 0)
+    return ragmi::fail(RAG_EINVAL, "sparse_create: the column exists with another slot count");
+  RAG_HIP(hipSetDevice(h->device));
+  DeviceBuf<uint16_t> nt;
+  DeviceBuf<float> nv;
+  if (const int rc = alloc_sparse(h->cap_rows, slots, nullptr, nullptr, 0, nt, nv)) return rc;
+  h->sp_terms = nt.release();
+  h->sp_vals = nv.release();
+  h->sp_slots = slots;
+  return RAG_OK;
+}
+
+int rag_index_sparse_slots(const rag_index_t* h) { return h ? h->sp_slots : 0; }
+
+int rag_index_sparse_write(rag_index_t* h, const int64_t* rows, const uint16_t* terms,
+                           const float* vals, int64_t n, void* stream) {
+  return sparse_rows_call(h, rows, terms, vals, n, stream, [&](dim3 grid, hipStream_t st) {
+    sp_write_kernel<<<grid, dim3(kSpBlock), 0, st>>>(h->sp_terms, h->sp_vals, rows, terms, vals, n,
+                                                     h->sp_slots, h->cap_rows);
+  });
+}
+
+int rag_index_sparse_gather(rag_index_t* h, const int64_t* rows, int64_t n, uint16_t* out_terms,
+                            float* out_vals, void* stream) {
+  return sparse_rows_call(h, rows, out_terms, out_vals, n, stream, [&](dim3 grid, hipStream_t st) {
+    sp_gather_kernel<<<grid, dim3(kSpBlock), 0, st>>>(h->sp_terms, h->sp_vals, rows, n,
+                                                      h->sp_slots, h->cap_rows, out_terms,
+                                                      out_vals);
+  });
+}
+
+int rag_index_sparse_df(rag_index_t* h, int64_t* out_df, void* stream) {
+  ragmi::clear_error();
+  if (!out_df) return ragmi::fail(RAG_EINVAL, "sparse_df: a NULL output pointer");
+  if (!h) return ragmi::fail(RAG_EINVAL, "sparse_df: index is NULL");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->sp_slots == 0)
+    return ragmi::fail(RAG_EINVAL, "sparse_df: no sparse column (call rag_index_sparse_create)");
+  RAG_HIP(hipSetDevice(h->device));
+  RAG_HIP(hipMemsetAsync(out_df, 0, (size_t)kSpTerms * 8, st));
+  const int64_t slots = h->count * h->sp_slots;
+  if (slots > 0) {
+    const int64_t grid = std::min<int64_t>(8 * h->n_cu, (slots + kSpBlock - 1) / kSpBlock);
+    sp_df_kernel<<<dim3((unsigned)grid), dim3(kSpBlock), 0, st>>>(
+        h->sp_terms, slots, reinterpret_cast<unsigned long long*>(out_df));
+    RAG_HIP(hipGetLastError());
+  }
+  return RAG_OK;
+}
+
+int rag_index_sparse_search(rag_index_t* h, const uint16_t* q_terms, const float* q_vals,
+                            const int32_t* q_nnz, int B, int k, const uint32_t* progs,
+                            int64_t words, int n_programs, const uint32_t* filters,
+                            int64_t id_offset, int flags, float* out_s, int64_t* out_i,
+                            void* stream) {
+  ragmi::clear_error();
+  if (B < 0 || (B > 0 && (!q_terms || !q_vals || !q_nnz || !out_s || !out_i)))
+    return ragmi::fail(RAG_EINVAL, "sparse_search: bad arguments (B < 0 or a NULL pointer)");
+  if (k < 1) return ragmi::fail(RAG_ERANGE, "sparse_search: k must be >= 1");
+  if (flags & ~RAG_SEARCH_FULL) return ragmi::fail(RAG_EINVAL, "sparse_search: unknown flags");
+  if (progs) {
+    if (const int rc = view_args(progs, words, n_programs)) return rc;
+  } else if (words != 0 || n_programs != 0) {
+    return ragmi::fail(RAG_EINVAL,
+                       "sparse_search: programs is NULL but words / n_programs are not 0");
+  }
+  if (!h) return ragmi::fail(RAG_EINVAL, "sparse_search: index is NULL");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->sp_slots == 0)
+    return ragmi::fail(RAG_EINVAL,
+                       "sparse_search: no sparse column (call rag_index_sparse_create)");
+  if (B == 0) return RAG_OK;
+  RAG_HIP(hipSetDevice(h->device));
+  // view and passes under this one hold of the lock (rag_index_search_view)
+  const uint32_t* tags = h->tags;
+  if (progs) {
+    uint32_t* v = nullptr;
+    if (const int rc = acquire_view(h, st, &v)) return rc;
+    if (const int rc = launch_filter_view(h, progs, words, n_programs, v, st)) return rc;
+    tags = v;
+  }
+  return sparse_search_locked(h, SparseQueries{q_terms, q_vals, q_nnz}, B, k, filters, tags,
+                              id_offset, (flags & RAG_SEARCH_FULL) != 0, out_s, out_i, st);
 }
 
 int rag_index_reco_bounds(rag_index_t* h, const float* pos, int n_pos, const float* neg, int n_neg,

@@ -299,6 +299,9 @@ int copy_rows(rag_index* h, const int64_t* src_rows, const int64_t* dst_rows, in
             key_cols(h), h->n_keys, src_rows, dst_rows, n, h->cap_rows);
         RAG_HIP(hipGetLastError());
       }
+    if constexpr (MODE == ragmi::kRowsMove)
+      if (h->sp_slots > 0)   // and so is the sparse row
+        if (const int rs = ragmi::sparse_move_rows(h, src_rows, dst_rows, n, st)) return rs;
     if constexpr (MODE != ragmi::kRowsGather)   // move / scatter wrote the rows dst_rows
       if (const int rq = requant(h, dst_rows, 0, n, st)) return rq;
   }
@@ -556,6 +559,8 @@ int rag_index_destroy(rag_index_t* h) {
   if (h->tags) (void)hipFree(h->tags);
   for (auto* k : h->keys)
     if (k) (void)hipFree(k);
+  if (h->sp_terms) (void)hipFree(h->sp_terms);
+  if (h->sp_vals) (void)hipFree(h->sp_vals);
   if (h->rows32) (void)hipFree(h->rows32);
   for (auto& c : h->copy) {
     if (c.data) (void)hipFree(c.data);
@@ -602,6 +607,9 @@ int rag_index_reserve(rag_index_t* h, int64_t capacity_rows) {
   for (int c = 0; c < h->n_keys; ++c)
     if ((rc = alloc_keys(cap, h->keys[c], h->cap_rows, nk[c]))) return rc;
   if (h->n_keys > 0) RAG_HIP(hipDeviceSynchronize());
+  // the sparse column regrows too: old rows keep their slots, new rows are empty
+  if (h->sp_slots > 0)
+    if ((rc = ragmi::sparse_reserve(h, cap))) return rc;
   RAG_HIP(hipMemcpy(nc.p, h->corpus, (size_t)h->cap_rows * h->dim * 2, hipMemcpyDeviceToDevice));
   RAG_HIP(hipMemcpy(nt.p, h->tags, (size_t)h->cap_rows * 4, hipMemcpyDeviceToDevice));
   if (n32.p)

@@ -171,6 +171,14 @@ INDEX_API = {
     "rag_index_reco_vector": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp,
                                              c_vp]),
     "rag_index_reco_stats": (ctypes.c_int, [c_vp, c_i64p]),
+    "rag_index_sparse_create": (ctypes.c_int, [c_vp, ctypes.c_int]),
+    "rag_index_sparse_slots": (ctypes.c_int, [c_vp]),
+    "rag_index_sparse_write": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "rag_index_sparse_gather": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "rag_index_sparse_df": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "rag_index_sparse_search": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int,
+                                               c_vp, ctypes.c_int64, ctypes.c_int, c_vp,
+                                               ctypes.c_int64, ctypes.c_int, c_vp, c_vp, c_vp]),
     "rag_index_select_rows_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp,
                                                   ctypes.c_int64, c_vp, c_vp]),
     "rag_shardset_search_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp,

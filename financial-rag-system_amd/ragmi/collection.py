@@ -21,9 +21,11 @@ from .filters import (DEFAULT_TAG_FIELDS, KEY_ABSENT, MAX_PROGRAMS, FilterProgra
                       PayloadRanges, PayloadTags, UnsupportedFilter, compile_filter,
                       compile_legacy_only, pack_view)
 from .formula import BAD, MISSING, NONFINITE, compile_formula
-from .index import (FUSION_MAX_ENTRIES, GROUPS_MAX, GROUPS_MAX_CELLS, ORDER_MAX, FlatIndex,
+from .index import (FUSION_MAX_ENTRIES, GROUPS_MAX, GROUPS_MAX_CELLS, ORDER_MAX,
+                    SPARSE_MAX_QUERY_NNZ, SPARSE_MAX_SLOTS, SPARSE_SLOTS, FlatIndex,
                     formula_rescore, fuse_rrf, hits_of, host_or_tensor)
 from .shardset import ShardSet, parse_devices
+from .sparse import idf_weights, pack_rows, unpack_row
 
 
 def _norm_id(pid):
@@ -40,6 +42,14 @@ def _norm_id(pid):
     if isinstance(pid, str):
         return str(uuid.UUID(pid))
     raise ValueError(f"unsupported point id type {type(pid)!r}")
+
+
+class SparsePrefetch:
+    """The query of a sparse prefetch of a fusion request: a SparseVector and the `using` it
+    came with (checked against the collection under its lock)."""
+
+    def __init__(self, vector, using):
+        self.vector, self.using = vector, using
 
 
 def _is_vector(example) -> bool:
@@ -108,6 +118,21 @@ def stack_queries(qs: list, dim: int, one: bool = False, host: bool = False,
     return Q
 
 
+class SparseBatch:
+    """The padded sparse queries of a batch (ragmi.sparse.pack_rows at 64 slots) as one object
+    the list builders index like a query array: batch[members] is the sub-batch."""
+
+    def __init__(self, terms, vals, nnz):
+        self.terms, self.vals, self.nnz = terms, vals, nnz
+
+    def __len__(self):
+        return len(self.nnz)
+
+    def __getitem__(self, members):
+        m = np.asarray(members, dtype=np.int64)
+        return SparseBatch(self.terms[m], self.vals[m], self.nnz[m])
+
+
 class Collection:
     """One COSINE collection: FlatIndex in HBM + host-side id/payload maps. With `devices`
     (one device index per shard, ragmi.shardset.parse_devices) the rows are striped over a
@@ -117,13 +142,17 @@ class Collection:
     `range_fields`: the numeric payload fields `range` conditions may name, a mapping of field
     to kind ("number" or "datetime") or a sequence of names all meaning "number" (at most 4;
     ragmi.filters.PayloadRanges). Each is a key column of the index, written with every upsert.
-    A collection without any never calls the index's key methods."""
+    A collection without any never calls the index's key methods.
+    `sparse`: None, or (name, idf, slots) — the collection's one named sparse vector (DESIGN
+    R19): a sparse column of `slots` slots per row in the index, written with every upsert (an
+    empty row for a point without a sparse vector); idf: Modifier.IDF. A collection without one
+    never calls the index's sparse methods."""
 
     BACKFILL_ROWS = 1 << 16      # rows per write_keys call of add_range_field
 
     def __init__(self, name: str, dim: int, device, tag_fields=DEFAULT_TAG_FIELDS,
                  capacity: int = 1024, storage: str = "fp32", devices=None, *, index=None,
-                 range_fields=None):
+                 range_fields=None, sparse=None):
         self.name = name
         self.dim = dim
         self.tags = PayloadTags(tag_fields)
@@ -149,6 +178,25 @@ class Collection:
                                    search=self.search_points)
         if len(self.ranges):
             self.index.keys_create(len(self.ranges))
+        self.sparse_name, self.sparse_idf, self.sparse_slots = None, False, 0
+        self.sparse_len: list[int] = []      # per row, the nonzeros of its sparse row
+        self._df = None                      # (df int64 [65535] host, N) of Modifier.IDF, cached
+        if sparse is not None:
+            name, idf, slots = sparse
+            slots = SPARSE_SLOTS if slots is None else int(slots)
+            if not isinstance(name, str) or name == "":
+                self.index.close()
+                raise ValueError('a sparse vector needs a name other than "" (the dense vector)')
+            if not 16 <= slots <= SPARSE_MAX_SLOTS or slots % 16:
+                self.index.close()
+                raise ValueError(f"sparse_slots must be a multiple of 16 in [16, "
+                                 f"{SPARSE_MAX_SLOTS}], got {slots}")
+            try:
+                self.index.sparse_create(slots)
+            except BaseException:
+                self.index.close()
+                raise
+            self.sparse_name, self.sparse_idf, self.sparse_slots = name, bool(idf), slots
 
     @property
     def rescued(self) -> int:
@@ -189,7 +237,9 @@ class Collection:
             return True
 
     # ---------------------------------------------------------------- writes
-    def upsert(self, ids: list, vectors, payloads: list) -> int:
+    def upsert(self, ids: list, vectors, payloads: list, sparse: list | None = None) -> int:
+        """`sparse`: per point its SparseVector or None, in a collection with a sparse vector
+        (a point without one gets an empty sparse row: an upsert replaces the whole point)."""
         with self.lock:
             self.op += 1
             vec = host_or_tensor(vectors)
@@ -197,6 +247,13 @@ class Collection:
                 raise ValueError(f"vectors must be [n, {self.dim}]")
             require_finite(vec, "upsert: the vector of point",
                            list(ids) if len(ids) == vec.shape[0] else None)
+            sp = None
+            if self.sparse_name is not None:
+                # refused before anything is written: the error names the point
+                sp = pack_rows(list(sparse) if sparse is not None else [None] * len(ids),
+                               self.sparse_slots, list(ids), "upsert: the sparse vector of point")
+            elif sparse is not None and any(v is not None for v in sparse):
+                raise ValueError(f"collection {self.name!r} has no sparse vector")
             # last write wins for duplicate ids inside one batch (Qdrant semantics)
             last: dict[Any, int] = {}
             for i, pid in enumerate(ids):
@@ -212,6 +269,8 @@ class Collection:
                     self.row_ids.append(pid)
                     self.payloads.append(None)
                     self.versions.append(0)
+                    if sp is not None:
+                        self.sparse_len.append(0)
                 p = payloads[i] if payloads is not None else None
                 self.payloads[r] = dict(p) if p is not None else None
                 self.versions[r] = self.op
@@ -231,6 +290,14 @@ class Collection:
                 for c, col_keys in enumerate(np.asarray(keys, dtype=np.int64).T if keys else ()):
                     self.index.write_keys(c, np.asarray(rows, dtype=np.int64),
                                           np.ascontiguousarray(col_keys))
+                if sp is not None:
+                    # the sparse row of every written row, under this hold of the lock
+                    pick = np.asarray(sel)
+                    self.index.sparse_write(np.asarray(rows, dtype=np.int64), sp[0][pick],
+                                            sp[1][pick])
+                    for r, m in zip(rows, sp[2][pick].tolist()):
+                        self.sparse_len[r] = m
+                    self._df = None
             return self.op
 
     def delete(self, points_selector) -> int:
@@ -268,7 +335,12 @@ class Collection:
             self.payloads[d] = self.payloads[s]
             self.versions[d] = self.versions[s]
             self.id_to_row[pid] = d
+            if self.sparse_name is not None:      # the device moved the sparse row with the rest
+                self.sparse_len[d] = self.sparse_len[s]
         del self.row_ids[n1:], self.payloads[n1:], self.versions[n1:]
+        if self.sparse_name is not None:
+            del self.sparse_len[n1:]
+            self._df = None
 
     # ---------------------------------------------------------------- reads
     def _matching(self, c, cap: int | None = None):
@@ -346,14 +418,16 @@ class Collection:
             return self._exact_lists(q, k, self._pairs(fl))
         return self._view_lists(q, fl, k)
 
-    def _view_lists(self, q, fl: list, k: int):
+    def _view_lists(self, q, fl: list, k: int, lists=None):
         """_lists with general filters among the live ones: the batch's distinct programs
         share view bits (a (mask, value) pair rides as its one-atom MASKEQ program; (0, 0)
         needs no bit, over any view it passes every row), every query gets the filter
         (1 << slot, 1 << slot), and one view search answers the batch. More than MAX_PROGRAMS
         distinct programs: the queries are dealt into calls of at most that many, each query
         into the first call that knows its program or has a free bit, and the results are
-        scattered back."""
+        scattered back. `lists`: the list builder (q, k, use, programs=) -> (scores, rows),
+        _exact_lists unless the queries are sparse (_sparse_exact)."""
+        lists = lists or self._exact_lists
         calls: list = []                       # (slots: {program: bit}, members, their filters)
         for j, f in enumerate(fl):
             prog = (f if isinstance(f, FilterProgram) else
@@ -374,8 +448,8 @@ class Collection:
             blob = pack_view(list(slots))
             use = np.asarray(bits, dtype=np.uint32).reshape(-1, 2)
             if len(calls) == 1:
-                return self._exact_lists(q, k, use, programs=blob)
-            s1, i1 = self._exact_lists(q[members], k, use, programs=blob)
+                return lists(q, k, use, programs=blob)
+            s1, i1 = lists(q[members], k, use, programs=blob)
             if s is None:
                 s = torch.empty((len(fl), k), dtype=s1.dtype, device=s1.device)
                 ids = torch.empty((len(fl), k), dtype=i1.dtype, device=i1.device)
@@ -392,6 +466,88 @@ class Collection:
         of its view."""
         view = {} if programs is None else {"programs": programs}
         return self.index.search(q, k, filters=use, rescue=True, **view)
+
+    # ---------------------------------------------------------------- sparse queries
+    def _need_sparse(self, using, what: str) -> None:
+        """ValueError unless `using` names this collection's sparse vector."""
+        if self.sparse_name is None:
+            raise ValueError(f"{what}: collection {self.name!r} has no sparse vector (create it "
+                             "with sparse_vectors_config={name: SparseVectorParams()})")
+        if using is None:
+            raise ValueError(f"{what}: a SparseVector query needs using={self.sparse_name!r}, the "
+                             "name of the collection's sparse vector")
+        if using != self.sparse_name:
+            raise ValueError(f"{what}: using={using!r} is not a vector of collection "
+                             f"{self.name!r}; its sparse vector is {self.sparse_name!r}")
+
+    def sparse_stats(self):
+        """(df, N) of Modifier.IDF: the document frequency of every term (host int64 [65535],
+        rag_index_sparse_df) and the points with a non-empty sparse row. Cached; every upsert and
+        delete invalidates it. Called under the lock; the first call after a write synchronises."""
+        if self._df is None:
+            self._df = (self.index.sparse_df().cpu().numpy(),
+                        sum(1 for m in self.sparse_len if m > 0))
+        return self._df
+
+    def sparse_batch(self, vectors: list, what: str) -> SparseBatch:
+        """Sparse query vectors as the padded batch the index takes, refused as
+        ragmi.sparse.entries refuses them and above SPARSE_MAX_QUERY_NNZ nonzeros; under
+        Modifier.IDF every weight is multiplied by its term's IDF (ragmi.sparse.idf_weights).
+        Called under the lock."""
+        for i, v in enumerate(vectors):
+            n = len(getattr(v, "indices", None) or ())
+            if n > SPARSE_MAX_QUERY_NNZ:
+                # (explicit zeros count here: the refusal must not depend on the values)
+                raise ValueError(f"{what} at position {i}: {n} entries, a sparse query holds at "
+                                 f"most {SPARSE_MAX_QUERY_NNZ} (RAG_SPARSE_MAX_QUERY_NNZ)")
+        terms, vals, nnz = pack_rows(vectors, SPARSE_MAX_QUERY_NNZ, None, what)
+        if self.sparse_idf and len(nnz) and self.index.count:
+            df, n_docs = self.sparse_stats()
+            for i, m in enumerate(nnz.tolist()):
+                vals[i, :m] = idf_weights(terms[i, :m], vals[i, :m], df, n_docs)
+        return SparseBatch(terms, vals, nnz)
+
+    def _sparse_exact(self, q: SparseBatch, k: int, use, programs=None):
+        """_exact_lists for sparse queries: the index's sparse search with rescue."""
+        view = {} if programs is None else {"programs": programs}
+        return self.index.sparse_search(q.terms, q.vals, q.nnz, k, filters=use, rescue=True,
+                                        **view)
+
+    def _sparse_lists(self, q: SparseBatch, fl: list, k: int):
+        """The exact sparse top-k lists of a batch whose compiled filters `fl` are all live:
+        (mask, value) pairs ride as they are, general filters through the view path."""
+        if not any(isinstance(f, FilterProgram) for f in fl):
+            return self._sparse_exact(q, k, self._pairs(fl))
+        return self._view_lists(q, fl, k, lists=self._sparse_exact)
+
+    def search_sparse(self, requests: list):
+        """Sparse queries. `requests`: per request (SparseVector, using, compiled
+        filter, limit). The requests of the batch ride one sparse search at k = the largest
+        limit (clamped to the collection's count), 32 per pass. The score is the sparse score; a
+        point that shares no term with the query is no hit, so a list may be shorter than its
+        limit. Returns per request [(row, score)], best first."""
+        with self.lock:
+            for _, using, _, _ in requests:
+                self._need_sparse(using, "sparse query")
+            batch = self.sparse_batch([v for v, _, _, _ in requests], "sparse query")
+            out = [[] for _ in requests]
+            count = self.index.count
+            live = [i for i, (_, _, c, lim) in enumerate(requests) if c is not None and lim >= 1]
+            if not live or count == 0:
+                return out
+            lims = [int(requests[i][3]) for i in live]
+            k = min(max(lims), count)
+            s, ids = self._sparse_lists(batch[live] if len(live) != len(requests) else batch,
+                                        [requests[i][2] for i in live], k)
+            for i, n, h in zip(live, lims, hits_of(s, ids)):
+                out[i] = h[:n]
+            return out
+
+    def search_points_sparse(self, requests: list, with_vectors=False):
+        """search_sparse with every hit resolved to its ScoredPoint under the same hold of the
+        lock (_points)."""
+        with self.lock:
+            return self._points(self.search_sparse(requests), with_vectors)
 
     def search_mmr(self, queries, limits, filters: list, diversity, candidates):
         """search with MMR re-selection, per request b: limits[b] hits chosen at diversity[b]
@@ -492,15 +648,19 @@ class Collection:
         with self.lock:
             return self._points(self.search_recommend(requests), with_vectors)
 
-    @staticmethod
-    def _check_prefetch_vectors(requests: list, route: str) -> None:
+    def _check_prefetch_vectors(self, requests: list, route: str) -> None:
         """Every prefetch vector of a fusion or formula request list, searched or not, so that
-        a refusal does not depend on the limits (require_finite): the error names the request
-        and the prefetch."""
+        a refusal does not depend on the limits (require_finite; a sparse prefetch:
+        _need_sparse and sparse_batch's refusals): the error names the request and the
+        prefetch."""
         for b, (_, pres, _) in enumerate(requests):
             for l, (vec, _, _) in enumerate(pres):
-                require_finite(host_or_tensor(vec).reshape(1, -1),
-                               f"{route}: request {b}, the query of prefetch", [l])
+                what = f"{route}: request {b}, the query of prefetch"
+                if isinstance(vec, SparsePrefetch):
+                    self._need_sparse(vec.using, f"{what} {l}")
+                    self.sparse_batch([vec.vector], f"{what} {l}")
+                else:
+                    require_finite(host_or_tensor(vec).reshape(1, -1), what, [l])
 
     def search_fusion(self, requests: list):
         """Fusion queries. `requests`: per request (rrf_k, [(vector, Filter or
@@ -509,7 +669,10 @@ class Collection:
         collection's count); the lists are arranged [B, Lmax, C] on the device, each cut to
         its own limit by ncand, and fused by rag_fuse_rrf in one launch per distinct rrf_k. A
         prefetch whose filter can match nothing, or whose limit is < 1, is an empty list and
-        is not searched. Returns per request [(row, fused score)], best first."""
+        is not searched. A prefetch whose vector is a SparsePrefetch (hybrid search, DESIGN
+        §R19) rides one batched sparse search beside the dense one, into the same row tensor;
+        its list is cut by ncand to its real hits (rows sharing a term), which may be fewer
+        than its limit. Returns per request [(row, fused score)], best first."""
         with self.lock:
             out = [[] for _ in requests]
             count = self.index.count
@@ -535,13 +698,26 @@ class Collection:
                 raise ValueError(f"fusion: {Lmax} prefetches of up to {C} hits are {Lmax * C} "
                                  f"entries; at most {FUSION_MAX_ENTRIES} (prefetches x the "
                                  "largest prefetch limit) are fused")
-            _, ids = self._lists(stack_queries(qs, self.dim), filters, list(range(len(qs))), C)
-            dev = ids.device
+            dense = [j for j, v in enumerate(qs) if not isinstance(v, SparsePrefetch)]
+            sparse = [j for j, v in enumerate(qs) if isinstance(v, SparsePrefetch)]
+            dev = self.index.device
             rows = torch.full((len(live), Lmax, C), -1, dtype=torch.int64, device=dev)
             at = np.asarray([(slot[b], l) for b, l, _ in where], dtype=np.int64)
-            rows[torch.from_numpy(at[:, 0]).to(dev), torch.from_numpy(at[:, 1]).to(dev)] = ids
             ncand = np.zeros((len(live), Lmax), dtype=np.int32)
             ncand[at[:, 0], at[:, 1]] = [n for _, _, n in where]
+            if dense:
+                _, ids = self._lists(stack_queries([qs[j] for j in dense], self.dim),
+                                     [filters[j] for j in dense], list(range(len(dense))), C)
+                rows[torch.from_numpy(at[dense, 0]).to(dev),
+                     torch.from_numpy(at[dense, 1]).to(dev)] = ids
+            if sparse:
+                batch = self.sparse_batch([qs[j].vector for j in sparse], "fusion: sparse prefetch")
+                _, ids = self._sparse_lists(batch, [filters[j] for j in sparse], C)
+                rows[torch.from_numpy(at[sparse, 0]).to(dev),
+                     torch.from_numpy(at[sparse, 1]).to(dev)] = ids
+                real = (ids >= 0).sum(dim=1).cpu().numpy().astype(np.int32)
+                ncand[at[sparse, 0], at[sparse, 1]] = np.minimum(
+                    ncand[at[sparse, 0], at[sparse, 1]], real)
             lim = [int(requests[b][2]) for b in live]
             k = min(max(lim), Lmax * C)
             by_k: dict[int, list] = {}
@@ -835,5 +1011,9 @@ class Collection:
         if with_vectors:
             vec = (self.index.export_rows32(row, 1)[0] if self.index.storage == "fp32" else
                    self.index.export_rows(row, 1)[0].view(np.float16).astype(np.float32)).tolist()
+            if self.sparse_name is not None:     # a collection with a sparse vector names both
+                t, v = self.index.sparse_gather(np.asarray([row], dtype=np.int64))
+                vec = {"": vec, self.sparse_name: unpack_row(t[0].cpu().numpy(),
+                                                             v[0].cpu().numpy())}
         return models.ScoredPoint(id=self.row_ids[row], version=self.versions[row],
                                   score=score, payload=payload, vector=vec)

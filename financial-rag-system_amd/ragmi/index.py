@@ -43,6 +43,30 @@ RECO_AVERAGE, RECO_BEST, RECO_SUM = 0, 1, 2   # RAG_RECO_AVERAGE / _BEST / _SUM
 RECO_MAX_SIDE = 16                 # RAG_RECO_MAX_SIDE: examples per side of a recommend request
 RECO_STRATEGIES = {"average_vector": RECO_AVERAGE, "best_score": RECO_BEST,
                    "sum_scores": RECO_SUM}
+SPARSE_TERM_NONE = 0xFFFF          # RAG_SPARSE_TERM_NONE: the term of an empty slot
+SPARSE_TERMS = 65535               # sparse terms lie in [0, SPARSE_TERMS)
+SPARSE_SLOTS = 128                 # default slots per row of a sparse column
+SPARSE_MAX_SLOTS = 512             # RAG_SPARSE_MAX_SLOTS
+SPARSE_MAX_QUERY_NNZ = 64          # RAG_SPARSE_MAX_QUERY_NNZ: slots of a padded sparse query
+SPARSE_MAX_UNION = 512             # RAG_SPARSE_MAX_UNION: distinct terms of one pass's queries
+
+
+def sparse_groups(q_terms, q_nnz, max_queries: int = QUERY_TILE,
+                  max_union: int = SPARSE_MAX_UNION) -> list:
+    """The passes of a sparse search: [(b0, b1), ...] covering the B padded queries in order,
+    each a run of at most `max_queries` consecutive queries whose distinct terms number at most
+    `max_union` (the scorer's LDS weight table). Greedy: a query that would overflow the union
+    opens the next pass; one query alone always fits (64 <= 512). Pure host code."""
+    groups, b0, union = [], 0, set()
+    for b in range(len(q_nnz)):
+        terms = set(np.asarray(q_terms[b][:int(q_nnz[b])]).tolist())
+        if b > b0 and (b - b0 == max_queries or len(union | terms) > max_union):
+            groups.append((b0, b))
+            b0, union = b, set()
+        union |= terms
+    if len(q_nnz) > b0:
+        groups.append((b0, len(q_nnz)))
+    return groups
 
 
 class RecoStats(NamedTuple):
@@ -565,6 +589,107 @@ class FlatIndex(ListOps):
                                             r.numel(), out.data_ptr() if r.numel() else None,
                                             _stream_ptr(self.device)))
         return out
+
+    # ---------------------------------------------------------------- sparse column
+    def sparse_create(self, slots: int = SPARSE_SLOTS) -> None:
+        """Make the index hold a sparse column of `slots` slots per row (a multiple of 16 in
+        [16, 512]; rag_index_sparse_create): terms uint16 and values fp32 [capacity, slots], new
+        rows empty. The same slot count again is a no-op, another one refused. Synchronises the
+        device."""
+        check(self._L.rag_index_sparse_create(self._h, int(slots)))
+
+    def sparse_slots(self) -> int:
+        """Slots per row of the sparse column, 0 without one (rag_index_sparse_slots)."""
+        return int(self._L.rag_index_sparse_slots(self._h))
+
+    def _sparse_rows(self, rows):
+        S = self.sparse_slots()
+        if S == 0:
+            raise ValueError("the index has no sparse column (sparse_create)")
+        return S, _as_dev(rows, torch.int64, self.device).reshape(-1)
+
+    def sparse_write(self, rows, terms, vals) -> None:
+        """Sparse row rows[i] = (terms[i], vals[i]): uint16 / fp32 [n, slots] in the stored layout
+        (ragmi.sparse.pack_rows; include/ragmi.h "Sparse vectors"), distinct rows, one outside
+        [0, capacity) skipped (rag_index_sparse_write). Enqueued on the current stream."""
+        S, r = self._sparse_rows(rows)
+        t = _as_dev(np.asarray(terms, np.uint16).view(np.int16)
+                    if not isinstance(terms, torch.Tensor) else terms, torch.int16, self.device)
+        v = _as_dev(vals, torch.float32, self.device)
+        if tuple(t.shape) != (r.numel(), S) or tuple(v.shape) != (r.numel(), S):
+            raise ValueError(f"terms and vals must be [n, {S}]")
+        if r.numel():
+            check(self._L.rag_index_sparse_write(self._h, r.data_ptr(), t.data_ptr(), v.data_ptr(),
+                                                 r.numel(), _stream_ptr(self.device)))
+
+    def sparse_gather(self, rows):
+        """The stored sparse rows of `rows`: (terms int16 [n, slots] holding the uint16 bits, vals
+        fp32 [n, slots]) as cuda tensors, an empty row for a row outside [0, capacity)
+        (rag_index_sparse_gather). Enqueued on the current stream."""
+        S, r = self._sparse_rows(rows)
+        t = torch.empty((r.numel(), S), dtype=torch.int16, device=self.device)
+        v = torch.empty((r.numel(), S), dtype=torch.float32, device=self.device)
+        if r.numel():
+            check(self._L.rag_index_sparse_gather(self._h, r.data_ptr(), r.numel(), t.data_ptr(),
+                                                  v.data_ptr(), _stream_ptr(self.device)))
+        return t, v
+
+    def sparse_df(self) -> torch.Tensor:
+        """Document frequency: an int64 cuda tensor [65535], entry t the rows below the count
+        that hold term t (rag_index_sparse_df). Enqueued on the current stream."""
+        out = torch.empty((SPARSE_TERMS,), dtype=torch.int64, device=self.device)
+        check(self._L.rag_index_sparse_df(self._h, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
+    def sparse_search(self, q_terms, q_vals, q_nnz, k: int, filters=None, programs=None,
+                      n_programs: int | None = None, full: bool = False, rescue: bool = False,
+                      id_offset: int = 0):
+        """Top-k of B sparse queries by the sparse score (rag_index_sparse_search; the contract:
+        include/ragmi.h "Sparse vectors"). The queries are padded host arrays
+        (ragmi.sparse.pack_rows at 64 slots): q_terms uint16 [B, 64] ascending, q_vals fp32
+        [B, 64], q_nnz [B]. Returns (scores fp32 [B, k], ids int64 [B, k]) as cuda tensors, -inf /
+        -1 past the eligible rows. `filters`, `programs`: as in search. The queries go to the
+        device in groups of consecutive queries, at most 32 and at most SPARSE_MAX_UNION distinct
+        terms each (sparse_groups): one pass of the hot path per group. full=True forces the full
+        pass. rescue=True: queries the hot pass left unanswered (more than 16384 rows at or above
+        the threshold) are re-run on the full pass (rescue_unanswered; synchronises)."""
+        qt = np.ascontiguousarray(np.asarray(q_terms, np.uint16))
+        qv = np.ascontiguousarray(np.asarray(q_vals, np.float32))
+        qn = np.ascontiguousarray(np.asarray(q_nnz, np.int32).reshape(-1))
+        B = qn.shape[0]
+        if qt.shape != (B, SPARSE_MAX_QUERY_NNZ) or qv.shape != qt.shape:
+            raise ValueError(f"sparse queries are padded to [B, {SPARSE_MAX_QUERY_NNZ}]")
+        if B and (int(qn.min()) < 0 or int(qn.max()) > SPARSE_MAX_QUERY_NNZ):
+            raise ValueError(f"a sparse query holds 0 to {SPARSE_MAX_QUERY_NNZ} nonzeros")
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        if self.sparse_slots() == 0:
+            raise ValueError("the index has no sparse column (sparse_create)")
+        f = None
+        if filters is not None:
+            f = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(filters, dtype=np.uint32).reshape(B, 2)).view(np.int32)).to(self.device)
+        view = None if programs is None else view_blob(programs, n_programs, self.device)
+        vp, words, U = (None, 0, 0) if view is None else (view[0].data_ptr(), view[1], view[2])
+        s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        t_dev = torch.from_numpy(qt.view(np.int16)).to(self.device)
+        v_dev = torch.from_numpy(qv).to(self.device)
+        n_dev = torch.from_numpy(qn).to(self.device)
+        for b0, b1 in ([(0, B)] if full else sparse_groups(qt, qn)):
+            check(self._L.rag_index_sparse_search(
+                self._h, t_dev[b0:].data_ptr(), v_dev[b0:].data_ptr(), n_dev[b0:].data_ptr(),
+                b1 - b0, int(k), vp, words, U, f[b0:].data_ptr() if f is not None else None,
+                int(id_offset), SEARCH_FULL if full else 0, s[b0:].data_ptr(),
+                ids[b0:].data_ptr(), _stream_ptr(self.device)))
+        if rescue and not full:
+            def again(redo):
+                return self.sparse_search(qt[redo], qv[redo], qn[redo], k,
+                                          None if f is None else f[redo].cpu().numpy(),
+                                          None if view is None else view[0], U or None, full=True,
+                                          id_offset=id_offset)
+            rescue_unanswered(self, s, ids, again)
+        return s, ids
 
     # ---------------------------------------------------------------- row removal
     def select_rows(self, tag_mask: int, tag_value: int, cap: int | None = None,

@@ -35,10 +35,12 @@ import numpy as np
 
 from . import qdrant_models as models
 from .coalesce import Coalescer                                           # noqa: F401
-from .collection import Collection, _norm_id, parse_selector, stack_queries  # noqa: F401
+from .collection import (Collection, SparsePrefetch, _norm_id, parse_selector,  # noqa: F401
+                         stack_queries)
 from .filters import (DEFAULT_TAG_FIELDS, PayloadTags, UnsupportedFilter,  # noqa: F401
                       compile_filter)
-from .index import FUSION_MAX_LISTS, MAX_K, MMR_MAX_CANDIDATES, RECO_MAX_SIDE, reco_strategy
+from .index import (FUSION_MAX_LISTS, MAX_K, MMR_MAX_CANDIDATES, RECO_MAX_SIDE, SPARSE_SLOTS,
+                    reco_strategy)
 from .shardset import parse_devices
 
 
@@ -53,6 +55,67 @@ def _storage_of(vectors_config) -> str:
     if str(dt).lower() == "float16":
         return "fp16"
     raise NotImplementedError(f"vector datatype {dt!r} (float32 and float16 are supported)")
+
+
+def sparse_config(sparse_vectors_config, sparse_slots):
+    """create_collection's sparse arguments -> Collection's `sparse` (name, idf, slots), None
+    without a sparse vector. Exactly one sparse name is built (more: NotImplementedError), the
+    name may not be "" (the dense vector), SparseIndexParams is accepted and ignored except for a
+    datatype other than float32 (NotImplementedError)."""
+    if not sparse_vectors_config:
+        return None
+    if not isinstance(sparse_vectors_config, dict):
+        raise ValueError("sparse_vectors_config is a dict {name: SparseVectorParams(...)}")
+    if len(sparse_vectors_config) > 1:
+        raise NotImplementedError("one sparse vector per collection is built, got "
+                                  f"{sorted(sparse_vectors_config)}")
+    (name, par), = sparse_vectors_config.items()
+    if not isinstance(name, str) or name == "":
+        raise ValueError('a sparse vector needs a name other than "" (the dense vector)')
+    par = par if par is not None else models.SparseVectorParams()
+    dt = getattr(getattr(par, "index", None), "datatype", None)
+    dt = getattr(dt, "value", dt)
+    if dt is not None and str(dt).lower() != "float32":
+        raise NotImplementedError(f"sparse vector datatype {dt!r} (float32 is stored)")
+    mod = getattr(par, "modifier", None)
+    mod = getattr(mod, "value", mod)
+    if mod not in (None, models.Modifier.NONE.value, models.Modifier.IDF.value):
+        raise ValueError(f"unknown sparse modifier {par.modifier!r}: Modifier.NONE or Modifier.IDF")
+    return name, mod == models.Modifier.IDF.value, int(sparse_slots)
+
+
+def split_vectors(col: Collection, ids: list, vectors) -> tuple:
+    """(dense vectors, sparse list or None) of an upsert's vectors. A plain list or array of
+    vectors means "dense only". A dict per point (PointStruct.vector) or one dict of lists
+    (Batch.vectors) names them: "" is the dense vector and is required, the collection's sparse
+    name maps to a SparseVector (absent or None: none); any other name is a ValueError."""
+    def names_ok(d, who):
+        for name in d:
+            if name != "" and name != col.sparse_name:
+                raise ValueError(f"{who}: {name!r} is not a vector of collection {col.name!r} "
+                                 f'(it has "" and '
+                                 + (repr(col.sparse_name) if col.sparse_name else "no sparse vector")
+                                 + ")")
+        if "" not in d or d[""] is None:
+            raise ValueError(f'{who}: the dense vector (the "" entry) is required')
+    if isinstance(vectors, dict):                       # Batch.vectors = {name: [per point]}
+        names_ok(vectors, "upsert")
+        sp = vectors.get(col.sparse_name) if col.sparse_name else None
+        if sp is not None and len(sp) != len(ids):
+            raise ValueError(f"upsert: {len(sp)} sparse vectors for {len(ids)} ids")
+        return vectors[""], (list(sp) if sp is not None else None)
+    if isinstance(vectors, (list, tuple)) and any(isinstance(v, dict) for v in vectors):
+        dense, sp = [], []
+        for pid, v in zip(ids, vectors):
+            if isinstance(v, dict):
+                names_ok(v, f"upsert: point {pid!r}")
+                dense.append(v[""])
+                sp.append(v.get(col.sparse_name) if col.sparse_name else None)
+            else:
+                dense.append(v)
+                sp.append(None)
+        return dense, sp
+    return vectors, None
 
 
 MMR_DIVERSITY = 0.5          # Mmr(diversity=None)
@@ -127,13 +190,16 @@ def fusion_params(query, prefetch, limit, query_filter=None):
                          "each Prefetch(filter=...)")
     if not _is_int(limit):
         raise ValueError("a fusion query needs an int limit")
-    return int(rrf_k), prefetch_lists(prefetch, "fusion", "to fuse", "fuses")
+    return int(rrf_k), prefetch_lists(prefetch, "fusion", "to fuse", "fuses", sparse_ok=True)
 
 
-def prefetch_lists(prefetch, what: str, to: str, verb: str) -> list:
+def prefetch_lists(prefetch, what: str, to: str, verb: str, sparse_ok: bool = False) -> list:
     """[(vector, Filter or None, limit), ...] of the prefetches of a `what` query — a Prefetch or
     a list of 1 to RAG_FUSION_MAX_LISTS of them, each a plain nearest query with an int limit —
-    or ValueError naming what is wrong or not built."""
+    or ValueError naming what is wrong or not built. sparse_ok (fusion): a prefetch may be
+    Prefetch(query=SparseVector(...), using=name, ...); its vector comes back as a
+    SparsePrefetch, whose `using` the collection checks. Elsewhere a sparse prefetch is refused,
+    naming the route."""
     if isinstance(prefetch, models.Prefetch):
         prefetch = [prefetch]
     if prefetch is None or len(prefetch) == 0:
@@ -148,6 +214,20 @@ def prefetch_lists(prefetch, what: str, to: str, verb: str) -> list:
         if p.prefetch is not None:
             raise ValueError(f"prefetch[{n}]: a nested Prefetch.prefetch is not built")
         vec, mmr = nearest_of(p.query)
+        using = getattr(p, "using", None)
+        if isinstance(vec, models.SparseVector):
+            if not sparse_ok:
+                raise ValueError(f"prefetch[{n}]: a sparse prefetch inside a {what} query is not "
+                                 "built; sparse prefetches are fused (FusionQuery / RrfQuery)")
+            if mmr is not None:
+                raise ValueError(f"prefetch[{n}]: an MMR query over a sparse vector is not built")
+            if not _is_int(p.limit):
+                raise ValueError(f"prefetch[{n}] needs an int limit")
+            out.append((SparsePrefetch(vec, using), p.filter, int(p.limit)))
+            continue
+        if using not in (None, ""):
+            raise ValueError(f"prefetch[{n}]: using={using!r} names a sparse vector, but the "
+                             "query is a dense vector: pass a SparseVector, or drop `using`")
         if isinstance(vec, models.OrderByQuery):
             raise ValueError(f"prefetch[{n}]: an OrderByQuery inside a Prefetch is not built")
         if isinstance(vec, models.RecommendQuery):
@@ -181,6 +261,7 @@ def formula_params(query, prefetch, limit, query_filter=None) -> list:
 FUSION, FORMULA, MMR, PLAIN = "fusion", "formula", "mmr", "plain"   # the routes of a request
 ORDER = "order"
 RECOMMEND = "recommend"
+SPARSE = "sparse"
 
 
 def route_of(query, prefetch=None) -> str:
@@ -188,7 +269,10 @@ def route_of(query, prefetch=None) -> str:
     FormulaQuery), FUSION (prefetched lists fused; every other use of a prefetch goes there to
     be refused), ORDER (an OrderByQuery: no vector, the points by a range field's value), MMR (a
     NearestQuery with an Mmr), RECOMMEND (a RecommendQuery, with or without a prefetch: it
-    refuses the prefetch itself) or PLAIN."""
+    refuses the prefetch itself), SPARSE (a SparseVector, bare or the `nearest` of a NearestQuery,
+    with or without a prefetch: it refuses the prefetch and an Mmr itself) or PLAIN."""
+    if isinstance(nearest_of(query)[0], models.SparseVector):
+        return SPARSE
     if isinstance(query, models.FormulaQuery):
         return FORMULA
     if isinstance(query, models.RecommendQuery):
@@ -246,17 +330,49 @@ def recommend_params(query, limit) -> tuple:
 
 def recommend_request(col: Collection, req) -> tuple:
     """(positive, negative, strategy, compiled filter, limit) of a RECOMMEND request, or
-    ValueError: prefetched candidates cannot be recommended from, and neither a named vector
-    (`using`) nor another collection's points (`lookup_from`) exist here."""
+    ValueError: prefetched candidates cannot be recommended from, recommend scores the dense
+    vector only (`using`, SparseVector examples) and knows no other collection's points
+    (`lookup_from`)."""
     if getattr(req, "prefetch", None) is not None:
         raise ValueError("a RecommendQuery over prefetched candidates (prefetch=...) is not "
                          "built: it scores every point a query_filter matches")
     for name in ("using", "lookup_from"):
         if getattr(req, name, None) is not None:
-            raise ValueError(f"a RecommendQuery with {name}=... is not built: a collection has "
-                             "one unnamed vector and examples are its own points")
+            raise ValueError(f"a RecommendQuery with {name}=... is not built: recommend scores "
+                             "the dense (unnamed) vector and examples are the collection's own "
+                             "points")
     pos, neg, strategy = recommend_params(req.query, req.limit)
+    if any(isinstance(x, models.SparseVector) for x in pos + neg):
+        raise ValueError("a RecommendQuery with SparseVector examples is not built: recommend "
+                         "scores the dense vector")
     return pos, neg, strategy, col.compile_filter(req.filter), int(req.limit)
+
+
+def sparse_request(col: Collection, req) -> tuple:
+    """(SparseVector, using, compiled filter, limit) of a SPARSE request, or ValueError:
+    prefetched candidates cannot be re-scored by a sparse query, MMR over a sparse vector is not
+    built, the limit must be an int. `using` is checked by the collection."""
+    vec, mmr = nearest_of(req.query)
+    if getattr(req, "prefetch", None) is not None:
+        raise ValueError("a sparse query over prefetched candidates (prefetch=...) is not built: "
+                         "fuse a sparse Prefetch with FusionQuery(Fusion.RRF) instead")
+    if mmr is not None:
+        raise ValueError("an MMR query (NearestQuery.mmr) over a sparse vector is not built")
+    if getattr(req, "lookup_from", None) is not None:
+        raise ValueError("a sparse query with lookup_from=... is not built")
+    if not _is_int(req.limit):
+        raise ValueError("a sparse query needs an int limit")
+    return vec, getattr(req, "using", None), col.compile_filter(req.filter), int(req.limit)
+
+
+def dense_using(col: Collection, req) -> None:
+    """ValueError for a dense query that names a vector: `using` selects the sparse vector and
+    goes with a SparseVector query."""
+    using = getattr(req, "using", None)
+    if using not in (None, ""):
+        raise ValueError(f"using={using!r} with a dense query vector: `using` names the sparse "
+                         f"vector of a collection and goes with query=SparseVector(...); drop it "
+                         "for a dense query")
 
 
 def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=False) -> list:
@@ -277,6 +393,10 @@ def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=Fals
     if route == RECOMMEND:
         return col.search_points_recommend([recommend_request(col, r) for r in reqs],
                                            with_vectors)
+    if route == SPARSE:
+        return col.search_points_sparse([sparse_request(col, r) for r in reqs], with_vectors)
+    for r in reqs:
+        dense_using(col, r)
     qs, filters, limits, div, cand = [], [], [], [], []
     for r in reqs:
         q, mmr = nearest_of(r.query)
@@ -357,19 +477,26 @@ class QdrantClient:
 
     def create_collection(self, collection_name: str, vectors_config: models.VectorParams,
                           payload_tag_fields: Iterable[str] = DEFAULT_TAG_FIELDS,
-                          capacity: int = 1024, payload_range_fields=None, **kwargs) -> bool:
+                          capacity: int = 1024, payload_range_fields=None,
+                          sparse_vectors_config=None, sparse_slots: int = SPARSE_SLOTS,
+                          **kwargs) -> bool:
         """`payload_range_fields`: the numeric payload fields `range` conditions may name, a
         mapping of field to "number" / "datetime" or a sequence of number fields
-        (Collection(range_fields=...)); create_payload_index adds one later."""
+        (Collection(range_fields=...)); create_payload_index adds one later.
+        `sparse_vectors_config`: {name: SparseVectorParams(...)}, the collection's one named
+        sparse vector (sparse_config), stored in `sparse_slots` slots per point (a multiple of 16
+        in [16, 512]): the most nonzeros a point's sparse vector may hold."""
         if vectors_config.distance != models.Distance.COSINE:
             raise NotImplementedError("only Distance.COSINE collections (database.py:126)")
         storage = _storage_of(vectors_config)
+        sparse = sparse_config(sparse_vectors_config, sparse_slots)
         with self._lock:
             if collection_name in self._collections:
                 raise ValueError(f"collection {collection_name!r} already exists")
             col = Collection(collection_name, int(vectors_config.size), self.device,
                              tuple(payload_tag_fields), capacity, storage,
-                             devices=self.devices, range_fields=payload_range_fields)
+                             devices=self.devices, range_fields=payload_range_fields,
+                             sparse=sparse)
             col.coalescer.window = self.coalesce_window_s
             self._collections[collection_name] = col
         return True
@@ -430,7 +557,8 @@ class QdrantClient:
             pls = [p.payload for p in points]
         if not ids:
             return models.UpdateResult(operation_id=col.op, status=models.UpdateStatus.COMPLETED)
-        op = col.upsert(ids, vecs, pls)
+        vecs, sparse = split_vectors(col, ids, vecs)
+        op = col.upsert(ids, vecs, pls) if sparse is None else col.upsert(ids, vecs, pls, sparse)
         return models.UpdateResult(operation_id=op, status=models.UpdateStatus.COMPLETED)
 
     def delete(self, collection_name: str, points_selector, wait: bool = True,
@@ -493,6 +621,8 @@ class QdrantClient:
         pass over the examples are passes of their own."""
         col = self._col(collection_name)
         route = route_of(query, prefetch)
+        if route == PLAIN and kwargs.get("using") not in (None, ""):
+            dense_using(col, models.QueryRequest(query=query, using=kwargs.get("using")))
         if route == PLAIN and self.coalesce and 1 <= int(limit) <= MAX_K and not with_vectors:
             flt = col.compile_filter(query_filter)
             q = stack_queries([nearest_of(query)[0]], col.dim, one=True, host=True)[0]
@@ -516,13 +646,15 @@ class QdrantClient:
         MMR launch — unless a plain limit exceeds RAG_MMR_MAX_CANDIDATES, in which case the
         plain requests are searched on their own."""
         col = self._col(collection_name)
-        routes: dict = {FUSION: [], FORMULA: [], ORDER: [], RECOMMEND: [], PLAIN: [], MMR: []}
+        routes: dict = {FUSION: [], FORMULA: [], ORDER: [], RECOMMEND: [], SPARSE: [], PLAIN: [],
+                        MMR: []}
         for i, r in enumerate(requests):
             routes[route_of(r.query, getattr(r, "prefetch", None))].append(i)
         if routes[MMR] and all(int(requests[i].limit) <= MMR_MAX_CANDIDATES
                                for i in routes[PLAIN]):
             routes = {FUSION: routes[FUSION], FORMULA: routes[FORMULA], ORDER: routes[ORDER],
-                      RECOMMEND: routes[RECOMMEND], MMR: sorted(routes[MMR] + routes[PLAIN])}
+                      RECOMMEND: routes[RECOMMEND], SPARSE: routes[SPARSE],
+                      MMR: sorted(routes[MMR] + routes[PLAIN])}
         out: list = [None] * len(requests)
         for route, members in routes.items():
             if members:
@@ -555,6 +687,9 @@ class QdrantClient:
             raise ValueError("a grouped query cannot be a RecommendQuery: grouped recommend is "
                              "not built")
         query, mmr = nearest_of(query)
+        if isinstance(query, models.SparseVector):
+            raise ValueError("a grouped query cannot be a SparseVector query: grouped sparse "
+                             "search is not built")
         if mmr is not None:
             raise ValueError("a grouped query cannot be an MMR query (NearestQuery.mmr)")
         flt = col.compile_filter(query_filter)

@@ -40,7 +40,40 @@ class VectorParams:
 
 
 @dataclass
+class SparseVector:
+    """A sparse vector: values[i] at index indices[i]. Indices are distinct integers in
+    [0, 65535) here (Qdrant: uint32), values finite; explicit zeros are dropped."""
+    indices: list
+    values: list
+
+
+@dataclass
+class SparseIndexParams:
+    """Accepted and ignored (the sparse rows are scored flat, in HBM) except for `datatype`:
+    anything but float32 is NotImplementedError."""
+    full_scan_threshold: Optional[int] = None
+    on_disk: Optional[bool] = None
+    datatype: Optional[str] = None
+
+
+class Modifier(str, enum.Enum):
+    NONE = "none"
+    IDF = "idf"
+
+
+@dataclass
+class SparseVectorParams:
+    """One named sparse vector of create_collection(sparse_vectors_config={name: ...}).
+    modifier Modifier.IDF: query weights are multiplied by the term's inverse document frequency
+    (ragmi.sparse.idf_weights)."""
+    index: Optional[SparseIndexParams] = None
+    modifier: Optional[Modifier] = None
+
+
+@dataclass
 class PointStruct:
+    """`vector`: the dense vector, or in a collection with a sparse vector a dict {"": dense,
+    name: SparseVector}."""
     id: ExtendedPointId
     vector: Any
     payload: Optional[dict] = None
@@ -285,11 +318,13 @@ class RrfQuery:
 @dataclass
 class Prefetch:
     """One candidate list of a fusion or formula query: the `limit` nearest points to `query` (a vector,
-    or a NearestQuery without mmr) under `filter`. A nested `prefetch` is refused."""
+    or a NearestQuery without mmr) under `filter`. A nested `prefetch` is refused. In a fusion
+    query `query` may be a SparseVector with `using` naming the collection's sparse vector."""
     query: Any = None
     filter: Optional[Filter] = None
     limit: int = 10
     prefetch: Any = None
+    using: Any = None
 
 
 # ---- formula queries (score boosting): the expression tree of FormulaQuery.formula. An
@@ -457,7 +492,8 @@ class FacetResponse:
 class QueryRequest:
     """Batched query entry for query_batch_points (one per request of a micro-batch); `query`
     is a vector or a NearestQuery, or with `prefetch` a FusionQuery / RrfQuery / FormulaQuery,
-    or a RecommendQuery. `using` and `lookup_from` exist to be refused where they are set."""
+    or a RecommendQuery, or a SparseVector with `using` naming the collection's sparse vector.
+    `lookup_from` exists to be refused where it is set."""
     query: Any
     filter: Optional[Filter] = None
     limit: int = 10

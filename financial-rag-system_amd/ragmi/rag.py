@@ -16,6 +16,9 @@ plus the batched forms a rewritten main2.batch_processor uses (SURVEY §8f rows 
   rerank_batch    -> one cross-encoder forward for all (query, chunk) pairs of a micro-batch
 and, not in the reference:
   similar_chunks  -> the chunks most like some chunks and least like others (recommend query)
+  hybrid retrieval -> ensure_collection(hybrid=True), chunk_points(sparse=True) and
+                     retrieve_from_qdrant(hybrid_text=...): a BM25 sparse vector "bm25" beside
+                     the dense one, fused by reciprocal rank (ragmi.sparse, DESIGN R19)
 
 Models come from local directories (env RAGMI_BGE_DIR, RAGMI_CE_DIR: config.json +
 model.safetensors + vocab.txt) — the reference's hub names cannot be fetched here. Env
@@ -145,18 +148,34 @@ def _query(vector, diversity, candidates):
 
 
 FUSION_PREFETCH = 50         # a rewrite's list is max(limit, this) hits long
+SPARSE_NAME = "bm25"         # the sparse vector of a hybrid collection (ensure_collection)
 
 
-def _fusion(vector, rewrites, flt, limit, rrf_k, diversity, candidates):
+def sparse_texts(texts, kind: str) -> list:
+    """The BM25 SparseVector of each text, from the embedder's own WordPiece vocabulary:
+    kind "document" (ragmi.sparse.bm25_document) or "query" (bm25_query)."""
+    from .sparse import bm25_document, bm25_query, sequences
+    ids, _, cu = get_embedder().tokenizer.encode_packed(list(texts))
+    make = bm25_document if kind == "document" else bm25_query
+    return [make(seq) for seq in sequences(ids, cu)]
+
+
+
+def _fusion(vector, rewrites, flt, limit, rrf_k, diversity, candidates, sparse=None):
     """(query, prefetch) of a multi-query retrieval: the original vector and each rewrite become
     one Prefetch under the request's filter, fused by reciprocal rank (rrf_k None: the default
-    constant)."""
+    constant). `sparse` (a SparseVector): one sparse prefetch of the same filter and limit more
+    (hybrid retrieval)."""
     if diversity is not None or candidates is not None:
         raise ValueError("rewrites (fusion) cannot be combined with diversity / candidates (MMR)")
     query = (models.FusionQuery(fusion=models.Fusion.RRF) if rrf_k is None else
              models.RrfQuery(rrf=models.Rrf(k=rrf_k)))
-    return query, [models.Prefetch(query=v, filter=flt, limit=max(limit, FUSION_PREFETCH))
-                   for v in [vector, *rewrites]]
+    prefetch = [models.Prefetch(query=v, filter=flt, limit=max(limit, FUSION_PREFETCH))
+                for v in [vector, *rewrites]]
+    if sparse is not None:
+        prefetch.append(models.Prefetch(query=sparse, using=SPARSE_NAME, filter=flt,
+                                        limit=max(limit, FUSION_PREFETCH)))
+    return query, prefetch
 
 
 RECENCY_PREFETCH = 50        # a recency boost re-scores max(limit, this) hits
@@ -189,7 +208,7 @@ def _recency(vector, recency, recency_now, flt, limit, diversity, candidates, re
 def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEVE_LIMIT, *,
                          diversity=None, candidates=None, rewrites=None, rrf_k=None,
                          ingested_since=None, ingested_until=None, recency=None,
-                         recency_now=None):
+                         recency_now=None, hybrid_text=None):
     """ingested_since / ingested_until (keyword-only, not in the reference): only chunks whose
     `ingested_at` timestamp lies in [since, until) — RFC 3339 strings or datetime / date objects,
     either may be None; a DatetimeRange on `ingested_at` joins the `must` list. The collection
@@ -208,9 +227,28 @@ def retrieve_from_qdrant(query_vector, ticker, document_type=None, limit=RETRIEV
     half_life_days), age measured from `recency_now` (a datetime or RFC 3339 string; None = the
     current UTC time) to the chunk's `ingested_at`, and cut to `limit`. The collection needs
     `ingested_at` declared a datetime range field, as for ingested_since. None is today's call;
-    with rewrites or diversity / candidates it is a ValueError."""
+    with rewrites or diversity / candidates it is a ValueError.
+    hybrid_text (keyword-only, not in the reference): the question's text; its BM25 query vector
+    (the distinct WordPiece terms, weighted by the collection's IDF) becomes one sparse prefetch
+    of the same filter and limit beside the dense one(s), fused by reciprocal rank as rewrites
+    are. The collection needs the sparse vector "bm25" (ensure_collection(hybrid=True)) and
+    chunks ingested with chunk_points(sparse=True). None is today's call; with recency or
+    diversity / candidates it is a ValueError."""
     if _testing():
         return type("obj", (object,), {"points": []})
+    if hybrid_text is not None:
+        if recency is not None:
+            raise ValueError("hybrid_text (fusion) cannot be combined with recency (a formula "
+                             "query)")
+        query, prefetch = _fusion(query_vector, rewrites or [],
+                                  _filter(ticker, document_type, ingested_since, ingested_until),
+                                  limit, rrf_k, diversity, candidates,
+                                  sparse=sparse_texts([hybrid_text], "query")[0])
+        try:
+            return get_qdrant().query_points(collection_name=COLLECTION_NAME, query=query,
+                                             prefetch=prefetch, limit=limit)
+        except Exception:
+            return type("obj", (object,), {"points": []})
     if recency is not None:
         query, prefetch = _recency(query_vector, recency, recency_now,
                                    _filter(ticker, document_type, ingested_since, ingested_until),
@@ -328,12 +366,17 @@ def rerank_batch(queries, texts_lists, top_k):
 
 
 # ------------------------------------------------------------------ ingest
-def ensure_collection(qdrant, collection_name=COLLECTION_NAME):
-    """ingest.py:86-96 / database.py:111-143."""
+def ensure_collection(qdrant, collection_name=COLLECTION_NAME, hybrid=False):
+    """ingest.py:86-96 / database.py:111-143. hybrid=True (not in the reference): the collection
+    also declares the sparse vector "bm25" with Modifier.IDF, for chunk_points(sparse=True) and
+    retrieve_from_qdrant(hybrid_text=...)."""
     if not qdrant.collection_exists(collection_name):
+        extra = {} if not hybrid else {"sparse_vectors_config": {
+            SPARSE_NAME: models.SparseVectorParams(modifier=models.Modifier.IDF)}}
         qdrant.create_collection(collection_name=collection_name,
                                  vectors_config=models.VectorParams(size=VECTOR_SIZE,
-                                                                    distance=models.Distance.COSINE))
+                                                                    distance=models.Distance.COSINE),
+                                 **extra)
 
 
 def embed_chunks(chunks, batch=EMBED_BATCH):
@@ -344,12 +387,17 @@ def embed_chunks(chunks, batch=EMBED_BATCH):
     return out
 
 
-def chunk_points(ticker, f_type, file, chunks, embeddings, ingested_at=None):
-    """ingest.py:148-168: md5 point ids (idempotent re-ingest) + payloads."""
+def chunk_points(ticker, f_type, file, chunks, embeddings, ingested_at=None, sparse=False):
+    """ingest.py:148-168: md5 point ids (idempotent re-ingest) + payloads. sparse=True (not in
+    the reference): every point's vector is {"": dense, "bm25": bm25_document of the chunk}, for a
+    collection made by ensure_collection(hybrid=True)."""
     ts = ingested_at or datetime.now(timezone.utc).isoformat()
     pts = []
-    for chunk, vector in zip(chunks, embeddings):
+    bm25 = sparse_texts(chunks, "document") if sparse else None
+    for n, (chunk, vector) in enumerate(zip(chunks, embeddings)):
         h = hashlib.md5(f"{ticker}_{f_type}_{file}_{chunk}".encode()).hexdigest()
+        if bm25 is not None:
+            vector = {"": vector, SPARSE_NAME: bm25[n]}
         pts.append(models.PointStruct(id=h, vector=vector, payload={
             "ticker": ticker.upper(), "document_type": f_type.upper(), "text": chunk,
             "source_file": file, "ingested_at": ts}))

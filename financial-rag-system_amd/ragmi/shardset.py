@@ -274,6 +274,12 @@ class ShardSet(ListOps):
             self._settle(shard)
         self._count = int(new_count)
 
+    # ---------------------------------------------------------------- sparse column
+    def sparse_create(self, slots: int = 128) -> None:
+        """Not built: a sparse search over several shards needs its own merge (the precedent:
+        recommend). A collection with a sparse vector lives on one FlatIndex."""
+        raise NotImplementedError("sparse vectors over a shard set are not built")
+
     # ---------------------------------------------------------------- key columns
     @_keeps_device
     def keys_create(self, n_cols: int) -> None:

@@ -15,9 +15,14 @@ A collection directory adds the host-side state of `collection.Collection`:
 
   collection.json    name, dim, distance, tag fields + codebooks, op counter, and
                      "range_fields": [[field, kind], ...] when the collection has range fields
-                     (their key columns are not saved: load re-derives them from the payloads)
+                     (their key columns are not saved: load re-derives them from the payloads);
+                     "sparse": {"name", "modifier": "idf" | "none", "slots"} when it has a
+                     sparse vector
   points.jsonl       one line per row, in row order: {"id": ..., "version": v, "payload": {...}}
-  shard/             the shard above
+  shard/             the shard above; with a sparse vector also, as the index stores them,
+                     sparse.terms.u16.npy [N, slots] uint16 and sparse.vals.f32.npy [N, slots]
+                     float32 (optional additions: the shard version does not change, and a
+                     directory without them loads as before)
 
 Rows move host<->HBM in chunks (`chunk_rows`, default 1M rows = 768 MB at D=384) through
 memory-mapped .npy files, so a 10M-row shard never needs the whole corpus in host RAM.
@@ -214,12 +219,66 @@ def load_sharded(sharded, path: str, chunk_rows: int = CHUNK_ROWS) -> int:
     return load_into(sharded.local, path, 0, chunk_rows, rows=(sharded.lo, sharded.hi))
 
 
+# ---------------------------------------------------------------- sparse rows
+SPARSE_FILES = ("sparse.terms.u16.npy", "sparse.vals.f32.npy")
+
+
+def save_sparse(index, path: str, chunk_rows: int = CHUNK_ROWS) -> None:
+    """The sparse rows [0, count) of `index` into shard directory `path`, chunked like the
+    vectors (sparse_gather)."""
+    n, S = index.count, index.sparse_slots()
+    terms = np.lib.format.open_memmap(os.path.join(path, SPARSE_FILES[0]), mode="w+",
+                                      dtype=np.uint16, shape=(n, S))
+    vals = np.lib.format.open_memmap(os.path.join(path, SPARSE_FILES[1]), mode="w+",
+                                     dtype=np.float32, shape=(n, S))
+    for r0 in range(0, n, chunk_rows):
+        m = min(chunk_rows, n - r0)
+        t, v = index.sparse_gather(np.arange(r0, r0 + m, dtype=np.int64))
+        terms[r0:r0 + m] = t.cpu().numpy().view(np.uint16)
+        vals[r0:r0 + m] = v.cpu().numpy()
+    terms.flush()
+    vals.flush()
+
+
+def load_sparse(index, path: str, chunk_rows: int = CHUNK_ROWS) -> np.ndarray:
+    """The saved sparse rows back into `index` (sparse_write, bit for bit); returns the nonzeros
+    per row. The rows must be in the stored layout: a row that is not (a term after an empty
+    slot, terms not ascending, a value not finite) is refused, naming it."""
+    terms = np.load(os.path.join(path, SPARSE_FILES[0]), mmap_mode="r")
+    vals = np.load(os.path.join(path, SPARSE_FILES[1]), mmap_mode="r")
+    n, S = index.count, index.sparse_slots()
+    if terms.shape != (n, S) or vals.shape != (n, S):
+        raise ValueError(f"{path}: the sparse arrays are not [{n}, {S}]")
+    nnz = np.zeros(n, np.int32)
+    for r0 in range(0, n, chunk_rows):
+        m = min(chunk_rows, n - r0)
+        t, v = np.asarray(terms[r0:r0 + m]), np.asarray(vals[r0:r0 + m])
+        full = t != 0xFFFF
+        k = full.sum(axis=1)
+        t32 = t.astype(np.int64)
+        bad = (full != (np.arange(S)[None, :] < k[:, None])).any(axis=1) | \
+            ((t32[:, 1:] <= t32[:, :-1]) & full[:, 1:]).any(axis=1) | \
+            ~np.isfinite(v).all(axis=1) | ((v != 0) & ~full).any(axis=1)
+        if bad.any():
+            raise ValueError(f"{path}: sparse row {r0 + int(np.argmax(bad))} is not in the "
+                             "stored layout")
+        index.sparse_write(np.arange(r0, r0 + m, dtype=np.int64), t, v)
+        nnz[r0:r0 + m] = k
+    return nnz
+
+
 # ---------------------------------------------------------------- collections
 def save_collection(col, path: str) -> None:
     """collection.Collection -> collection directory."""
     os.makedirs(path, exist_ok=True)
     with col.lock:
-        save_index(col.index, os.path.join(path, "shard"))
+        shard = os.path.join(path, "shard")
+        save_index(col.index, shard)
+        for old in SPARSE_FILES:              # a re-save of a collection without a sparse vector
+            if os.path.exists(os.path.join(shard, old)):
+                os.remove(os.path.join(shard, old))
+        if getattr(col, "sparse_name", None) is not None:
+            save_sparse(col.index, shard)
         tmp = os.path.join(path, "points.jsonl.tmp")
         with open(tmp, "w") as f:
             for pid, ver, pl in zip(col.row_ids, col.versions, col.payloads):
@@ -231,6 +290,10 @@ def save_collection(col, path: str) -> None:
               "codebooks": [[[v, c] for v, c in t.items()] for t in col.tags.codes]}
         if len(col.ranges):      # only then: a collection without range fields saves as it did
             cj["range_fields"] = [[f, k] for f, k in zip(col.ranges.fields, col.ranges.kinds)]
+        if getattr(col, "sparse_name", None) is not None:      # only then, likewise
+            cj["sparse"] = {"name": col.sparse_name,
+                            "modifier": "idf" if col.sparse_idf else "none",
+                            "slots": col.sparse_slots}
         _write_json(os.path.join(path, "collection.json"), cj)
 
 
@@ -245,7 +308,9 @@ def load_collection(path: str, device=None, devices=None):
     col = Collection(cj["name"], int(cj["dim"]), device, tuple(cj["tag_fields"]),
                      capacity=max(meta["count"], 1024),
                      storage=cj.get("storage", meta.get("storage", "fp16")), devices=devices,
-                     range_fields=dict(cj.get("range_fields", [])) or None)
+                     range_fields=dict(cj.get("range_fields", [])) or None,
+                     **({"sparse": (cj["sparse"]["name"], cj["sparse"]["modifier"] == "idf",
+                                    int(cj["sparse"]["slots"]))} if "sparse" in cj else {}))
     for f_i, book in enumerate(cj["codebooks"]):
         col.tags.codes[f_i] = {v: int(c) for v, c in book}
     with open(os.path.join(path, "points.jsonl")) as f:
@@ -268,4 +333,6 @@ def load_collection(path: str, device=None, devices=None):
         for c in range(len(col.ranges)):
             col.index.write_keys(c, np.arange(r0, r0 + m, dtype=np.int64),
                                  np.ascontiguousarray(keys[:, c]))
+    if "sparse" in cj:
+        col.sparse_len = load_sparse(col.index, os.path.join(path, "shard")).tolist()
     return col

@@ -655,6 +655,78 @@ int rag_index_write_keys(rag_index_t* index, int col, const int64_t* rows_dev,
 int rag_index_gather_keys(rag_index_t* index, int col, const int64_t* rows_dev, int64_t n,
                           int64_t* out_keys_dev, void* stream);
 
+/* Sparse vectors (a named sparse vector beside the dense one: Qdrant's sparse_vectors_config,
+ * SparseVector queries and hybrid prefetches). An index holds 0 or 1 sparse
+ * column of S slots per row, S a multiple of 16 in [16, RAG_SPARSE_MAX_SLOTS], fixed when the
+ * column is created: terms uint16 [capacity][S] and values fp32 [capacity][S]. A stored row
+ * holds its nonzero entries in ascending term order, no term twice, every value finite, terms in
+ * [0, 65535); the remaining slots hold RAG_SPARSE_TERM_NONE with value 0. The callers keep these
+ * rules (ragmi.collection refuses what breaks them); the kernels read a row up to its first empty
+ * slot. Deviations from Qdrant, all refused by the host layer and never truncated: indices are
+ * below 65535 (Qdrant: uint32), a point holds at most S nonzeros, a query at most
+ * RAG_SPARSE_MAX_QUERY_NNZ, a collection one sparse name, and shard sets hold none.
+ *
+ * Score. score(q, r) = the sum, over the slots of r in stored order whose term occurs in q, of
+ * (double)val_r * (double)w_q, accumulated in fp64 in that order and rounded once to fp32, -0.0
+ * taken as +0.0. Both factors are fp32, so every product is exact in fp64 and a fused
+ * multiply-add gives the bits of a multiply and an add: a numpy loop reproduces the score bit
+ * for bit. A row is eligible when it is < count, passes the filter and shares at least one term
+ * with the query; a row without a shared term is no hit even when k exceeds the matches
+ * (Qdrant's sparse semantics), so a point without a sparse vector is never one. Result: the k
+ * best eligible rows by (score desc, row asc), -inf / -1 past them — rag_index_search's order
+ * and padding; ids are id_offset + row.
+ *
+ * rag_index_sparse_create: make the index hold the column; a second call with the same `slots`
+ * is a no-op, another slot count RAG_EINVAL. New rows are empty. Synchronises the device.
+ * rag_index_sparse_slots: S, or 0 without a column (and for NULL).
+ * rag_index_sparse_write: row rows_dev[i] = (terms_dev, vals_dev)[i] (uint16 / fp32 [n][S], the
+ * slot layout above; distinct rows). A row outside [0, capacity) is skipped, never dereferenced.
+ * rag_index_sparse_gather: the stored rows back, an empty row for a row outside [0, capacity).
+ * rag_index_sparse_df: out_df_dev[t] (int64 [65535], device; zeroed by the call) = the rows
+ * < count that hold term t. One streaming pass over the terms, integer atomics only: the same
+ * bits on every run.
+ * rag_index_sparse_search: B queries, padded: q_terms_dev uint16 [B][64] ascending, q_vals_dev
+ * fp32 [B][64], q_nnz_dev int32 [B] (read clamped to [0, 64]; a term >= 65535 matches nothing).
+ * Filters follow rag_index_search / rag_index_search_view: progs_dev NULL (words = n_programs =
+ * 0): filters_dev [B][2] (or NULL) over the stored tags; else over the blob's filter view.
+ * k <= RAG_MAX_K_LARGE takes the hot pass — up to 32 queries share one stream of the sparse
+ * rows: their distinct terms form a bitmap and a weight table in LDS, a sample of 16-row tiles
+ * gives each query a threshold that every top-k row reaches (the k-th largest tile maximum),
+ * the rows at or above it are collected with their scores (at most 16384 kept) and the k best
+ * emitted. A query with more than 16384 rows at or above its last threshold is left unanswered
+ * (-inf / -1, counted in rag_index_unanswered), and so is every query of a pass (32 consecutive
+ * queries) whose distinct terms exceed RAG_SPARSE_MAX_UNION: the host layer groups queries so
+ * that none does, and re-runs an unanswered query with RAG_SEARCH_FULL. flags RAG_SEARCH_FULL,
+ * or k > RAG_MAX_K_LARGE: the full pass, one query at a time (every row scored, the stable sort
+ * and emit of rag_index_search_full), which always answers. Both give the same lists bit for bit.
+ * write, gather, df and search are asynchronous on `stream`, under the handle's lock; every
+ * argument error (a NULL pointer, no column, k < 1, unknown flags, the program rules of
+ * rag_index_search_view) is refused on the host before any HIP call.
+ *
+ * The sparse row is a stored form of the row, as a key is: rag_index_move_rows moves it with the
+ * dense row (a kernel of its own on the same stream under the same hold of the lock, launched
+ * only when the column exists), rag_index_reserve regrows the column (old rows kept, new rows
+ * empty), rag_index_destroy frees it. rag_index_upsert, the imports, rag_index_gather_rows and
+ * rag_index_scatter_rows do NOT touch it: the host layer writes the sparse row of every point it
+ * upserts, an empty one when the point has none. Rows at or past the count are unspecified and
+ * never eligible. No reference counterpart: the reference retrieves by one dense vector. */
+#define RAG_SPARSE_TERM_NONE 0xFFFFu
+#define RAG_SPARSE_MAX_SLOTS 512
+#define RAG_SPARSE_MAX_QUERY_NNZ 64
+#define RAG_SPARSE_MAX_UNION 512
+int rag_index_sparse_create(rag_index_t* index, int slots);
+int rag_index_sparse_slots(const rag_index_t* index);
+int rag_index_sparse_write(rag_index_t* index, const int64_t* rows_dev, const uint16_t* terms_dev,
+                           const float* vals_dev, int64_t n, void* stream);
+int rag_index_sparse_gather(rag_index_t* index, const int64_t* rows_dev, int64_t n,
+                            uint16_t* out_terms_dev, float* out_vals_dev, void* stream);
+int rag_index_sparse_df(rag_index_t* index, int64_t* out_df_dev, void* stream);
+int rag_index_sparse_search(rag_index_t* index, const uint16_t* q_terms_dev,
+                            const float* q_vals_dev, const int32_t* q_nnz_dev, int B, int k,
+                            const uint32_t* progs_dev, int64_t words, int n_programs,
+                            const uint32_t* filter_dev, int64_t id_offset, int flags,
+                            float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+
 /* Payload queries (QdrantClient.scroll, order_by, facet): ranking and counting over the tag and
  * key columns, with no vector in play. All three take a filter the way
  * rag_index_select_rows_view does: progs_dev == NULL means every row < count; otherwise ONE
