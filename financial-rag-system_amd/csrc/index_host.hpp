@@ -245,6 +245,9 @@ struct rag_index {
   // (rag_index_reco_stats)
   int64_t reco_hot = 0, reco_full = 0;
   ragmi::Workspace* reco_last = nullptr;
+  // the same for discover / context passes (rag_index_discover_stats): counters of their own
+  int64_t disc_hot = 0, disc_full = 0;
+  ragmi::Workspace* disc_last = nullptr;
   int n_cu = 256;
   int max_wgs = 0;        // scan workgroups at full occupancy
   int scan_wgs = 0;       // D <= 384 scan grid cap: 3/4 of the CUs (scan_grid)

@@ -12,6 +12,7 @@
 #include "merge_kernels.hip"
 #include "largek_kernels.hip"
 #include "reco_kernels.hip"
+#include "discover_kernels.hip"
 #include "sparse_kernels.hip"
 #include "reselect_kernels.hip"
 #include "formula_kernels.hip"
@@ -872,16 +873,16 @@ int launch_reco_hot(rag_index* h, Workspace& w, const RecoArgs& r, const PassArg
   return RAG_OK;
 }
 
-// The full pass of one BEST / SUM request, any k: every row's exact combined score, the full
-// pass's stable sort and emit (launch_full_pass). No thresholds: nothing can overflow.
-template <int D>
-int launch_reco_full(rag_index* h, Workspace& w, const RecoArgs& r, const PassArgs& a,
-                     hipStream_t st) {
-  if (const int rc = launch_reco_prep<D>(h, w, r, st)) return rc;
+// The full pass of a request whose every row `score` scores exactly (recommend, discover), any
+// k: score(grid, keys, rows, n_match) launches the score kernel (reco_full_score_kernel's
+// outputs), then the full pass's stable sort and emit (launch_full_pass). No thresholds: nothing
+// can overflow. `what` names the request in the error.
+template <typename ScoreFn>
+int launch_scored_full(rag_index* h, Workspace& w, const PassArgs& a, hipStream_t st,
+                       const char* what, ScoreFn score) {
   const int n = (int)h->count, k = a.k;
   const dim3 egrid((unsigned)std::min<int64_t>(1024, ((int64_t)k + 255) / 256));
   StreamScratch scratch(st);
-  ++h->reco_full;
   if (n == 0) {
     RAG_HIP(scratch.alloc(4));
     RAG_HIP(hipMemsetAsync(scratch.p, 0, 4, st));
@@ -907,18 +908,32 @@ int launch_reco_full(rag_index* h, Workspace& w, const RecoArgs& r, const PassAr
   RAG_HIP(hipMemsetAsync(n_match, 0, 4, st));
   // one wave per reco_group rows per step; up to 8 workgroups per CU (launch_full_pass)
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(8 * h->n_cu, (n + 3) / 4));
-  with_filter(a.filt, [&](auto f) {
-    reco_full_score_kernel<D, decltype(f)::value><<<dim3(grid), dim3(256), 0, st>>>(
-        h->corpus, a.tags, a.filt, w.qn, r.P, r.N, r.strat, n, h->rows32, k_in, v_in, n_match);
-  });
+  score(grid, k_in, v_in, n_match);
   if (hipGetLastError() != hipSuccess ||
       sort_pairs_desc(buf + t_off, tmp_bytes, k_in, k_out, v_in, v_out, n, st) != hipSuccess)
-    return ragmi::fail(RAG_EHIP, "recommend full pass: score / sort launch failed");
+    return ragmi::fail(RAG_EHIP, what);
   full_emit_kernel<<<egrid, dim3(256), 0, st>>>(k_out, v_out, n_match, k, a.id_offset, a.out_s,
                                                 a.out_i, nullptr);
   RAG_HIP(hipGetLastError());
   (void)hipMemsetAsync(w.fb_tier, 0, 4, st);   // certified by construction
   return RAG_OK;
+}
+
+// The full pass of one BEST / SUM request
+template <int D>
+int launch_reco_full(rag_index* h, Workspace& w, const RecoArgs& r, const PassArgs& a,
+                     hipStream_t st) {
+  if (const int rc = launch_reco_prep<D>(h, w, r, st)) return rc;
+  ++h->reco_full;
+  return launch_scored_full(
+      h, w, a, st, "recommend full pass: score / sort launch failed",
+      [&](int grid, uint32_t* k_in, int* v_in, int* n_match) {
+        with_filter(a.filt, [&](auto f) {
+          reco_full_score_kernel<D, decltype(f)::value><<<dim3(grid), dim3(256), 0, st>>>(
+              h->corpus, a.tags, a.filt, w.qn, r.P, r.N, r.strat, (int)h->count, h->rows32, k_in,
+              v_in, n_match);
+        });
+      });
 }
 
 // AVERAGE_VECTOR's target of a request in w.reco_q's tail (reco_average_kernel)
@@ -952,6 +967,142 @@ int recommend_locked(rag_index* h, const RecoArgs& r, int k, const uint32_t* fil
   return with_dim(h->dim, [&](auto d) {
     constexpr int D = decltype(d)::value;
     return full ? launch_reco_full<D>(h, w, r, a, st) : launch_reco_hot<D>(h, w, r, a, st);
+  });
+}
+
+// ---- discovery queries (discover_kernels.hip; the contract: ragmi.h "Discovery queries") ----
+
+// one request: the target ([dim] fp32, device; NULL: a context search) and its n pairs
+// (pos / neg [n][dim])
+struct DiscArgs {
+  const float* target;
+  const float* pos;
+  const float* neg;
+  int n;
+  int kind() const { return target ? kDiscover : kContext; }
+};
+
+// the argument rules of the discover entry points, checked before any HIP call
+int disc_args(const DiscArgs& r) {
+  static_assert(kDiscMaxPairs == RAG_DISCOVER_MAX_PAIRS && kCtxMaxPairs == RAG_CONTEXT_MAX_PAIRS &&
+                    kCtxMaxPairs == kRecoSide && kDiscTargetSlot == kDiscMaxPairs &&
+                    2 * kCtxMaxPairs == kQ,
+                "discover_kernels.hip's slots: pair i in slots i and 16 + i, the target in 15");
+  if (r.target) {
+    if (r.n < 0 || r.n > RAG_DISCOVER_MAX_PAIRS)
+      return ragmi::fail(RAG_ERANGE,
+                         "discover: a request with a target holds 0 to "
+                         "RAG_DISCOVER_MAX_PAIRS=15 pairs");
+  } else {
+    if (r.n == 0)
+      return ragmi::fail(RAG_EINVAL, "discover: a context search (no target) needs a pair");
+    if (r.n < 0 || r.n > RAG_CONTEXT_MAX_PAIRS)
+      return ragmi::fail(RAG_ERANGE,
+                         "discover: a context search holds 1 to RAG_CONTEXT_MAX_PAIRS=16 pairs");
+  }
+  if (r.n > 0 && (!r.pos || !r.neg))
+    return ragmi::fail(RAG_EINVAL, "discover: a NULL pair pointer");
+  return RAG_OK;
+}
+
+// the request's query block in w (recommend's buffers): slots assembled, prepared by qprep, and
+// the request's parameters
+template <int D>
+int launch_disc_prep(rag_index* h, Workspace& w, const DiscArgs& r, hipStream_t st) {
+  static_assert(D <= 1024, "reco_q holds [32][1024]");
+  if (const int rc = ensure_reco(w)) return rc;
+  disc_assemble_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(r.target, r.pos, r.neg, r.n, w.reco_q);
+  qprep_kernel<D><<<dim3(kQ), dim3(64), 0, st>>>(w.reco_q, kQ, nullptr, w.qn, w.qfrag, w.filt,
+                                                  w.eps, store_eps(h));
+  disc_prep_kernel<D><<<dim3(1), dim3(64), 0, st>>>(w.eps, w.qn, r.n, w.reco_par);
+  RAG_HIP(hipGetLastError());
+  return RAG_OK;
+}
+
+// go(kind tag) with the kind as a compile-time constant
+template <typename F>
+auto with_disc_kind(int kind, F&& f) {
+  if (kind == kDiscover) return f(std::integral_constant<int, kDiscover>{});
+  return f(std::integral_constant<int, kContext>{});
+}
+
+// The hot pass of one request, k <= RAG_MAX_K_LARGE (discover_kernels.hip): launch_reco_hot's
+// sequence with this feature's kernels. A saturated request (more than kLkCap rows tied at its
+// k-th score) overflows round 0 with T already at the tied score, so lk_final_kernel leaves it
+// unanswered there and the later rounds' launches return at once.
+template <int D>
+int launch_disc_hot(rag_index* h, Workspace& w, const DiscArgs& r, const PassArgs& a,
+                    hipStream_t st) {
+  if (const int rc = ensure_lk(w)) return rc;
+  if (const int rc = launch_disc_prep<D>(h, w, r, st)) return rc;
+  const int k = a.k, kind = r.kind();
+  const int n_tiles = (int)((h->count + 15) / 16);
+  // the large-k pass's sample (launch_large_k_pass)
+  const int n_sample = n_tiles == 0 ? 0 : std::min({n_tiles, std::max(4 * k, n_tiles / 32),
+                                                    kLkSampleMax});
+  const int cgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2 * h->n_cu, (n_tiles + 3) / 4));
+  const int per_wg = reco_rescore_per_wg(disc_examples(kind, r.n));
+  const int rgrid = (kLkCap + per_wg - 1) / per_wg;
+  with_filter(a.filt, [&](auto f) {
+    with_disc_kind(kind, [&](auto kd) {
+      constexpr bool F = decltype(f)::value;
+      constexpr int KIND = decltype(kd)::value;
+      if (n_sample > 0)
+        disc_sample_kernel<D, F, KIND><<<dim3((n_sample + 3) / 4), dim3(256), 0, st>>>(
+            h->corpus, a.tags, a.filt, w.qfrag, w.eps, w.reco_par, r.n, (int)h->count, n_tiles,
+            n_sample, w.lk_smax);
+      // T = the k-th largest sample maximum (L is a bound already: the eps it subtracts is 0)
+      lk_bound_kernel<<<dim3(1), dim3(256), 0, st>>>(w.lk_smax, n_sample, k, w.reco_par,
+                                                     w.lk_thr, w.lk_cnt, w.lk_again, w.lk_need);
+      for (int round = 0; round < kLkRounds; ++round) {
+        disc_collect_kernel<D, F, KIND><<<dim3(cgrid), dim3(256), 0, st>>>(
+            h->corpus, a.tags, a.filt, w.qfrag, w.eps, w.reco_par, r.n, (int)h->count, n_tiles,
+            w.lk_thr, w.lk_cnt, w.lk_cand, w.lk_again, w.lk_need, round);
+        disc_rescore_kernel<D><<<dim3(rgrid), dim3(256), 0, st>>>(
+            h->corpus, w.qn, kind, r.n, w.lk_cnt, w.lk_cand, w.lk_again, w.lk_need, round,
+            w.lk_es, h->rows32, w.reco_par);
+        lk_final_kernel<D><<<dim3(1), dim3(256), 0, st>>>(
+            h->corpus, w.qn, k, w.lk_cnt, w.lk_cand, w.lk_es, w.reco_par, w.lk_thr, w.lk_again,
+            w.lk_need, round, w.fb_tier, w.fb_cnt, a.id_offset, a.out_s, a.out_i, nullptr,
+            h->rows32);
+      }
+    });
+  });
+  RAG_HIP(hipGetLastError());
+  ++h->disc_hot;
+  h->disc_last = &w;
+  return RAG_OK;
+}
+
+// The full pass of one request, any k
+template <int D>
+int launch_disc_full(rag_index* h, Workspace& w, const DiscArgs& r, const PassArgs& a,
+                     hipStream_t st) {
+  if (const int rc = launch_disc_prep<D>(h, w, r, st)) return rc;
+  ++h->disc_full;
+  return launch_scored_full(
+      h, w, a, st, "discover full pass: score / sort launch failed",
+      [&](int grid, uint32_t* k_in, int* v_in, int* n_match) {
+        with_filter(a.filt, [&](auto f) {
+          disc_full_score_kernel<D, decltype(f)::value><<<dim3(grid), dim3(256), 0, st>>>(
+              h->corpus, a.tags, a.filt, w.qn, r.kind(), r.n, (int)h->count, h->rows32, k_in,
+              v_in, n_match);
+        });
+      });
+}
+
+// one discover / context request under the handle's lock; tags: the stored tags or a filter view
+int discover_locked(rag_index* h, const DiscArgs& r, int k, const uint32_t* filt,
+                    const uint32_t* tags, int64_t id_offset, bool full, float* out_s,
+                    int64_t* out_i, hipStream_t st) {
+  Workspace* wp = nullptr;
+  if (const int rc = take_workspace(h, st, 1, &wp)) return rc;
+  Workspace& w = *wp;
+  const PassArgs a{nullptr, 1, k, filt, tags, id_offset, out_s, out_i, nullptr};
+  full = full || k > RAG_MAX_K_LARGE;
+  return with_dim(h->dim, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    return full ? launch_disc_full<D>(h, w, r, a, st) : launch_disc_hot<D>(h, w, r, a, st);
   });
 }
 
@@ -1673,6 +1824,87 @@ int rag_index_reco_stats(rag_index_t* h, int64_t out[4]) {
     RAG_HIP(hipDeviceSynchronize());
     int32_t c[2];
     RAG_HIP(hipMemcpy(c, reinterpret_cast<const int32_t*>(h->reco_last->reco_par) + kRecoParCnt,
+                      sizeof(c), hipMemcpyDeviceToHost));
+    out[2] = c[0];
+    out[3] = c[1];
+  }
+  return RAG_OK;
+}
+
+// ---- discovery queries (discover_kernels.hip) ----
+
+int rag_index_discover(rag_index_t* h, const float* target, const float* pos, const float* neg,
+                       int n_pairs, int k, const uint32_t* progs, int64_t words, int n_programs,
+                       const uint32_t* filter, int64_t id_offset, int flags, float* out_s,
+                       int64_t* out_i, void* stream) {
+  ragmi::clear_error();
+  const DiscArgs r{target, pos, neg, n_pairs};
+  if (const int rc = disc_args(r)) return rc;
+  if (k < 1) return ragmi::fail(RAG_ERANGE, "discover: k must be >= 1");
+  if (flags & ~RAG_SEARCH_FULL) return ragmi::fail(RAG_EINVAL, "discover: unknown flags");
+  if (progs) {
+    if (const int rc = view_args(progs, words, n_programs)) return rc;
+  } else if (words != 0 || n_programs != 0) {
+    return ragmi::fail(RAG_EINVAL, "discover: programs is NULL but words / n_programs are not 0");
+  }
+  if (!out_s || !out_i) return ragmi::fail(RAG_EINVAL, "discover: a NULL output pointer");
+  if (!h) return ragmi::fail(RAG_EINVAL, "discover: index is NULL");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  // view and passes under this one hold of the lock (rag_index_search_view)
+  const uint32_t* tags = h->tags;
+  if (progs) {
+    uint32_t* v = nullptr;
+    if (const int rc = acquire_view(h, st, &v)) return rc;
+    if (const int rc = launch_filter_view(h, progs, words, n_programs, v, st)) return rc;
+    tags = v;
+  }
+  return discover_locked(h, r, k, filter, tags, id_offset, (flags & RAG_SEARCH_FULL) != 0, out_s,
+                         out_i, st);
+}
+
+int rag_index_discover_bounds(rag_index_t* h, const float* target, const float* pos,
+                              const float* neg, int n_pairs, const int64_t* rows_dev, int64_t n,
+                              float* out_lo, float* out_hi, void* stream) {
+  ragmi::clear_error();
+  const DiscArgs r{target, pos, neg, n_pairs};
+  if (const int rc = disc_args(r)) return rc;
+  if (n < 0 || (n > 0 && (!rows_dev || !out_lo || !out_hi)))
+    return ragmi::fail(RAG_EINVAL, "discover_bounds: a NULL row or output pointer");
+  if (n > 0x7fffffff) return ragmi::fail(RAG_ERANGE, "discover_bounds: n too large for one call");
+  if (!h) return ragmi::fail(RAG_EINVAL, "discover_bounds: index is NULL");
+  if (n == 0) return RAG_OK;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(h->mu);
+  RAG_HIP(hipSetDevice(h->device));
+  Workspace* wp = nullptr;
+  if (const int rc = take_workspace(h, st, 1, &wp)) return rc;
+  Workspace& w = *wp;
+  return with_dim(h->dim, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (const int rc = launch_disc_prep<D>(h, w, r, st)) return rc;
+    with_disc_kind(r.kind(), [&](auto kd) {
+      disc_bounds_kernel<D, decltype(kd)::value><<<dim3((unsigned)n), dim3(64), 0, st>>>(
+          h->corpus, w.qfrag, w.eps, w.reco_par, r.n, rows_dev, n, h->count, out_lo, out_hi);
+    });
+    RAG_HIP(hipGetLastError());
+    return (int)RAG_OK;
+  });
+}
+
+int rag_index_discover_stats(rag_index_t* h, int64_t out[4]) {
+  ragmi::clear_error();
+  if (!h || !out) return ragmi::fail(RAG_EINVAL, "discover_stats: bad args");
+  std::lock_guard<std::mutex> lk(h->mu);
+  out[0] = h->disc_hot;
+  out[1] = h->disc_full;
+  out[2] = out[3] = 0;
+  if (h->disc_last) {
+    RAG_HIP(hipSetDevice(h->device));
+    RAG_HIP(hipDeviceSynchronize());
+    int32_t c[2];
+    RAG_HIP(hipMemcpy(c, reinterpret_cast<const int32_t*>(h->disc_last->reco_par) + kDiscParCnt,
                       sizeof(c), hipMemcpyDeviceToHost));
     out[2] = c[0];
     out[3] = c[1];

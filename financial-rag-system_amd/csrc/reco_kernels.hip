@@ -299,13 +299,15 @@ __global__ __launch_bounds__(256) void reco_collect_kernel(const half8* __restri
 __host__ __device__ __forceinline__ int reco_group(int E) { return E <= 8 ? 8 : 64 / E; }
 __host__ __device__ __forceinline__ int reco_trips(int E) { return (reco_group(E) * E + 7) / 8; }
 
-template <int D, typename RowFn>
-__device__ __forceinline__ float reco_exact_group(const half8* __restrict__ corpus,
-                                                  const float* __restrict__ rows32,
-                                                  const float* __restrict__ qn, int P, int N,
-                                                  int strat, RowFn row_of, int lane) {
+// the gather half: lane p's e of pair p = g E + x, x's query slot being slot_of(x) (shared with
+// discover_kernels.hip)
+template <int D, typename SlotFn, typename RowFn>
+__device__ __forceinline__ float reco_gather_group(const half8* __restrict__ corpus,
+                                                   const float* __restrict__ rows32,
+                                                   const float* __restrict__ qn, int E,
+                                                   SlotFn slot_of, RowFn row_of, int lane) {
   constexpr int NC = 8;
-  const int E = P + N, G = reco_group(E);
+  const int G = reco_group(E);
   const int trips = reco_trips(E);
   float val = 0.0f;   // lane p holds pair p = g E + x of the group
   for (int t = 0; t < trips; ++t) {
@@ -314,7 +316,7 @@ __device__ __forceinline__ float reco_exact_group(const half8* __restrict__ corp
     for (int j = 0; j < NC; ++j) {
       const int p = t * NC + j, g = p / E, x = p - g * E;
       rows[j] = g < G ? row_of(g) : -1;
-      qoff[j] = reco_slot(x, P) * D;
+      qoff[j] = slot_of(x) * D;
     }
     float sc[NC];
     exact_scores_pairs<D, NC>(corpus, rows, qoff, qn, lane, sc, rows32);
@@ -322,6 +324,17 @@ __device__ __forceinline__ float reco_exact_group(const half8* __restrict__ corp
     for (int j = 0; j < NC; ++j)
       if (lane == t * NC + j) val = sc[j];
   }
+  return val;
+}
+
+template <int D, typename RowFn>
+__device__ __forceinline__ float reco_exact_group(const half8* __restrict__ corpus,
+                                                  const float* __restrict__ rows32,
+                                                  const float* __restrict__ qn, int P, int N,
+                                                  int strat, RowFn row_of, int lane) {
+  const int E = P + N;
+  const float val = reco_gather_group<D>(
+      corpus, rows32, qn, E, [&](int x) { return reco_slot(x, P); }, row_of, lane);
   // lane g combines pairs g E .. g E + E - 1 in example order, positives first
   float mp = kNegInf, mn = kNegInf;
   double sum = 0.0;

@@ -171,6 +171,12 @@ INDEX_API = {
     "rag_index_reco_vector": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp,
                                              c_vp]),
     "rag_index_reco_stats": (ctypes.c_int, [c_vp, c_i64p]),
+    "rag_index_discover": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int,
+                                          c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.c_int64,
+                                          ctypes.c_int, c_vp, c_vp, c_vp]),
+    "rag_index_discover_bounds": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp,
+                                                 ctypes.c_int64, c_vp, c_vp, c_vp]),
+    "rag_index_discover_stats": (ctypes.c_int, [c_vp, c_i64p]),
     "rag_index_sparse_create": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "rag_index_sparse_slots": (ctypes.c_int, [c_vp]),
     "rag_index_sparse_write": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp]),

@@ -634,11 +634,11 @@ class Collection:
                 out.append([h for h in hits if h[0] not in own][:int(limit)])
             return out
 
-    def _example_row(self, pid) -> int:
+    def _example_row(self, pid, what: str = "recommend") -> int:
         """The row of example point `pid`, or ValueError naming the id. Under the lock."""
         r = self.id_to_row.get(_norm_id(pid))
         if r is None:
-            raise ValueError(f"recommend: example point {pid!r} is not in collection "
+            raise ValueError(f"{what}: example point {pid!r} is not in collection "
                              f"{self.name!r}")
         return r
 
@@ -661,6 +661,58 @@ class Collection:
                     self.sparse_batch([vec.vector], f"{what} {l}")
                 else:
                     require_finite(host_or_tensor(vec).reshape(1, -1), what, [l])
+
+    def search_discover(self, requests: list):
+        """Discovery and context queries. `requests`: per request (target or None,
+        [(positive, negative), ...], compiled filter, limit) — every example a point id or a
+        vector, as discover_params returns them; no target: a context search. Under the lock:
+        every id resolves to its row (an unknown id is a ValueError naming it) and the example
+        rows are gathered on the device in their stored form, as search_recommend does. Each
+        request is one index.discover call for limit + m hits, m its distinct id examples, with
+        rescue — a saturated request (a context search with few pairs) is re-answered on the
+        full pass, never returned empty —: the example rows are dropped and the list is cut to
+        limit. limit < 1, an empty collection and a filter nothing can match give [] without a
+        launch. Returns per request [(row, score)], best first."""
+        if not hasattr(self.index, "discover"):                # a ShardSet has none
+            raise NotImplementedError("discover over a shard set is not built")
+        with self.lock:
+            out = []
+            for target, pairs, c, limit in requests:
+                flat = ([] if target is None else [target]) + [x for pair in pairs for x in pair]
+                by_id = {j: self._example_row(x, "discover") for j, x in enumerate(flat)
+                         if not _is_vector(x)}
+                own = set(by_id.values())
+                count = self.index.count
+                if limit < 1 or count == 0 or c is None:
+                    out.append([])
+                    continue
+                vecs = list(flat)
+                if by_id:
+                    got = self.index.gather_rows(np.asarray(list(by_id.values()), np.int64))
+                    stored = got[1] if got[1] is not None else got[0].view(torch.float16).float()
+                    for j, v in zip(by_id, stored):
+                        vecs[j] = v
+                t = None
+                if target is not None:
+                    t, vecs = stack_queries(vecs[:1], self.dim)[0], vecs[1:]
+                pos = stack_queries(vecs[0::2], self.dim) if vecs else None
+                neg = stack_queries(vecs[1::2], self.dim) if vecs else None
+                view = {}
+                if isinstance(c, FilterProgram):
+                    view = {"programs": pack_view([c]), "filters": (1, 1)}
+                elif tuple(c) != (0, 0):
+                    view = {"filters": tuple(c)}
+                k = min(int(limit) + len(own), count)
+                hits = hits_of(*(x.unsqueeze(0) for x in self.index.discover(
+                    t, pos, neg, k, rescue=True, **view)))[0]
+                out.append([h for h in hits if h[0] not in own][:int(limit)])
+            return out
+
+    def search_points_discover(self, requests: list, with_vectors=False):
+        """search_discover with every hit resolved to its ScoredPoint under the same hold of the
+        lock (_points)."""
+        with self.lock:
+            return self._points(self.search_discover(requests), with_vectors)
 
     def search_fusion(self, requests: list):
         """Fusion queries. `requests`: per request (rrf_k, [(vector, Filter or

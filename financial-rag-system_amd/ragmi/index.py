@@ -41,6 +41,8 @@ PRESCAN6_MIN_ROWS = 4000000    # RAG_PRESCAN6_MIN_ROWS: auto mode's smallest 6-b
 CREATE_DIAGNOSTIC = 0x100          # RAG_CREATE_DIAGNOSTIC: honour the RAGMI_* A/B knobs
 RECO_AVERAGE, RECO_BEST, RECO_SUM = 0, 1, 2   # RAG_RECO_AVERAGE / _BEST / _SUM
 RECO_MAX_SIDE = 16                 # RAG_RECO_MAX_SIDE: examples per side of a recommend request
+DISCOVER_MAX_PAIRS = 15            # RAG_DISCOVER_MAX_PAIRS: pairs of a discover request (a target)
+CONTEXT_MAX_PAIRS = 16             # RAG_CONTEXT_MAX_PAIRS: pairs of a context request (no target)
 RECO_STRATEGIES = {"average_vector": RECO_AVERAGE, "best_score": RECO_BEST,
                    "sum_scores": RECO_SUM}
 SPARSE_TERM_NONE = 0xFFFF          # RAG_SPARSE_TERM_NONE: the term of an empty slot
@@ -67,6 +69,15 @@ def sparse_groups(q_terms, q_nnz, max_queries: int = QUERY_TILE,
     if len(q_nnz) > b0:
         groups.append((b0, len(q_nnz)))
     return groups
+
+
+class DiscoverStats(NamedTuple):
+    """rag_index_discover_stats: discover / context passes since creation by path, and the last
+    hot pass's counted candidates (of its last round) and rounds."""
+    hot: int
+    full: int
+    candidates: int
+    rounds: int
 
 
 class RecoStats(NamedTuple):
@@ -506,6 +517,98 @@ class FlatIndex(ListOps):
         out = (ctypes.c_int64 * 4)()
         check(self._L.rag_index_reco_stats(self._h, out))
         return RecoStats(*[int(x) for x in out])
+
+    # ---------------------------------------------------------------- discover
+    def _discover_sides(self, target, pairs_pos, pairs_neg):
+        """(target tensor or None, pos tensor or None, neg tensor or None, n) of a discover /
+        context request, refused as the C ABI refuses it, but as ValueError."""
+        t = None
+        if target is not None:
+            t = _as_dev(target, torch.float32, self.device).reshape(-1)
+            if t.numel() != self.dim:
+                raise ValueError(f"target must be [{self.dim}]")
+        sides = []
+        for name, x in (("positive", pairs_pos), ("negative", pairs_neg)):
+            if x is None or len(x) == 0:
+                sides.append((None, 0))
+                continue
+            v = _as_dev(x, torch.float32, self.device)
+            if v.dim() == 1:
+                v = v.unsqueeze(0)
+            if v.dim() != 2 or v.shape[1] != self.dim:
+                raise ValueError(f"{name} examples must be [n, {self.dim}]")
+            sides.append((v, int(v.shape[0])))
+        (p, P), (n, N) = sides
+        if P != N:
+            raise ValueError(f"a context pair is one positive and one negative: got {P} "
+                             f"positives and {N} negatives")
+        limit, name = (DISCOVER_MAX_PAIRS, "RAG_DISCOVER_MAX_PAIRS") if t is not None else \
+            (CONTEXT_MAX_PAIRS, "RAG_CONTEXT_MAX_PAIRS")
+        if P > limit:
+            raise ValueError(f"at most {limit} context pairs ({name}), got {P}")
+        if t is None and P == 0:
+            raise ValueError("a context search (no target) needs at least one pair")
+        return t, p, n, P
+
+    def discover(self, target, pairs_pos, pairs_neg, k: int, filters=None, programs=None,
+                 full: bool = False, rescue: bool = False, n_programs: int | None = None,
+                 id_offset: int = 0):
+        """One discovery request (rag_index_discover; the contract: include/ragmi.h "Discovery
+        queries"): `target` a vector [dim] or None (None: a context search), `pairs_pos` /
+        `pairs_neg` the pairs' positive and negative vectors [n, dim], pair i being
+        (pairs_pos[i], pairs_neg[i]) — at most 15 with a target, 1 to 16 without. Returns
+        (scores fp32 [k], ids int64 [k]) as cuda tensors, the k best rows by (score desc, row
+        asc), -inf / -1 past the matching rows, enqueued on the current stream. Example rows are
+        not excluded (Collection.search_discover does that). `filters`, `programs`, `full` as in
+        recommend. rescue=True: a request the hot pass left unanswered (more than 16384 rows
+        tied within its bounds of the k-th best: a context search with few pairs, a zero
+        target) is re-answered on the full pass and counted in `rescued` (rescue_unanswered);
+        reads the list back, so it synchronises."""
+        t, p, n, P = self._discover_sides(target, pairs_pos, pairs_neg)
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        f = None
+        if filters is not None:
+            f = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(filters, dtype=np.uint32).reshape(2)).view(np.int32)).to(self.device)
+        view = None if programs is None else view_blob(programs, n_programs, self.device)
+
+        def launch(full_pass: bool):
+            s = torch.empty((1, k), dtype=torch.float32, device=self.device)
+            ids = torch.empty((1, k), dtype=torch.int64, device=self.device)
+            vp, words, U = (None, 0, 0) if view is None else (view[0].data_ptr(), view[1], view[2])
+            check(self._L.rag_index_discover(
+                self._h, t.data_ptr() if t is not None else None,
+                p.data_ptr() if P else None, n.data_ptr() if P else None, P, int(k), vp, words, U,
+                f.data_ptr() if f is not None else None, int(id_offset),
+                SEARCH_FULL if full_pass else 0, s.data_ptr(), ids.data_ptr(),
+                _stream_ptr(self.device)))
+            return s, ids
+
+        s, ids = launch(full)
+        if rescue and not full:
+            rescue_unanswered(self, s, ids, lambda redo: launch(True))
+        return s[0], ids[0]
+
+    def discover_bounds(self, target, pairs_pos, pairs_neg, rows):
+        """(lo, hi) fp32 [n]: the hot pass's certified bounds of the exact discover / context
+        score of stored rows `rows` (rag_index_discover_bounds, diagnostic)."""
+        t, p, n, P = self._discover_sides(target, pairs_pos, pairs_neg)
+        r = _as_dev(rows, torch.int64, self.device).reshape(-1)
+        lo = torch.empty((r.numel(),), dtype=torch.float32, device=self.device)
+        hi = torch.empty_like(lo)
+        check(self._L.rag_index_discover_bounds(
+            self._h, t.data_ptr() if t is not None else None, p.data_ptr() if P else None,
+            n.data_ptr() if P else None, P, r.data_ptr() if r.numel() else None, r.numel(),
+            lo.data_ptr(), hi.data_ptr(), _stream_ptr(self.device)))
+        return lo, hi
+
+    def discover_stats(self) -> "DiscoverStats":
+        """(hot passes, full passes, candidates the last hot pass counted, rounds it ran) —
+        rag_index_discover_stats; synchronises the device."""
+        out = (ctypes.c_int64 * 4)()
+        check(self._L.rag_index_discover_stats(self._h, out))
+        return DiscoverStats(*[int(x) for x in out])
 
     # ---------------------------------------------------------------- MMR
     def mmr(self, cand_scores, cand_rows, k: int, diversity, ncand=None,

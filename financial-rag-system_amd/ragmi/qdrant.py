@@ -9,7 +9,8 @@ Drop-in for the calls the reference makes on `qdrant_client.QdrantClient`:
                                           main.py:232-237, main2.py:163
 plus query_batch_points (one GPU scan for a whole micro-batch; main2.py:281-295 stage 2),
 the prefetch routes of query_points (FusionQuery / RrfQuery, FormulaQuery), its OrderByQuery
-and RecommendQuery routes, recommend (the legacy spelling of the latter), scroll (in storage
+and RecommendQuery routes, recommend (the legacy spelling of the latter), the DiscoverQuery /
+ContextQuery route and its legacy spelling discover, scroll (in storage
 order, or order_by a range field), facet, count (also filtered), retrieve, delete (by ids or by filter) and delete_collection.
 
 `url` is accepted and ignored: the collection lives in this process's GPU memory (the
@@ -39,8 +40,8 @@ from .collection import (Collection, SparsePrefetch, _norm_id, parse_selector,  
                          stack_queries)
 from .filters import (DEFAULT_TAG_FIELDS, PayloadTags, UnsupportedFilter,  # noqa: F401
                       compile_filter)
-from .index import (FUSION_MAX_LISTS, MAX_K, MMR_MAX_CANDIDATES, RECO_MAX_SIDE, SPARSE_SLOTS,
-                    reco_strategy)
+from .index import (CONTEXT_MAX_PAIRS, DISCOVER_MAX_PAIRS, FUSION_MAX_LISTS, MAX_K,
+                    MMR_MAX_CANDIDATES, RECO_MAX_SIDE, SPARSE_SLOTS, reco_strategy)
 from .shardset import parse_devices
 
 
@@ -232,6 +233,9 @@ def prefetch_lists(prefetch, what: str, to: str, verb: str, sparse_ok: bool = Fa
             raise ValueError(f"prefetch[{n}]: an OrderByQuery inside a Prefetch is not built")
         if isinstance(vec, models.RecommendQuery):
             raise ValueError(f"prefetch[{n}]: a RecommendQuery inside a Prefetch is not built")
+        if isinstance(vec, (models.DiscoverQuery, models.ContextQuery)):
+            raise ValueError(f"prefetch[{n}]: a {type(vec).__name__} inside a Prefetch is not "
+                             "built")
         if vec is None or is_fusion(vec) or isinstance(vec, models.FormulaQuery):
             raise ValueError(f"prefetch[{n}] needs a query: a vector or a NearestQuery")
         if mmr is not None:
@@ -261,6 +265,7 @@ def formula_params(query, prefetch, limit, query_filter=None) -> list:
 FUSION, FORMULA, MMR, PLAIN = "fusion", "formula", "mmr", "plain"   # the routes of a request
 ORDER = "order"
 RECOMMEND = "recommend"
+DISCOVER = "discover"
 SPARSE = "sparse"
 
 
@@ -269,7 +274,8 @@ def route_of(query, prefetch=None) -> str:
     FormulaQuery), FUSION (prefetched lists fused; every other use of a prefetch goes there to
     be refused), ORDER (an OrderByQuery: no vector, the points by a range field's value), MMR (a
     NearestQuery with an Mmr), RECOMMEND (a RecommendQuery, with or without a prefetch: it
-    refuses the prefetch itself), SPARSE (a SparseVector, bare or the `nearest` of a NearestQuery,
+    refuses the prefetch itself), DISCOVER (a DiscoverQuery or a ContextQuery, likewise), SPARSE (a
+    SparseVector, bare or the `nearest` of a NearestQuery,
     with or without a prefetch: it refuses the prefetch and an Mmr itself) or PLAIN."""
     if isinstance(nearest_of(query)[0], models.SparseVector):
         return SPARSE
@@ -277,6 +283,8 @@ def route_of(query, prefetch=None) -> str:
         return FORMULA
     if isinstance(query, models.RecommendQuery):
         return RECOMMEND
+    if isinstance(query, (models.DiscoverQuery, models.ContextQuery)):
+        return DISCOVER
     if isinstance(query, models.OrderByQuery):
         return ORDER
     if prefetch is not None or isinstance(query, (models.FusionQuery, models.RrfQuery)):
@@ -348,6 +356,70 @@ def recommend_request(col: Collection, req) -> tuple:
     return pos, neg, strategy, col.compile_filter(req.filter), int(req.limit)
 
 
+def discover_params(query, limit) -> tuple:
+    """(target or None, [(positive, negative), ...]) of a discovery request — every example a
+    point id or a vector; no target: a context search — or ValueError: the query must be a
+    DiscoverQuery over a DiscoverInput (a target and 0 to RAG_DISCOVER_MAX_PAIRS pairs) or a
+    ContextQuery (1 to RAG_CONTEXT_MAX_PAIRS pairs), its context one ContextPair or a list of
+    them, each with both sides; the limit must be an int."""
+    if isinstance(query, models.DiscoverQuery):
+        if not isinstance(query.discover, models.DiscoverInput):
+            raise ValueError("discover_params: query must be DiscoverQuery(discover="
+                             "DiscoverInput(target, context))")
+        target, context, most, name = query.discover.target, query.discover.context, \
+            DISCOVER_MAX_PAIRS, "RAG_DISCOVER_MAX_PAIRS"
+        if target is None:
+            raise ValueError("a DiscoverQuery needs a target; without one it is a "
+                             "ContextQuery(context=[...])")
+    elif isinstance(query, models.ContextQuery):
+        target, context, most, name = None, query.context, CONTEXT_MAX_PAIRS, \
+            "RAG_CONTEXT_MAX_PAIRS"
+    else:
+        raise ValueError("discover_params: query must be a DiscoverQuery or a ContextQuery")
+    what = type(query).__name__
+    if not _is_int(limit):
+        raise ValueError("a discovery query needs an int limit")
+    if context is None:
+        context = []
+    elif isinstance(context, models.ContextPair):
+        context = [context]
+    if isinstance(context, (str, bytes, dict)) or not hasattr(context, "__len__"):
+        raise ValueError(f"{what}: context must be a ContextPair or a list of them")
+    pairs = []
+    for n, pair in enumerate(context):
+        if not isinstance(pair, models.ContextPair):
+            raise ValueError(f"{what}: context[{n}] is not a ContextPair")
+        if pair.positive is None or pair.negative is None:
+            raise ValueError(f"{what}: context[{n}] needs a positive and a negative example")
+        pairs.append((pair.positive, pair.negative))
+    if len(pairs) > most:
+        raise ValueError(f"a {what} takes at most {most} context pairs ({name}), "
+                         f"got {len(pairs)}")
+    if target is None and not pairs:
+        raise ValueError("a ContextQuery without pairs is not built: it needs at least one "
+                         "ContextPair")
+    return target, pairs
+
+
+def discover_request(col: Collection, req) -> tuple:
+    """(target or None, pairs, compiled filter, limit) of a DISCOVER request, or ValueError:
+    prefetched candidates cannot be discovered among, discovery scores the dense vector only
+    (`using`, SparseVector examples) and knows no other collection's points (`lookup_from`)."""
+    what = type(req.query).__name__
+    if getattr(req, "prefetch", None) is not None:
+        raise ValueError(f"a {what} over prefetched candidates (prefetch=...) is not built: it "
+                         "scores every point a query_filter matches")
+    for name in ("using", "lookup_from"):
+        if getattr(req, name, None) is not None:
+            raise ValueError(f"a {what} with {name}=... is not built: discovery scores the dense "
+                             "(unnamed) vector and examples are the collection's own points")
+    target, pairs = discover_params(req.query, req.limit)
+    if any(isinstance(x, models.SparseVector) for x in [target] + [x for p in pairs for x in p]):
+        raise ValueError(f"a {what} with SparseVector examples is not built: discovery scores "
+                         "the dense vector")
+    return target, pairs, col.compile_filter(req.filter), int(req.limit)
+
+
 def sparse_request(col: Collection, req) -> tuple:
     """(SparseVector, using, compiled filter, limit) of a SPARSE request, or ValueError:
     prefetched candidates cannot be re-scored by a sparse query, MMR over a sparse vector is not
@@ -393,6 +465,8 @@ def answer(col: Collection, route: str, reqs: list, with_vectors=False, one=Fals
     if route == RECOMMEND:
         return col.search_points_recommend([recommend_request(col, r) for r in reqs],
                                            with_vectors)
+    if route == DISCOVER:
+        return col.search_points_discover([discover_request(col, r) for r in reqs], with_vectors)
     if route == SPARSE:
         return col.search_points_sparse([sparse_request(col, r) for r in reqs], with_vectors)
     for r in reqs:
@@ -616,9 +690,9 @@ class QdrantClient:
                      query_filter: models.Filter | None = None, with_payload=True,
                      with_vectors=False, prefetch=None, **kwargs) -> models.QueryResponse:
         """One request on its route (route_of, answer). A plain request with a limit the scan
-        serves rides the coalescer; fusion, formula, MMR, order_by and recommend requests never
-        do: their prefetches, their candidate search, their ranking of a key column, their
-        pass over the examples are passes of their own."""
+        serves rides the coalescer; fusion, formula, MMR, order_by, recommend and discovery
+        requests never do: their prefetches, their candidate search, their ranking of a key
+        column, their pass over the examples are passes of their own."""
         col = self._col(collection_name)
         route = route_of(query, prefetch)
         if route == PLAIN and kwargs.get("using") not in (None, ""):
@@ -638,22 +712,23 @@ class QdrantClient:
                            **kwargs) -> list[models.QueryResponse]:
         """One GPU scan for the whole batch (per-query filters ride along in the kernel). The
         requests are partitioned by route once, each non-empty route is answered by one call
-        (answer), fusion and formula first, then the order_by and the recommend requests
-        (routes of their own, answered one request at a time, in order), and the results are
-        scattered back in request order.
+        (answer), fusion and formula first, then the order_by, the recommend and the discovery
+        requests (routes of their own, answered one request at a time, in order), and the
+        results are scattered back in request order.
         With MMR requests in the batch the plain requests ride with them, at diversity 0 with their own
         limit as candidate count: one search at the batch's largest candidate count and one
         MMR launch — unless a plain limit exceeds RAG_MMR_MAX_CANDIDATES, in which case the
         plain requests are searched on their own."""
         col = self._col(collection_name)
-        routes: dict = {FUSION: [], FORMULA: [], ORDER: [], RECOMMEND: [], SPARSE: [], PLAIN: [],
-                        MMR: []}
+        routes: dict = {FUSION: [], FORMULA: [], ORDER: [], RECOMMEND: [], DISCOVER: [],
+                        SPARSE: [], PLAIN: [], MMR: []}
         for i, r in enumerate(requests):
             routes[route_of(r.query, getattr(r, "prefetch", None))].append(i)
         if routes[MMR] and all(int(requests[i].limit) <= MMR_MAX_CANDIDATES
                                for i in routes[PLAIN]):
             routes = {FUSION: routes[FUSION], FORMULA: routes[FORMULA], ORDER: routes[ORDER],
-                      RECOMMEND: routes[RECOMMEND], SPARSE: routes[SPARSE],
+                      RECOMMEND: routes[RECOMMEND], DISCOVER: routes[DISCOVER],
+                      SPARSE: routes[SPARSE],
                       MMR: sorted(routes[MMR] + routes[PLAIN])}
         out: list = [None] * len(requests)
         for route, members in routes.items():
@@ -686,6 +761,9 @@ class QdrantClient:
         if isinstance(query, models.RecommendQuery):
             raise ValueError("a grouped query cannot be a RecommendQuery: grouped recommend is "
                              "not built")
+        if isinstance(query, (models.DiscoverQuery, models.ContextQuery)):
+            raise ValueError(f"a grouped query cannot be a {type(query).__name__}: grouped "
+                             "discovery is not built")
         query, mmr = nearest_of(query)
         if isinstance(query, models.SparseVector):
             raise ValueError("a grouped query cannot be a SparseVector query: grouped sparse "
@@ -706,6 +784,16 @@ class QdrantClient:
         query_points(query=RecommendQuery(RecommendInput(positive, negative, strategy)))."""
         query = models.RecommendQuery(recommend=models.RecommendInput(
             positive=positive, negative=negative, strategy=strategy))
+        return self.query_points(collection_name, query, limit, query_filter, with_payload,
+                                 with_vectors, **kwargs).points
+
+    def discover(self, collection_name: str, target=None, context=None, query_filter=None,
+                 limit: int = 10, with_payload=True, with_vectors=False, **kwargs):
+        """Legacy qdrant_client.discover: list[ScoredPoint] of query_points with
+        DiscoverQuery(DiscoverInput(target, context)) when a target is given, else with
+        ContextQuery(context)."""
+        query = models.ContextQuery(context=context) if target is None else \
+            models.DiscoverQuery(discover=models.DiscoverInput(target=target, context=context))
         return self.query_points(collection_name, query, limit, query_filter, with_payload,
                                  with_vectors, **kwargs).points
 

@@ -290,6 +290,37 @@ class RecommendQuery:
     recommend: RecommendInput
 
 
+@dataclass
+class ContextPair:
+    """One example pair of a discovery or context query: a point id or a vector each."""
+    positive: Any
+    negative: Any
+
+
+@dataclass
+class DiscoverInput:
+    """The examples of a discovery query: `target` a point id or a vector, `context` one
+    ContextPair or a list of them (at most 15; none is allowed)."""
+    target: Any
+    context: Any = None
+
+
+@dataclass
+class DiscoverQuery:
+    """query_points(query=DiscoverQuery(discover=DiscoverInput(target, context))): the points
+    nearest the target among those on the positive side of the most context pairs; points given
+    as examples by id are never among the hits."""
+    discover: DiscoverInput
+
+
+@dataclass
+class ContextQuery:
+    """query_points(query=ContextQuery(context=[ContextPair(...), ...])): the points on the
+    positive side of every pair first (score 0), the others by how far they miss; `context` is
+    one ContextPair or a list of 1 to 16."""
+    context: Any
+
+
 class Fusion(str, enum.Enum):
     RRF = "rrf"
     DBSF = "dbsf"

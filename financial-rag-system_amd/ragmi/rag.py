@@ -16,6 +16,7 @@ plus the batched forms a rewritten main2.batch_processor uses (SURVEY §8f rows 
   rerank_batch    -> one cross-encoder forward for all (query, chunk) pairs of a micro-batch
 and, not in the reference:
   similar_chunks  -> the chunks most like some chunks and least like others (recommend query)
+  retrieve_steered -> retrieve_from_qdrant steered by (liked, disliked) chunk pairs (discovery)
   hybrid retrieval -> ensure_collection(hybrid=True), chunk_points(sparse=True) and
                      retrieve_from_qdrant(hybrid_text=...): a BM25 sparse vector "bm25" beside
                      the dense one, fused by reciprocal rank (ragmi.sparse, DESIGN R19)
@@ -291,6 +292,27 @@ def similar_chunks(point_ids, not_like=(), ticker=None, limit=RETRIEVE_LIMIT):
     query = models.RecommendQuery(recommend=models.RecommendInput(
         positive=list(point_ids), negative=list(not_like),
         strategy=models.RecommendStrategy.BEST_SCORE))
+    try:
+        return get_qdrant().query_points(collection_name=COLLECTION_NAME, query=query,
+                                         limit=limit,
+                                         query_filter=_filter(ticker) if ticker else None)
+    except Exception:
+        return type("obj", (object,), {"points": []})
+
+
+def retrieve_steered(query_vector, prefer, ticker=None, limit=RETRIEVE_LIMIT):
+    """Not in the reference: retrieve_from_qdrant steered by feedback. `prefer` is a list of
+    (liked_point_id, disliked_point_id): the `limit` chunks nearest `query_vector` among those
+    that lie on the liked side of the most pairs ("nearest to this question, but like the
+    paragraphs users up-voted rather than the ones they down-voted"), by Qdrant's discovery
+    search with the query as the target, under retrieve_from_qdrant's ticker filter when
+    `ticker` is given. The example chunks are never among the hits. Every failure reads as no
+    documents, as in retrieve_from_qdrant."""
+    if _testing():
+        return type("obj", (object,), {"points": []})
+    query = models.DiscoverQuery(discover=models.DiscoverInput(
+        target=query_vector,
+        context=[models.ContextPair(positive=p, negative=n) for p, n in prefer]))
     try:
         return get_qdrant().query_points(collection_name=COLLECTION_NAME, query=query,
                                          limit=limit,

@@ -618,6 +618,64 @@ int rag_index_reco_vector(rag_index_t* index, const float* pos_dev, int n_pos,
                           const float* neg_dev, int n_neg, float* out_v_dev, void* stream);
 int rag_index_reco_stats(rag_index_t* index, int64_t out[4]);
 
+/* Discovery queries (Qdrant's DiscoverQuery — "nearest to this target, but on the positive side
+ * of these example pairs" —, ContextQuery — the pairs alone — and client.discover; DESIGN.md
+ * R20). A request has n pairs (positive_i, negative_i) and optionally a target, each a vector of
+ * the index's dim (target_dev [dim], pos_dev / neg_dev [n_pairs][dim], fp32, device; the caller
+ * resolves point ids to stored rows with rag_index_gather_rows). Every example goes through the
+ * canonical query normalisation, exactly as a search query does, so a zero or non-finite example
+ * is the zero query; e_x(r) is the canonical exact score (fp32) of stored row r against example
+ * x — the arithmetic of every exact score of this library, never another dot product.
+ *   Discover (target given, 0 <= n <= RAG_DISCOVER_MAX_PAIRS):
+ *     rank(r) = sum_i sgn(e_pi(r) - e_ni(r)), compared on the fp32 values: each term +1, 0 or -1;
+ *     score = fp32(rank + sig(e_t(r))), sig(x) = 0.5 (x / (1 + |x|) + 1) in fp64 on the fp32
+ *     value (recommend's sig before its rounding), the add in fp64: one rounding in all.
+ *     n = 0 is allowed: the order is then the nearest search's for the target, except that rows
+ *     whose scores sig's rounding merges order by row.
+ *   Context (target NULL, 1 <= n <= RAG_CONTEXT_MAX_PAIRS):
+ *     d_i = (double)e_pi - (double)e_ni - 2^-23, m_i = min(d_i, 0), l_i = m_i / (1 + |m_i|);
+ *     score = fp32(sum_i l_i), accumulated in fp64 in pair order, one rounding. Scores are <= 0;
+ *     a score is 0 exactly when every pair has e_p - e_n >= 2^-23.
+ *   Both map -0 to +0.
+ * Result: the k best rows passing the filter by (score desc, row asc), -inf / -1 past the
+ * matching rows — rag_index_search's order and padding; ids are id_offset + row. Example points
+ * are NOT excluded here: the host layer asks for k + m and drops them.
+ * Both forms are Qdrant's scoring restated from memory of its source:
+ * parity with a Qdrant server's own arithmetic is unpinned (as for recommend, MMR and formulas).
+ * Results are exact with respect to the contract above.
+ *
+ * rag_index_discover: one request, asynchronous on `stream`, under the handle's lock; target_dev
+ * NULL makes it a context search. Filters as for rag_index_recommend: progs_dev NULL (words =
+ * n_programs = 0) for the stored tags, else the blob's filter view; filter_dev one (mask, value)
+ * pair [2] or NULL. k <= RAG_MAX_K_LARGE takes the hot pass — one MFMA stream of the fp16 rows
+ * whatever n: pair i's positive in query slot i and its negative in slot 16 + i (the target in
+ * slot 15: hence the limits), certified bounds [L, U] of every row's score, a sampled threshold,
+ * candidates (at most 16384 kept) scored exactly. A request with more than 16384 rows within its
+ * bounds of the k-th best — a context search with few pairs, whose best score 0 a large part of
+ * the corpus shares; a discover request with a zero target — is left unanswered (-inf / -1,
+ * counted in rag_index_unanswered), after one round where the tie is exact: re-run it with
+ * RAG_SEARCH_FULL. flags RAG_SEARCH_FULL, or k > RAG_MAX_K_LARGE: the full pass (every row scored
+ * exactly, sorted), which always answers. Both give the same lists bit for bit.
+ * rag_index_discover_bounds: diagnostic; out_lo_dev[i] <= exact score of rows_dev[i] <=
+ * out_hi_dev[i] as the hot pass computes them, (-inf, +inf) for a row outside [0, count).
+ * rag_index_discover_stats: out[0] hot passes and out[1] full passes since creation, out[2] the
+ * candidates the last hot pass counted in its last round, out[3] the rounds it ran; synchronises
+ * the device. Counters of their own: rag_index_reco_stats does not move.
+ * Argument errors are refused before any HIP call: a NULL side with n_pairs > 0, n_pairs above
+ * the limit for the kind, a context search with n_pairs = 0, k < 1, unknown flags, the program
+ * rules of rag_index_search_view. */
+#define RAG_DISCOVER_MAX_PAIRS 15
+#define RAG_CONTEXT_MAX_PAIRS 16
+int rag_index_discover(rag_index_t* index, const float* target_dev /* [dim] or NULL: context */,
+                       const float* pos_dev, const float* neg_dev, int n_pairs, int k,
+                       const uint32_t* progs_dev, int64_t words, int n_programs,
+                       const uint32_t* filter_dev /* [2] or NULL */, int64_t id_offset, int flags,
+                       float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+int rag_index_discover_bounds(rag_index_t* index, const float* target_dev, const float* pos_dev,
+                              const float* neg_dev, int n_pairs, const int64_t* rows_dev,
+                              int64_t n, float* out_lo_dev, float* out_hi_dev, void* stream);
+int rag_index_discover_stats(rag_index_t* index, int64_t out[4]);
+
 /* Key columns (range and datetime filters: the numeric payload fields of a collection, in HBM).
  * An index holds 0 to RAG_KEYS_MAX_COLS columns, each int64 [capacity] (8 B per row, the tag
  * array's extent: a multiple of 16 rows). A column holds KEYS: for a double x, -0.0 taken as
